@@ -8,10 +8,12 @@ forward arithmetic that keeps the full-depth logits within 1e-3 of the fp32 refe
 bf16 hi + lo operand pairs (3 MFMAs per product) on the cross-attention kv projection and to_logits; TWO fp16 MFMAs (fp16 activation x
 the weight as an fp16 hi + lo pair) on to_out x2 and the cross-attention q projection; SINGLE fp16 MFMAs (fp16 operands, fp32
 accumulate) on the Sparse3DNA q / k / v projection, FF1 (+ GEGLU gate), FF2 and both attention cores;
-the backward runs single bf16 MFMAs.  The all-bf16 mode (faster, logits ~8e-3) is timed in the same run as `fast_mode`.
+the backward runs single bf16 MFMAs.  The all-bf16 mode (faster, logits ~8e-3) is timed in a `--full` run as `fast_mode`.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: re-executes itself under torch.distributed.run)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full  (+ every side measurement and check below)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
+    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: starts itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -19,28 +21,38 @@ One "step" = embedding assemble -> 24 decoder layers -> StableLayerNorm -> to_lo
 backward to all decoder parameter gradients (+ the RCCL gradient all-reduce for N > 1), on `--batch`
 samples per GPU (weak scaling).  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given and prints the line; everything else it
+can measure or check (`roofline.families`, `parity`, `fast_mode`, `vae_tokenizer`, `cpu_baseline`) runs only with --full.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller -- the loss (DIR/loss.npy,
+float64) and the gradient of every decoder parameter (DIR/grad.<parameter name>.npy, float32) -- so that two builds can be compared
+output for output on identical inputs.  Gradients of at most 65536 elements are written whole; of the larger ones a fixed, seeded,
+sorted sample of flat positions (the same for the same shape and name), sized to keep the directory under 64 MB.
+
 What the line carries (rank 0):
   value / ms_per_step   EXACTLY K steps between barrier + synchronize on both sides, wall clock, max over ranks; the per-launch
                         HIP-event timer of the library is OFF in this region.  `ms_per_step_median` = median of the K per-step
                         HIP-event intervals recorded on the compute stream in the same region.
   roofline              SURVEY 8(d): the WHOLE decoder step -- algorithmic FLOPs of forward + backward / ms_per_step against the dense bf16
-                        MFMA peak (`frac` == `step_mfma_frac`); `families` = the same object per kernel family (gemm_nt, xattn: MFMA-bound;
+                        MFMA peak (`frac` == `step_mfma_frac`); `families` (--full) = the same object per kernel family (gemm_nt, xattn: MFMA-bound;
                         s3, ln: HBM-bound, algorithmic bytes / time against 8 TB/s) from a SECOND pass of a few steps with the library's
                         per-launch HIP-event timer armed (events on the launch stream, inside libamdnuwa).
-  parity                the same 24-layer decoder, one sample, logits against the oracle's (fp32 CPU restatement of the
+  parity (--full)       the same 24-layer decoder, one sample, logits against the oracle's (fp32 CPU restatement of the
                         reference) in every precision mode, measured in this run; `worst_of_8` = the committed sweep over 8 samples / 3
                         models (tools/parity_sweep.py -> profiles/parity_sweep.json); `grad_rel_max` = worst gradient error of ONE cfg-3
                         decoder layer (dx, dcontext, every parameter) against the oracle, live, in the headline mode and in 'bf16'.
-  fast_mode             throughput of the all-bf16 mode (no lo parts anywhere; logits error in `parity.bf16`) in the same run.
-  cpu_baseline          the oracle's full step (24 layers forward + backward through the CE loss), b = 1, on the host cores.
+  fast_mode (--full)    throughput of the all-bf16 mode (no lo parts anywhere; logits error in `parity.bf16`) in the same run.
+  cpu_baseline (--full) the oracle's full step (24 layers forward + backward through the CE loss), b = 1, on the host cores.
 """
 import argparse
 import hashlib
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
+import zlib
 
 import torch
 import torch.distributed as dist
@@ -253,6 +265,30 @@ def tokenizer_rate(nuwa, c, b, dev):
     return {'frames_per_s': b * c['frames'] / dt, 'video_tokens_per_s': ids.numel() / dt, 'ms': dt * 1e3, 'videos': b, 'dtype': 'f32'}
 
 
+DUMP_BYTES = 60 * 2 ** 20      # --dump-outputs stays under 64 MB
+DUMP_WHOLE = 65536             # gradients up to this many elements are written whole
+
+
+def dump_outputs(out_dir, nuwa, params, loss):
+    """writes the loss and every decoder parameter gradient of the last step (module docstring: --dump-outputs)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    names = {id(p): k for k, p in nuwa.named_parameters()}
+    grads = [(names[id(p)], p.grad) for p in params if p.grad is not None]
+    whole = sum(g.numel() for _, g in grads if g.numel() <= DUMP_WHOLE)
+    large = sum(g.numel() for _, g in grads if g.numel() > DUMP_WHOLE)
+    frac = min(1.0, (DUMP_BYTES // 4 - whole) / max(large, 1))
+    np.save(os.path.join(out_dir, 'loss.npy'), np.asarray(float(loss.detach()), dtype=np.float64))
+    for name, g in grads:
+        flat = g.detach().reshape(-1)
+        if flat.numel() > DUMP_WHOLE:
+            gen = torch.Generator(device='cpu').manual_seed(zlib.crc32(name.encode()))
+            keep = max(1, int(flat.numel() * frac))
+            idx = torch.randperm(flat.numel(), generator=gen)[:keep].sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, f'grad.{name}.npy'), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -275,13 +311,21 @@ def main():
                     help='replay the timed steps as ONE HIP graph (forward + backward, ~2700 launches) instead of launching kernel by kernel; '
                          'single GPU only.  Measured neutral (DESIGN.md 5m): off by default')
     ap.add_argument('--no-tokenizer', action='store_true', help='skip the (untimed, separately reported) frozen-VAE tokenizer rate')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: the per-family roofline pass, the all-bf16 side pass, the tokenizer rate, the CPU baseline and the '
+                         'parity checks (the --no-* options above leave parts of it out); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss and the decoder parameter gradients of the last timed step to DIR/*.npy (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('bench.py: --steps must be >= 1 and --warmup >= 0')
 
     if not torch.cuda.is_available():
         raise SystemExit('bench.py needs a HIP device (the decoder path has no CPU fallback)')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
-        # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, RCCL), so that the line says n_gpus: N
-        # and measures N devices -- or fail loudly when the box does not have them
+        # `python bench.py --gpus N` without a launcher: start the launcher (one rank per GPU, RCCL) as a child, so that the line says n_gpus: N
+        # and measures N devices -- or fail loudly when the box does not have them.  A child, not exec: this process has already opened the
+        # device (device_count), and replacing a process that holds the device with another program is not safe on every driver
         have = torch.cuda.device_count()
         if have < args.gpus and not args.single_device:
             raise SystemExit(f'bench.py --gpus {args.gpus}: this box exposes {have} HIP device(s)')
@@ -292,7 +336,7 @@ def main():
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}', '--master-addr', '127.0.0.1',
                '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        raise SystemExit(subprocess.call(cmd))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -392,6 +436,8 @@ def main():
     dt = float(tmax.item())
     peak_gb = torch.cuda.max_memory_allocated(dev) / 2 ** 30
     loss_val = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, nuwa, params, loss)
     graph_used = graph is not None
     if graph is not None:                        # the graph's private pool holds a whole step's tensors: release it before the side passes
         del timed_step, static_loss, loss
@@ -400,28 +446,29 @@ def main():
             p.grad = None
         torch.cuda.empty_cache()
 
-    # ---- second pass (rank 0's numbers): the library's per-launch HIP-event timer armed around every amdnuwa_gemm_nt launch
+    # ---- second pass (--full, rank 0's numbers): the library's per-launch HIP-event timer armed around every amdnuwa_gemm_nt launch
     probe_steps = max(1, min(args.steps, 5))
     gemm_ms, gemm_launches, gemm_flops, gemm_bytes, gemm_issued = (0.0, 0, 0.0, 0.0, 0.0)
     families = {}
-    if rank == 0:
-        K.timer_arm(True)
-    t1 = time.perf_counter()
-    for _ in range(probe_steps):
-        step()
-    fence()
-    dt_probe = time.perf_counter() - t1
-    if rank == 0:
-        gemm_ms, gemm_launches, gemm_flops, gemm_bytes = K.timer_collect()
-        gemm_issued = K.timer_issued_flops()
-        families = K.timer_families()
-        K.timer_arm(False)
+    if args.full:
+        if rank == 0:
+            K.timer_arm(True)
+        t1 = time.perf_counter()
+        for _ in range(probe_steps):
+            step()
+        fence()
+        dt_probe = time.perf_counter() - t1
+        if rank == 0:
+            gemm_ms, gemm_launches, gemm_flops, gemm_bytes = K.timer_collect()
+            gemm_issued = K.timer_issued_flops()
+            families = K.timer_families()
+            K.timer_arm(False)
 
-    # ---- the all-bf16 mode beside the headline (same batch unless --side-batch), a few steps
+    # ---- the all-bf16 mode beside the headline (--full; same batch unless --side-batch), a few steps
     fast_mode = None
     loss = None
-    torch.cuda.empty_cache()          # the side pass allocates differently sized activations: hand the cached blocks back first
-    if not args.no_parity and args.precision != 'bf16':
+    if args.full and not args.no_parity and args.precision != 'bf16':
+        torch.cuda.empty_cache()      # the side pass allocates differently sized activations: hand the cached blocks back first
         pb = max(1, args.side_batch or b)
         pbatch = (ids, ctx, mask) if pb == b else synthetic_batch(c, pb, rank, dev)
         A.set_precision('bf16')
@@ -498,7 +545,7 @@ def main():
                          'frac': step_flops / (dt / args.steps) / 1e12 / PEAK_BF16_TFLOPS, 'traffic': None,
                          'flops_per_step': step_flops, 'families': {}},
         }
-        gemm_fam = {'bound': 'mfma', 'kernel': 'gemm_nt_* (bf16 / fp16 MFMA NT GEMM family; `achieved` counts the ALGORITHMIC 2MNK per product, `mfma_issued_tflops` what the hi+lo forward GEMMs really issue; every amdnuwa_gemm_nt launch of a separate pass of '
+        gemm_fam = {} if not args.full else {'bound': 'mfma', 'kernel': 'gemm_nt_* (bf16 / fp16 MFMA NT GEMM family; `achieved` counts the ALGORITHMIC 2MNK per product, `mfma_issued_tflops` what the hi+lo forward GEMMs really issue; every amdnuwa_gemm_nt launch of a separate pass of '
                               f'{probe_steps} step(s) with the per-launch HIP-event timer armed, events on the launch stream)',
                     'achieved': ach, 'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s', 'frac': ach / PEAK_BF16_TFLOPS,
                     'traffic': None, 'algorithmic_bytes_per_launch': gemm_bytes / max(gemm_launches, 1),
@@ -506,7 +553,8 @@ def main():
                     'mfma_issued_tflops': gemm_issued / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0,
                     'launches': gemm_launches, 'avg_launch_us': gemm_ms * 1e3 / max(gemm_launches, 1),
                     'ms_per_step': gemm_ms / probe_steps, 'share_of_step': gemm_ms * 1e-3 / dt_probe}
-        out['roofline']['families']['gemm_nt'] = gemm_fam
+        if args.full:
+            out['roofline']['families']['gemm_nt'] = gemm_fam
         for nm, bound, what in (('xattn', 'mfma', 'cross-attention cores: forward, backward query side, batched dK / dV products (algorithmic QK^T / P\'V / head-mix FLOPs)'),
                                 ('s3', 'hbm', 'Sparse3DNA cores: forward (reads q, k, v, writes o) and backward (reads q, k, v, dO, writes dq, dk, dv)'),
                                 ('ln', 'hbm', 'LayerNorm kernels: every large operand read once, every result written once')):
@@ -527,10 +575,10 @@ def main():
         out['roofline']['traffic_source'] = why
         if fast_mode is not None:
             out['fast_mode'] = fast_mode
-        if not args.no_tokenizer and world == 1:          # (side measurement, single-GPU runs only: keeps the ranks in step)
+        if args.full and not args.no_tokenizer and world == 1:          # (side measurement, single-GPU runs only: keeps the ranks in step)
             out['vae_tokenizer'] = tokenizer_rate(nuwa, c, min(b, 8), dev)
         oracle_logits = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out['cpu_baseline'], oracle_logits = cpu_baseline(c, nuwa, ids, ctx, mask, threads=(os.cpu_count() if args.cpu_threads == 0 else args.cpu_threads))
             except Exception as e:      # the baseline is a report, never a reason to lose the GPU number
@@ -576,10 +624,11 @@ def main():
             out['parity'] = par
         # fp16 saturation monitor over everything this process ran (timed steps included): the COUNTED stores (LayerNorm fp16 copies, cross-attention
         # output copy, fp16-gradient epilogues; include/amdnuwa.h says which clamp without counting): 0 in a healthy run
-        try:
-            out.setdefault('parity', {})['f16_saturations'] = K.f16_sat_count(reset=False)
-        except Exception as e:
-            out.setdefault('parity', {})['f16_saturations'] = f'{type(e).__name__}: {e}'
+        if args.full:
+            try:
+                out.setdefault('parity', {})['f16_saturations'] = K.f16_sat_count(reset=False)
+            except Exception as e:
+                out.setdefault('parity', {})['f16_saturations'] = f'{type(e).__name__}: {e}'
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

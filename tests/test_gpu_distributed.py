@@ -111,7 +111,7 @@ def test_bench_py_two_ranks_end_to_end(launcher):
     import subprocess
     port = 29900 + (os.getpid() % 90)
     tail = ['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2', '--side-batch', '1', '--backend', 'gloo', '--single-device',
-            '--no-tokenizer', '--no-cpu-baseline']
+            '--no-tokenizer', '--no-cpu-baseline', '--full']
     if launcher == 'self':
         cmd = [sys.executable, os.path.join(ROOT, 'bench.py')] + tail
     else:

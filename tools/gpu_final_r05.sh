@@ -10,7 +10,7 @@ rm -f gpurun_out/parity_log.jsonl gpurun_out/named_size.json
 timeout 900 python tools/determinism_stress.py 128 --rep 10 > gpurun_out/${TAG}_determinism_stress.txt 2>&1; tail -n 1 gpurun_out/${TAG}_determinism_stress.txt
 timeout 1800 python -m pytest tests -m gpu -q --tb=short > gpurun_out/${TAG}_pytest_gpu.txt 2>&1; echo "pytest rc=$?" >> gpurun_out/${TAG}_pytest_gpu.txt; tail -n 4 gpurun_out/${TAG}_pytest_gpu.txt
 cp gpurun_out/named_size.json gpurun_out/${TAG}_named_size.json 2>/dev/null
-BA="--steps 1 --warmup 1 --no-cpu-baseline --no-tokenizer --no-parity"
+BA="--full --steps 1 --warmup 1 --no-cpu-baseline --no-tokenizer --no-parity"
 for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_VALU_MFMA_MOPS_F16" "SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS"; do
   n=$(echo $pass | cut -d' ' -f1)
   O=$R/gpurun_out/pmc_${TAG}_$n; rm -rf $O; mkdir -p $O

@@ -12,7 +12,7 @@ timeout 1800 python -m pytest tests -m gpu -q --tb=short > gpurun_out/${TAG}_pyt
 cp gpurun_out/named_size.json gpurun_out/${TAG}_named_size.json 2>/dev/null
 timeout 900 python tools/parity_sweep.py 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_parity_sweep.txt; tail -n 3 gpurun_out/${TAG}_parity_sweep.txt | cut -c1-200
 cp gpurun_out/parity_sweep.json profiles/parity_sweep.json 2>/dev/null      # (on the box: the bench line below reads it; copy it back by hand afterwards)
-BA="--steps 1 --warmup 1 --no-cpu-baseline --no-tokenizer --no-parity"
+BA="--full --steps 1 --warmup 1 --no-cpu-baseline --no-tokenizer --no-parity"
 for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_VALU_MFMA_MOPS_F16" "SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS"; do
   n=$(echo $pass | cut -d' ' -f1)
   O=$R/gpurun_out/pmc_${TAG}_$n; rm -rf $O; mkdir -p $O

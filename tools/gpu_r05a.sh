@@ -13,7 +13,7 @@ grep -E "===|TOTAL" gpurun_out/r05a_mix_variants.txt
 for i in 1 2; do
   for v in "" nopk; do
     lib=$R/nuwa_pytorch_amd/lib${v:+_$v}/libamdnuwa.so
-    AMDNUWA_LIBRARY=$lib timeout 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity 2>/dev/null | tail -n 1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('build ${v:-default}:', round(d['ms_per_step'],1), 'ms/step', round(d['value']), d['unit'], '| fast_mode', d.get('fast_mode',{}).get('ms_per_step'))"
+    AMDNUWA_LIBRARY=$lib timeout 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity 2>/dev/null | tail -n 1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('build ${v:-default}:', round(d['ms_per_step'],1), 'ms/step', round(d['value']), d['unit'], '| fast_mode', d.get('fast_mode',{}).get('ms_per_step'))"
   done
 done > gpurun_out/r05a_ab_nopk.txt 2>&1; cat gpurun_out/r05a_ab_nopk.txt
 timeout 900 python tools/parity_sweep.py > gpurun_out/r05a_parity_sweep.txt 2>&1; tail -n 24 gpurun_out/r05a_parity_sweep.txt

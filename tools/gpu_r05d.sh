@@ -8,7 +8,7 @@ timeout 900 python tools/determinism_stress.py 128 --rep 10 > gpurun_out/r05_det
 for i in 1 2; do
   for v in "" pk; do
     lib=$R/nuwa_pytorch_amd/lib${v:+_$v}/libamdnuwa.so
-    AMDNUWA_LIBRARY=$lib timeout 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity 2>/dev/null | tail -n 1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('build ${v:-shipped (no packed fp32)}:', round(d['ms_per_step'],1), 'ms/step', round(d['value']), d['unit'], '| fp16 saturations', d['parity']['f16_saturations'])"
+    AMDNUWA_LIBRARY=$lib timeout 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity 2>/dev/null | tail -n 1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('build ${v:-shipped (no packed fp32)}:', round(d['ms_per_step'],1), 'ms/step', round(d['value']), d['unit'], '| fp16 saturations', d['parity']['f16_saturations'])"
   done
 done > gpurun_out/r05d_ab_pk.txt 2>&1; cat gpurun_out/r05d_ab_pk.txt
 timeout 1500 python -m pytest tests -m gpu -q --tb=short > gpurun_out/r05d_pytest.txt 2>&1; tail -n 6 gpurun_out/r05d_pytest.txt

@@ -10,7 +10,7 @@ for lib in prev new prev new; do
   echo "== $lib" | tee -a gpurun_out/${TAG}_attn_b128.txt
   timeout 600 python tools/attn_bench.py --batch 128 2>&1 | grep dilation | cut -c1-420 | tee -a gpurun_out/${TAG}_attn_b128.txt
 done
-BA="--steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity"
+BA="--full --steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity"
 for lib in prev new prev new; do
   if [ $lib = prev ]; then export AMDNUWA_LIBRARY=$PREV; else unset AMDNUWA_LIBRARY; fi
   timeout 600 python bench.py $BA 2>/dev/null | tail -n 1 | python -c "

@@ -4,7 +4,7 @@
 #   20=1  no persistent ring          AMDNUWA_FUSE_LINEAR_CE_X3=1  fused to_logits + cross entropy          3=1 / 12..: see include/amdnuwa.h
 mkdir -p gpurun_out; export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 TAG=${TAG:-r06zk}
-BA="--steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity"
+BA="--full --steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity"
 run() {
   timeout 600 python bench.py $BA 2>/dev/null | tail -n 1 | python -c "
 import sys, json

@@ -3,7 +3,7 @@
 # -mllvm -amdgpu-sched-strategy=max-ilp / max-memory-clause), A/B against the shipped build in one call
 mkdir -p gpurun_out; export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 TAG=${TAG:-r06zm}
-BA="--steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity"
+BA="--full --steps 6 --warmup 2 --no-cpu-baseline --no-tokenizer --no-parity"
 for lib in default ilp mclause default ilp mclause; do
   if [ $lib = default ]; then unset AMDNUWA_LIBRARY; else export AMDNUWA_LIBRARY=$PWD/nuwa_pytorch_amd/lib_$lib/libamdnuwa.so; fi
   timeout 600 python bench.py $BA 2>/dev/null | tail -n 1 | python -c "
