@@ -175,7 +175,7 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // erf-GELU (F.gelu default, np.py:255-258) and its derivative.  Phi(x) = 0.5 * erfc(-x / sqrt 2) through the Abramowitz-Stegun
-// 7.1.26 rational form (|abs error| <= 1.5e-7, no cancellation on the negative side): 1 rcp + 1 exp + 5 fma instead of the
+// 7.1.26 rational form (|abs error| <= 3e-7 over [-9, 9], absolute on both sides: see below): 1 rcp + 1 exp + 5 fma instead of the
 // ~60-instruction libm erff, which made the GEGLU kernels VALU-bound.  Returns Phi(x); e = exp(-x*x/2).
 __device__ __forceinline__ float norm_cdf_f(float x, float& e) {
     // (round 6, 16 -> 13 instructions: w = |x| sqrt(log2(e) / 2) serves the exponent directly (e = exp2(-w w): no separate log2(e) multiply),

@@ -311,8 +311,10 @@ class XInner:
         rot = meta.get('rotary')
         R, D, _ = K.bf_rows_cols(h)
         inner = g.heads * g.dim_head
-        if meta.get('bwd16') and 'qT_16' in W and ctx.lo is not None and nk.dtype == torch.float32:
+        if meta.get('bwd16'):
             # fp16-gradient backward: ONE (fp16) copy of h, of q and of the core's output; the backward's images come from the fp16 copy of k / v
+            # (_block_bwd16 decided it: the context's hi + lo copy, fp32 null key / value, the fp16 weight copies of this mode)
+            assert 'qT_16' in W and ctx.lo is not None and nk.dtype == torch.float32
             q16 = K.gemm_nt_f16x2(h.f16, W['q_16'], out_f16=True)
             kv = K.gemm_nt(ctx, W['kv'], out_bf16=True, out_f16=True)
             nk2, nv2 = nk.detach().reshape(g.heads, g.dim_head).contiguous(), nv.detach().reshape(g.heads, g.dim_head).contiguous()
@@ -740,26 +742,37 @@ def _block_bwd16(kind, R, D, p, meta):
     if kind == 's3':
         return S3Inner.bwd16_ok(R, D, p[0].shape[0], meta['geom'], (p[0], p[1]), p[3], len(p) > 5)
     if kind == 'xattn':
-        return XInner.bwd16_ok(R, D, p[3].shape[0], meta['xgeom'], meta, (p[3], p[5]))
+        # (the fp16 branch of XInner.fwd projects the context's hi + lo copy and reads fp32 null key / value)
+        c = meta.get('ctx_bf')
+        return c is not None and c.lo is not None and p[0].dtype == torch.float32 and \
+            XInner.bwd16_ok(R, D, p[3].shape[0], meta['xgeom'], meta, (p[3], p[5]))
     return False
 
 
 _CTX_CAST = [None, -1, None]      # (weak reference to the context tensor, its version, its BF copy)
 
 
+def _ctx_cast_drop(ref):
+    """the context tensor died: release its copy"""
+    if _CTX_CAST[0] is ref:
+        _CTX_CAST[0], _CTX_CAST[1], _CTX_CAST[2] = None, -1, None
+
+
 def _ctx_to_bf(context):
     """context fp32 [B, T, D] -> BF [B*T, D].  Every cross-attention block of a stack receives the SAME context tensor: its cast (27 us at
-    cfg 3, b = 128) runs once per tensor object and version, not once per layer (the copy is read-only: kv projection, its weight gradient)"""
+    cfg 3, b = 128) runs once per tensor object and version, not once per layer (the copy is read-only: kv projection, its weight gradient).
+    The copy is hi-only or hi + lo as the precision mode wants: a copy cast in another mode is not reused."""
     ref = _CTX_CAST[0]
-    if ref is not None and ref() is context and _CTX_CAST[1] == context._version:
+    lo = K.want_lo()
+    if ref is not None and ref() is context and _CTX_CAST[1] == context._version and (_CTX_CAST[2].lo is not None) == lo:
         return _CTX_CAST[2]
     B, T, D = context.shape
-    out = K.empty_bf((B * T, D), context.device)
+    out = K.empty_bf((B * T, D), context.device, lo=lo)
     K.cast_pad(context.detach().reshape(B * T, D), out)
     try:
-        _CTX_CAST[0], _CTX_CAST[1], _CTX_CAST[2] = weakref.ref(context), context._version, out
+        _CTX_CAST[0], _CTX_CAST[1], _CTX_CAST[2] = weakref.ref(context, _ctx_cast_drop), context._version, out
     except TypeError:
-        _CTX_CAST[0] = None
+        _CTX_CAST[0], _CTX_CAST[1], _CTX_CAST[2] = None, -1, None
     return out
 
 

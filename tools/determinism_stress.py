@@ -8,7 +8,7 @@ shows up here.
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from nuwa_pytorch_amd import kernels as K, _lib  # noqa: E402
+from nuwa_pytorch_amd import kernels as K, ops, _lib  # noqa: E402
 
 L = _lib.lib()
 DEV = 'cuda'
@@ -60,6 +60,9 @@ def main():
             total += check(f'3DNA fwd fp16, dilation {dil[0]}, {rows} row(s) per tile, b={B}', lambda: K.sparse3dna_fwd(g, p16, wth))
         L.amdnuwa_set_tuning(16, 0)
         total += check(f'3DNA bwd bf16, dilation {dil[0]}, b={B}', lambda: K.sparse3dna_bwd(g, pbf, wth, dO))
+        s2 = ops._grad_scale(dO.hi)
+        dO16 = (dO.hi.float() * s2[0]).half()
+        total += check(f'3DNA bwd fp16 gradients, dilation {dil[0]}, b={B}', lambda: K.sparse3dna_bwd16(g, p16.f16, wth, dO16, s2))
     if only_s3:
         print('TOTAL differing elements:', total)
         return 1 if total else 0
@@ -79,6 +82,22 @@ def main():
     o, stats = K.xattn2_fwd(gx, qb, pkb, wth)
     dO = K.BF(torch.randn(B * n, inner, device=DEV).to(torch.bfloat16), None)
     total += check(f'cross attention bwd (xattn3, query side), b={B}', lambda: (lambda r: (r[0], K.xattn_rows(gx, r[1].hi), K.xattn_rows(gx, r[2].hi), r[3]))(K.xattn2_bwd(gx, qb, dO, pkb, wth, stats)))
+    # the xattn6 backward the training step runs: bf16, and the fp16-gradient form with its chunk-major dK / dV products
+    rows = lambda r: (r[0], K.xattn_rows(gx, r[1].hi if isinstance(r[1], K.BF) else r[1]), K.xattn_rows(gx, r[2].hi if isinstance(r[2], K.BF) else r[2]), r[3])
+    kvb = kv.to(torch.bfloat16)
+    _, st6 = K.xattn6_fwd(gx, qb.hi, K.xattn6_pack(gx, kvb, mask), nk, nv, wth, lo=False)
+    pk6b = K.xattn6_pack_bwd(gx, kvb, nk, nv, mask)
+    total += check(f'cross attention bwd bf16 (xattn6, query side), b={B}', lambda: rows(K.xattn6_bwd(gx, qb, dO, pk6b, wth, st6)))
+    s2 = ops._grad_scale(dO.hi)
+    dO16 = (dO.hi.float() * s2[0]).half()
+    _, st16 = K.xattn6_fwd(gx, q16.f16, K.xattn6_pack(gx, kv16.f16, mask), nk, nv, wth, o_f16='only')
+    pk16b = K.xattn6_pack_bwd(gx, kv16.f16, nk, nv, mask)
+    total += check(f'cross attention bwd fp16 gradients (xattn6, query side), b={B}',
+                   lambda: rows(K.xattn6_bwd16(gx, q16.f16, dO16, pk16b, wth, st16, s2)))
+    _, dS16, Pm16, _ = K.xattn6_bwd16(gx, q16.f16, dO16, pk16b, wth, st16, s2)
+    mx = K.xattn_permuted_extent(gx)            # (the rows past it are not written)
+    total += check(f'cross attention dK / dV fp16 gradients (chunk-major TN), b={B}',
+                   lambda: (lambda r: (r[0][:, :, :mx], r[1][:, :, :mx]))(K.xattn_kv_grads16(gx, dS16, Pm16, q16.f16, dO16, s2)))
     total += other_families(B, check)
     print('TOTAL differing elements:', total)
     return 1 if total else 0
