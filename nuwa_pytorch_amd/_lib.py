@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # AMDNUWA_LIBRARY: another build of the same library (A/B runs of compiler options inside one process group; tools/ only)
 LIB_PATH = os.environ.get('AMDNUWA_LIBRARY') or os.path.join(HERE, 'lib', 'libamdnuwa.so')
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 P = C.c_void_p
 I = C.c_int
@@ -45,12 +45,16 @@ class X6KV(C.Structure):
     _fields_ = [('K6', P), ('V6', P), ('vbits', P)]
 
 
+class CGeom(C.Structure):
+    _fields_ = [('B', I), ('n', I), ('heads', I), ('dim_head', I), ('scale', F), ('causal', I)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [('N', I), ('Cin', I), ('H', I), ('W', I), ('Cout', I), ('KH', I), ('KW', I), ('stride', I), ('pad', I),
                 ('Ho', I), ('Wo', I), ('leaky', I)]
 
 
-GD, SG, XG, XK, CD, X6 = (C.POINTER(t) for t in (GemmDesc, S3Geom, XGeom, XKV, ConvDesc, X6KV))
+GD, SG, XG, XK, CD, X6, CG = (C.POINTER(t) for t in (GemmDesc, S3Geom, XGeom, XKV, ConvDesc, X6KV, CGeom))
 
 # name -> (restype, argtypes).  Mirrors include/amdnuwa.h declaration by declaration.
 SIGNATURES = {
@@ -138,6 +142,10 @@ SIGNATURES = {
     'amdnuwa_xattn6_bwd': (I, [XG, P, I, P, I, X6, P, P, P, P, P, P, P, I, P, SZ, P]),
     'amdnuwa_xattn6_pack_bwd_f16': (I, [XG, P, I, P, P, P, X6, P]),
     'amdnuwa_xattn6_bwd_f16': (I, [XG, P, I, P, I, X6, P, P, P, P, P, P, P, I, P, SZ, P]),
+    'amdnuwa_cattn_supported': (I, [CG]),
+    'amdnuwa_cattn_fwd': (I, [CG, P, I, P, P, I, P, P, P, P, P, P, I, I, P, I, P]),
+    'amdnuwa_cattn_bwd_workspace_bytes': (SZ, [CG]),
+    'amdnuwa_cattn_bwd': (I, [CG, P, I, P, P, I, P, I, P, P, P, P, P, P, I, P, P, I, P, P, P, P, SZ, P]),
     'amdnuwa_xattn2_bwd_rc_supported': (I, [XG]),
     'amdnuwa_xattn2_bwd_rc_stats_bytes': (SZ, [XG]),
     'amdnuwa_xattn2_bwd_rc': (I, [XG, P, I, P, I, XK, P, P, P, I, P, SZ, P, SZ, P, P, P]),

@@ -111,6 +111,9 @@ class IncrementalDecoder:
                                      inner.dim_head)
                 blk.kvcache = K.zeros_bf((batch, max_rows, 2 * inner.heads * inner.dim_head), dev, lo=lo)
             elif isinstance(inner, Attention):
+                if inner.causal:
+                    # plain causal self-attention has no cached single-row path: generate() keeps the recompute loop for such stacks
+                    raise NotImplementedError('IncrementalDecoder: no single-row path for plain (causal) self-attention')
                 blk.kind = 'x'
                 p = inner._params()
                 W = ops.XInner.weights(inner._cache, p)

@@ -9,7 +9,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from ._lib import GemmDesc, S3Geom, XGeom, XKV, check
+from ._lib import CGeom, GemmDesc, S3Geom, XGeom, XKV, check
 
 # bf16 hi part + optional bf16 residual `lo` (hi + lo = the value to ~16 bits: the operand form of the 3-MFMA products) + optional
 # `f16` = the fp16 rendering of the same value (the operand form of the fp16 attention cores of the 'bf16x3-fwd' mode)
@@ -1402,6 +1402,86 @@ def xattn6_bwd(g, q, dO, pk, wth, stats):
                                _p(dS.hi), _p(Pm.hi), _p(dq.hi), inner, _p(part), nb, _stream()), 'amdnuwa_xattn6_bwd')
     dwth = colsum(part).reshape(g.heads, g.heads)          # fixed-order reduction over the workgroups
     return dq, BF(dS.hi, None), BF(Pm.hi, None), dwth
+
+
+# ------------------------------------------------------------------------------------------------
+# plain (causal) self-attention with linear memory: the cattn family
+# ------------------------------------------------------------------------------------------------
+
+def cattn_geom(B, n, heads, dim_head, causal=True):
+    g = CGeom()
+    g.B, g.n, g.heads, g.dim_head, g.scale, g.causal = B, n, heads, dim_head, dim_head ** -0.5, 1 if causal else 0
+    return g
+
+
+def cattn_supported(g):
+    return bool(_lib.lib().amdnuwa_cattn_supported(C.byref(g)))
+
+
+def _c_work(kind):
+    """algorithmic MFMA work of the cattn cores over the VISIBLE (query, key) pairs only -- the causal half plus the null key (U = one
+    2 pairs d product): forward QK^T + A V + head mix; backward S, dA, dq, dk, dv + two mixes"""
+    def w(a, k, r):
+        g = a[0]
+        pairs = float(g.B) * g.heads * (g.n * (g.n + 1) / 2.0 + g.n if g.causal else g.n * (g.n + 1.0))
+        U, mix = 2.0 * pairs * g.dim_head, 2.0 * pairs * g.heads
+        act = 2.0 * g.B * g.n * g.heads * g.dim_head                       # one 16-bit [B*n, inner] tensor
+        return ((2 * U + mix, 4 * act) if kind == 'fwd' else (5 * U + 2 * mix, 7 * act))
+    return w
+
+
+def _rows16(t, inner):
+    assert t.dim() == 2 and t.stride(1) == 1 and t.shape[1] == inner and t.dtype in (torch.float16, torch.bfloat16)
+    return t
+
+
+@_family('cattn', _c_work('fwd'))
+def cattn_fwd(g, q16, k16, v16, null_k, null_v, wth, mask_u8=None, o_f16=False, lo=True):
+    """the cattn forward core on 16-bit rows q16 / k16 / v16 [B*n, inner] (views with a row stride; k16 and v16 share theirs: the two
+    halves of to_kv's output).  fp16 rows: every MFMA the fp16 one; else bf16.  Returns o BF [B*n, inner] (hi + lo pair; with o_f16 a bf16
+    copy + an fp16 copy; lo=False: the bf16 copy alone) and the softmax statistics [B, heads, n, 2]"""
+    L = _lib.lib()
+    inner = g.heads * g.dim_head
+    f16 = q16.dtype == torch.float16
+    _rows16(q16, inner), _rows16(k16, inner), _rows16(v16, inner)
+    assert k16.dtype == q16.dtype == v16.dtype and k16.stride(0) == v16.stride(0) and q16.shape[0] == g.B * g.n == k16.shape[0]
+    _chk_dev(q16, k16, v16, null_k, null_v, wth, mask_u8)
+    dev = q16.device
+    if o_f16:
+        o = BF(torch.empty((g.B * g.n, inner), dtype=torch.bfloat16, device=dev), None,
+               torch.empty((g.B * g.n, inner), dtype=torch.float16, device=dev))
+    else:
+        o = empty_bf((g.B * g.n, inner), dev, lo=lo)
+    stats = torch.empty((g.B, g.heads, g.n, 2), dtype=torch.float32, device=dev)
+    check(L.amdnuwa_cattn_fwd(C.byref(g), _p(q16), q16.stride(0), _p(k16), _p(v16), k16.stride(0), _p(mask_u8), _p(null_k), _p(null_v), _p(wth),
+                              _p(o.hi), _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _p(stats), 1 if f16 else 0, _stream()),
+          'amdnuwa_cattn_fwd')
+    return o, stats
+
+
+@_family('cattn', _c_work('bwd'))
+def cattn_bwd(g, q, k, v, dO, null_k, null_v, wth, stats, mask_u8=None):
+    """the recomputing cattn backward on bf16 rows (q / k / v / dO [B*n, inner] views) and the forward's statistics.  Returns dq BF
+    [B*n, inner], dkv BF [B*n, 2 inner] (dk | dv: the layout of to_kv's output), dw_th [heads, heads], dnull_k and dnull_v [heads, dim_head]
+    fp32.  No n x n array: the workspace is O(B n heads) floats"""
+    L = _lib.lib()
+    inner = g.heads * g.dim_head
+    for t in (q, k, v, dO):
+        assert _rows16(t, inner).dtype == torch.bfloat16
+    assert k.stride(0) == v.stride(0)
+    _chk_dev(q, k, v, dO, null_k, null_v, wth, stats, mask_u8)
+    dev = q.device
+    R = g.B * g.n
+    dq = torch.empty((R, inner), dtype=torch.bfloat16, device=dev)
+    dkv = torch.empty((R, 2 * inner), dtype=torch.bfloat16, device=dev)
+    small = torch.empty(64 + 2 * inner, dtype=torch.float32, device=dev)
+    nb = L.amdnuwa_cattn_bwd_workspace_bytes(C.byref(g))
+    ws = workspace(nb, dev)
+    check(L.amdnuwa_cattn_bwd(C.byref(g), _p(q), q.stride(0), _p(k), _p(v), k.stride(0), _p(dO), dO.stride(0), _p(mask_u8), _p(null_k), _p(null_v),
+                              _p(wth), _p(stats), _p(dq), inner, _p(dkv), dkv.data_ptr() + 2 * inner, 2 * inner, _p(small), small.data_ptr() + 4 * 64,
+                              small.data_ptr() + 4 * (64 + inner), _p(ws), nb, _stream()), 'amdnuwa_cattn_bwd')
+    dwth = small[:64].reshape(8, 8)[:g.heads, :g.heads].contiguous()
+    return BF(dq, None), BF(dkv, None), dwth, small[64:64 + inner].reshape(g.heads, g.dim_head), small[64 + inner:].reshape(g.heads, g.dim_head)
 
 
 def xattn_fwd(g, q, pk, wth, save=True, want_stats=False):

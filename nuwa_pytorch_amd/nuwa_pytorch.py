@@ -180,6 +180,8 @@ class SandwichNorm(nn.Module):
             return fn, shift                      # non-causal self-attention (text encoder): same kernels, keys = the query rows
         if isinstance(fn, SparseCross2DNA) and context is not None and fn._hip_ok(context.shape[1]):
             return fn, shift                      # NUWASketch decoder: 2-D nearby cross-attention on the 3DNA kernels (row f4)
+        if isinstance(fn, Attention) and context is None and seq_len is not None and fn._causal_hip_ok(seq_len):
+            return fn, shift                      # plain causal self-attention (sparse_3dna_attn=False): the linear-memory kernels, any length
         return None
 
     def fused_residual(self, x, resid=None, context=None, context_mask=None, mask=None, rotary_pos_emb=None, chain=None, minus=False):
@@ -346,8 +348,10 @@ class FeedForward(nn.Module):
 class Attention(nn.Module):
     """np.py:290-379.  With `context` (the decoder's text cross-attention) and as non-causal self-attention (the text encoder, row f1:
     keys / values = the query rows, rotary on q, k and v) the core runs on the MFMA cross-attention kernels (xattn6; xattn2 / xattn for
-    the shapes it does not take).  Outside `_hip_ok` -- causal=True, more than 287 keys, more than 8 heads, dim_head not 32 / 64,
-    attention dropout > 0 in training -- the forward below runs on PyTorch-ROCm ops."""
+    the shapes it does not take).  Causal self-attention (causal=True without a context: the decoder of `sparse_3dna_attn=False`) runs on
+    the linear-memory cattn kernels at any length (`_causal_hip_ok`; precision modes 'bf16x3-fwd' and 'bf16').  What still runs the
+    PyTorch-ROCm forward below: more than 8 heads, dim_head not 32 / 64, attention dropout > 0 in training, non-causal attention over more
+    than 287 keys, causal attention with a context, and causal self-attention in the 'bf16x3' parity mode."""
 
     def __init__(self, *, dim, heads=8, dim_head=64, causal=False, dropout=0.):
         super().__init__()
@@ -373,8 +377,20 @@ class Attention(nn.Module):
         return (not self.causal) and self.dim_head in (32, 64) and self.heads <= 8 and n_keys + 1 <= 288 and \
             not (self.training and self.dropout.p > 0)
 
+    def _causal_hip_ok(self, n):
+        """causal self-attention the cattn kernels take: any length; 'bf16x3-fwd' (fp16 forward core, bf16 backward) and 'bf16'"""
+        return self.causal and n >= 1 and self.dim_head in (32, 64) and self.heads <= 8 and not (self.training and self.dropout.p > 0) and \
+            (K.get_precision() == 'bf16' or K.cores_f16())
+
     def _meta(self, B, n, device, context=None, context_mask=None, mask=None, rotary_pos_emb=None, **_):
         assert not (self.training and self.dropout.p > 0)      # (_hip_ok routes attn_dropout > 0 in training to the torch-op forward)
+        if self.causal:                               # plain causal self-attention: the cattn kernels (keys = the query rows, key mask = `mask`)
+            assert context is None
+            meta = dict(kind='cattn', cache=self._cache, cgeom=K.cattn_geom(B, n, self.heads, self.dim_head, causal=True),
+                        mask_u8=mask.to(torch.uint8).contiguous() if exists(mask) else None)
+            if exists(rotary_pos_emb):
+                meta['rotary'] = rotary_pos_emb.detach().float()
+            return meta
         self_kv = context is None
         T = n if self_kv else context.shape[1]
         key_mask = mask if self_kv else context_mask
@@ -392,6 +408,9 @@ class Attention(nn.Module):
         if x.is_cuda and self._hip_ok(context.shape[1] if exists(context) else n):
             meta = self._meta(B, n, x.device, context, context_mask, mask=mask, rotary_pos_emb=rotary_pos_emb)
             return ops.InnerFn.apply(x, context, meta, *self._params())
+        if x.is_cuda and not exists(context) and self._causal_hip_ok(n):
+            meta = self._meta(B, n, x.device, mask=mask, rotary_pos_emb=rotary_pos_emb)
+            return ops.InnerFn.apply(x, None, meta, *self._params())
         return self._forward_torch(x, mask=mask, context=context, context_mask=context_mask, rotary_pos_emb=rotary_pos_emb)
 
     def _forward_torch(self, x, mask=None, context=None, context_mask=None, rotary_pos_emb=None):

@@ -425,6 +425,71 @@ class XInner:
         return dh, dctx, [dnk.reshape(nk.shape), dnv.reshape(nv.shape), dwth.reshape(wth.shape), dwq, dwkv, dwo]
 
 
+class CInner:
+    """to_q(x), to_kv(x) -> plain self-attention core with linear memory (cattn: causal or not, any length) -> to_out (np.py:315-379 with
+    `context is None`).  params: null_k, null_v, talking_heads.w, to_q.w, to_kv.w, to_out.w  (the layout and weight cache of XInner).
+    'bf16x3-fwd': hi + lo projections with an fp16 copy, the core on fp16 MFMAs, two-MFMA to_out; the backward on the bf16 hi parts.
+    'bf16': bf16 throughout.  ('bf16x3' keeps the torch-op formulation: Attention._causal_hip_ok.)"""
+    nparams = 6
+
+    @staticmethod
+    def _small(p, g):
+        nk, nv, wth = p[0], p[1], p[2]
+        return (nk.detach().float().reshape(g.heads, g.dim_head).contiguous(), nv.detach().float().reshape(g.heads, g.dim_head).contiguous(),
+                wth.detach().float().reshape(g.heads, g.heads).contiguous())
+
+    @staticmethod
+    def fwd(h, p, meta):
+        W = XInner.weights(meta['cache'], p)
+        g = meta['cgeom']
+        rot = meta.get('rotary')
+        R, D, _ = K.bf_rows_cols(h)
+        inner = g.heads * g.dim_head
+        assert h.hi is not None, 'a bf16 backward needs the bf16 copy of the LayerNorm output'
+        h = _f16_to_pair(h)
+        f16 = K.cores_f16() and h.lo is not None
+        q = K.gemm_nt(h, W['q'], out_bf16=True, out_f16=f16 and rot is None)
+        kv = K.gemm_nt(h, W['kv'], out_bf16=True, out_f16=f16 and rot is None)
+        if rot is not None:
+            q = _rotary_bf(q, rot, g.B, g.n, g.heads)
+            kv = _rotary_bf(kv, rot, g.B, g.n, 2 * g.heads)
+            if f16:
+                q, kv = BF(q.hi, q.lo, K.hilo_to_f16(q)), BF(kv.hi, kv.lo, K.hilo_to_f16(kv))
+        nk2, nv2, wth2 = CInner._small(p, g)
+        o16 = False
+        if f16:             # fp16 core; the output as a bf16 copy + an fp16 copy (two-MFMA to_out) or a bf16 hi + lo pair (3-MFMA to_out)
+            o16 = K.proj_f16x2('o') and 'out_16' in W and K.gemm_nt_f16x2_ok(R, p[5].shape[0], p[5].shape[1], out_bf16=False)
+            o, stats = K.cattn_fwd(g, q.f16, kv.f16[:, :inner], kv.f16[:, inner:], nk2, nv2, wth2, meta['mask_u8'], o_f16=o16)
+        else:
+            o, stats = K.cattn_fwd(g, q.hi, kv.hi[:, :inner], kv.hi[:, inner:], nk2, nv2, wth2, meta['mask_u8'], lo=False)
+        y = K.gemm_nt_f16x2(o.f16, W['out_16']) if o16 else K.gemm_nt(o, W['out'], out_bf16=_fast())
+        return y, (K.hi_only(h), K.hi_only(q), K.hi_only(kv), stats, K.hi_only(o))
+
+    @staticmethod
+    def bwd(saved, dy, p, meta, need_dbias=False, dy_f32=None):
+        h, q, kv, stats, o = saved
+        W = XInner.weights(meta['cache'], p)
+        nk, nv, wth, wq, wkv, wo = p
+        g = meta['cgeom']
+        inner = g.heads * g.dim_head
+        nk2, nv2, wth2 = CInner._small(p, g)
+        dy = K.hi_only(dy)
+        d_o = K.gemm_nt(dy, W['outT'], out_bf16=True)
+        dwo = torch.empty_like(wo)
+        K.gemm_tn(dy, o, dwo)
+        dq, dkv, dwth, dnk, dnv = K.cattn_bwd(g, q.hi, kv.hi[:, :inner], kv.hi[:, inner:], d_o.hi, nk2, nv2, wth2, stats, meta['mask_u8'])
+        rot = meta.get('rotary')
+        if rot is not None:
+            dq = _rotary_bf(dq, rot, g.B, g.n, g.heads, inverse=True)
+            dkv = _rotary_bf(dkv, rot, g.B, g.n, 2 * g.heads, inverse=True)
+        dh = K.gemm_nt(dq, W['qT'], out_bf16=_fast_bwd())
+        dwq, dwkv = torch.empty_like(wq), torch.empty_like(wkv)
+        K.gemm_tn(dq, h, dwq)
+        K.gemm_tn(dkv, h, dwkv)
+        dh = _as_f32(dh) + K.gemm_nt(dkv, W['kvT'])          # the key / value rows ARE the query rows: one gradient for h
+        return dh, None, [dnk.reshape(nk.shape), dnv.reshape(nv.shape), dwth.reshape(wth.shape), dwq, dwkv, dwo]
+
+
 def _ff_keep_mask(R, C, p, device):
     """keep mask of nn.Dropout(p) over the GEGLU output [R, C] (torch's RNG stream; tests replace this function by a fixed mask)"""
     return torch.rand((R, C), device=device) >= p
@@ -668,7 +733,7 @@ class XC2Inner:
         return dh_, dctx, [dnk.reshape(nkp.shape), dnv.reshape(nvp.shape), dwth.reshape(wth.shape), dwq, dwkv, dwo]
 
 
-INNERS = {'s3': S3Inner, 'xattn': XInner, 'ff': FFInner, 'xc2': XC2Inner}
+INNERS = {'s3': S3Inner, 'xattn': XInner, 'ff': FFInner, 'xc2': XC2Inner, 'cattn': CInner}
 
 FUSE_LINEAR_CE = os.environ.get('AMDNUWA_FUSE_LINEAR_CE', '1') != '0'   # to_logits + cross entropy without the fp32 logits (A/B switch)
 # ... in 'bf16x3-fwd' (hi + lo logits): OFF by default.  The fused form needs the three-MFMA product twice (statistics, then dlogits -- the

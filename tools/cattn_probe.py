@@ -1,0 +1,92 @@
+#!/usr/bin/env python
+"""Plain causal self-attention: the linear-memory cattn kernels against the torch-op formulation, in one process.
+
+Times forward + backward of ONE `Attention(dim=512, heads=8, dim_head=64, causal=True)` through the module's kernel path and through
+`Attention._forward_torch` (the PyTorch-ROCm formulation the module ran before the cattn kernels existed), alternating, after warm-up,
+device-synchronised (one HIP-event pair per iteration), and prints the peak memory of each above the baseline.
+
+    python tools/cattn_probe.py [--batch 8] [--n 2561] [--iters 20] [--warmup 3] [--mode bf16x3-fwd] [--kernels-only] [--json PATH]
+
+--kernels-only runs just the kernel path (e.g. under `rocprofv3 --kernel-trace --stats`).  The MFMA roof fraction quoted is the algorithmic
+FLOP count of the visible (query, key) pairs (kernels._c_work: 2 products forward, 5 backward) over 2.5 PFLOP/s dense bf16 / fp16."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nuwa_pytorch_amd as A  # noqa: E402
+from nuwa_pytorch_amd import kernels as K  # noqa: E402
+
+MFMA_ROOF = 2.5e15
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=8)
+    ap.add_argument('--n', type=int, default=2561)
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--mode', default='bf16x3-fwd')
+    ap.add_argument('--kernels-only', action='store_true')
+    ap.add_argument('--json', default=None)
+    args = ap.parse_args()
+    dev = 'cuda'
+    torch.manual_seed(0)
+    A.set_precision(args.mode)
+    m = A.Attention(dim=512, heads=8, dim_head=64, causal=True).to(dev)
+    x = torch.randn(args.batch, args.n, 512, device=dev, requires_grad=True)
+    dy = torch.randn(args.batch, args.n, 512, device=dev)
+    assert m._causal_hip_ok(args.n), 'the module would not take the kernel path in this mode'
+
+    def step(fn):
+        m.zero_grad(set_to_none=True)
+        x.grad = None
+        y = fn(x)
+        y.backward(dy)
+
+    paths = [('cattn', m)] + ([] if args.kernels_only else [('torch', m._forward_torch)])
+    times, peaks = {k: [] for k, _ in paths}, {}
+    for name, fn in paths:                                   # warm-up + peak memory, one path at a time
+        for _ in range(args.warmup):
+            step(fn)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        step(fn)
+        torch.cuda.synchronize()
+        peaks[name] = torch.cuda.max_memory_allocated() - base
+    for _ in range(args.iters):                              # alternate the two paths
+        for name, fn in paths:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            step(fn)
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1))
+    g = K.cattn_geom(args.batch, args.n, 8, 64, causal=True)
+    flops = K._c_work('fwd')((g,), {}, None)[0] + K._c_work('bwd')((g,), {}, None)[0]
+    res = dict(batch=args.batch, n=args.n, mode=args.mode, iters=args.iters, core_flops=flops)
+    for name, _ in paths:
+        t = times[name]
+        res[name] = dict(ms_median=statistics.median(t), ms_min=min(t), ms_max=max(t), peak_bytes=peaks[name])
+        print(f'{name:6s} forward + backward: median {statistics.median(t):9.3f} ms  (min {min(t):.3f}, max {max(t):.3f}, {len(t)} iterations)   '
+              f'peak above the baseline {peaks[name] / 1e6:10.1f} MB')
+    if 'torch' in res:
+        res['ratio'] = res['torch']['ms_median'] / res['cattn']['ms_median']
+        print(f"torch / cattn = {res['ratio']:.2f} x")
+    # the module time includes the three projections and their gradients; the per-kernel split comes from a profiler run (--kernels-only)
+    res['roof_fraction_whole_module'] = flops / (res['cattn']['ms_median'] * 1e-3) / MFMA_ROOF
+    print(f"core FLOPs (visible pairs) {flops / 1e9:.1f} G  ->  {res['roof_fraction_whole_module'] * 100:.2f} % of the MFMA roof over the WHOLE module time")
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, 'w') as f:
+            json.dump(res, f, indent=1)
+    A.set_precision('bf16')
+
+
+if __name__ == '__main__':
+    main()
