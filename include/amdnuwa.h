@@ -35,7 +35,7 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 *     o_lo_f16 on the two fp16 forward cores; 16: the fp16-gradient backward; 17: amdnuwa_gemm_desc.a_chunk32, amdnuwa_gemm_tn_chunked_a_supported,
                                                 *     amdnuwa_xattn2_bwd_ex, AMDNUWA_LN_RESID_MINUS, tuning key 25; 18: the amdnuwa_xattn6_* family; 19: amdnuwa_sparse3dna_bwd_f16, amdnuwa_xattn6_bwd_f16, amdnuwa_xattn6_pack_bwd_f16, o == NULL in the two fp16 forward cores,
                                                 *     ab_f16 on the whole-M TN kernel with alpha_dev in its direct epilogue, c_f16 on the two-MFMA NT product;
-                                                * 20: the amdnuwa_cattn_* family) */
+                                                * 20: the amdnuwa_cattn_* family, 21: amdnuwa_cattn_geom.n_keys) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -536,27 +536,33 @@ int amdnuwa_xattn6_pack_bwd_f16(const amdnuwa_xattn_geom* g, const uint16_t* kv_
 int amdnuwa_xattn6_bwd_f16(const amdnuwa_xattn_geom* g, const uint16_t* q_f16, int ldq, const uint16_t* dO_f16, int lddo, const amdnuwa_xattn6_kv* kv,
                            const float* null_k, const float* null_v, const float* w_th, const float* stats, uint16_t* dS, uint16_t* Pm, uint16_t* dq,
                            int lddq, float* part_th, size_t part_bytes, amdnuwa_stream stream);
-/* ---- plain self-attention core with linear memory ("cattn", ABI 20; reference nuwa_pytorch.py:339-378 with `context is None`, the causal
- * mask of :364-367 when g->causal): keys = [learned null key | the n rows of the sequence], query i sees the null key and rows 0..i
- * (causal) or every row, minus rows whose key_mask byte is 0 (key_mask [B][n] or NULL; the null key is never masked); fp32 softmax per
- * head, then the heads x heads talking-heads mix, then the product with V.  ANY n >= 1, heads 1..8, dim_head 32 or 64.  q16 / k16 / v16
- * are 16-bit rows [B*n, ld] straight out of the projection GEMMs (k16 and v16 share ldkv: two column ranges of to_kv's output); f16 != 0:
- * fp16 operands and fp16 MFMAs ('bf16x3-fwd'), else bf16.  Nothing of size n x n is written: the forward makes two passes over the keys
- * and leaves stats [B][heads][n][2] = (maximum of the scaled scores in the log2 domain incl. the null key, 1 / sum of exp2), the backward
+/* ---- plain attention core with linear memory ("cattn", ABI 20; reference nuwa_pytorch.py:339-378, the causal mask of :364-367 when
+ * g->causal): keys = [learned null key | the T key rows], query i sees the null key and rows 0..i (causal) or every row, minus rows
+ * whose key_mask byte is 0 (key_mask [B][T] or NULL; the null key is never masked); fp32 softmax per head, then the heads x heads
+ * talking-heads mix, then the product with V.  ANY n >= 1, heads 1..8, dim_head 32 or 64.
+ * ABI 21, the rectangular form: g->n_keys = T key rows per sample taken from another tensor (a context); 0 means T = n, self-attention,
+ * exactly the ABI 20 behaviour.  With T != n: q16 / dO / o / dq are [B*n, ld], k16 / v16 / dk / dv [B*T, ldkv], stats stays
+ * [B][heads][n][2]; causal != 0 is then unsupported (amdnuwa_cattn_supported returns 0, the entry points AMDNUWA_ERR_UNSUPPORTED).
+ * q16 / k16 / v16 are 16-bit rows straight out of the projection GEMMs (k16 and v16 share ldkv: two column ranges of to_kv's output);
+ * f16 != 0: fp16 operands and fp16 MFMAs ('bf16x3-fwd'), else bf16.  Nothing of size n x T is written: the forward makes two passes over
+ * the keys and leaves stats [B][heads][n][2] = (maximum of the scaled scores in the log2 domain incl. the null key, 1 / sum of exp2), the backward
  * recomputes the probabilities from q, k and stats.  o / o_lo / o_lo_f16 as amdnuwa_xattn6_fwd (o == NULL with o_lo_f16: the fp16 copy alone). */
 typedef struct {
-    int B, n;               /* samples, sequence length (queries == keys) */
+    int B, n;               /* samples, query rows per sample */
     int heads, dim_head;    /* heads 1..8, dim_head in {32, 64} */
     float scale;
-    int causal;             /* != 0: query i sees keys 0..i */
+    int causal;             /* != 0: query i sees keys 0..i (needs n_keys == 0 or n_keys == n) */
+    int n_keys;             /* ABI 21: key rows per sample; 0 = n (self-attention) */
 } amdnuwa_cattn_geom;
 int amdnuwa_cattn_supported(const amdnuwa_cattn_geom* g);
 int amdnuwa_cattn_fwd(const amdnuwa_cattn_geom* g, const uint16_t* q16, int ldq, const uint16_t* k16, const uint16_t* v16, int ldkv,
                       const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o, uint16_t* o_lo,
                       int ldo, int o_lo_f16, float* stats, int f16, amdnuwa_stream stream);
-/* The recomputing backward on bf16 operands (q / k / v / dO [B*n, ld] bf16, stats from the forward): a query-stationary sweep for
+/* The recomputing backward on bf16 operands (q / dO [B*n, ld], k / v [B*T, ldkv] bf16, stats from the forward): a query-stationary sweep for
  * delta[h][i] = sum_j P_h dP_h (the head mix sits between P and O, so O . dO does not give it), one for dq, key-stationary sweeps over the
- * query tiles at or below the diagonal for dk and dv.  dq / dk / dv leave as bf16 rows (dk and dv share lddkv); dw_th is [8][8] fp32 with
+ * query tiles (causal: those at or below the diagonal) for dk and dv.  The query-stationary sweeps run B * ceil(n / 64) workgroups, the
+ * key-stationary ones B * ceil(T / 64); only the former leave partials, so the workspace grows with n and does not depend on T.
+ *  dq / dk / dv leave as bf16 rows (dk and dv share lddkv); dw_th is [8][8] fp32 with
  * dW_th[g][h] at 8 g + h (rows / columns >= heads are zero), dnull_k / dnull_v [heads][dim_head] fp32.  No atomics: per-workgroup partials
  * inside `workspace` (>= _workspace_bytes, AMDNUWA_ERR_WORKSPACE otherwise) are reduced in a fixed order, two runs are bit-identical. */
 size_t amdnuwa_cattn_bwd_workspace_bytes(const amdnuwa_cattn_geom* g);

@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # AMDNUWA_LIBRARY: another build of the same library (A/B runs of compiler options inside one process group; tools/ only)
 LIB_PATH = os.environ.get('AMDNUWA_LIBRARY') or os.path.join(HERE, 'lib', 'libamdnuwa.so')
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 P = C.c_void_p
 I = C.c_int
@@ -46,7 +46,7 @@ class X6KV(C.Structure):
 
 
 class CGeom(C.Structure):
-    _fields_ = [('B', I), ('n', I), ('heads', I), ('dim_head', I), ('scale', F), ('causal', I)]
+    _fields_ = [('B', I), ('n', I), ('heads', I), ('dim_head', I), ('scale', F), ('causal', I), ('n_keys', I)]
 
 
 class ConvDesc(C.Structure):

@@ -1,7 +1,8 @@
-// Plain self-attention core with linear memory ("cattn"): np.py:339-378 with `context is None`, causal (np.py:364-367) or not,
-// any sequence length, heads 1..8, dim_head 32 / 64.  Keys = [learned null key | the n sequence rows]; fp32 softmax per head, THEN the
+// Plain attention core with linear memory ("cattn"): np.py:339-378, causal self-attention (np.py:364-367) or non-causal attention of n
+// query rows over nk key rows of the same or of another tensor (a context), any lengths, heads 1..8, dim_head 32 / 64.
+// Keys = [learned null key | the nk key rows]; fp32 softmax per head, THEN the
 // heads x heads talking-heads mix, then the product with V -- so the forward is two passes over the keys (statistics, then apply), and the
-// backward recomputes the probabilities from q, k and the statistics.  Nothing of size n x n is ever written to memory.
+// backward recomputes the probabilities from q, k and the statistics.  Nothing of size n x nk is ever written to memory.
 //
 // One schedule serves every sweep.  A workgroup of four waves owns 64 STATIONARY rows (16 per wave, all heads, operands in registers) and
 // streams the other side through LDS 32 rows at a time:
@@ -19,6 +20,8 @@
 // the streamed side's transposed LDS copy stores its 32 rows in that slot order (slot_of).  So probabilities never leave the registers
 // between the two MFMAs, and the head mix runs on the lane's own values (VALU: heads x heads FMAs per probability).
 // The null key is not a key row: its score is one dot product per (query, head), its value a rank-one term (as in xattn6.hip).
+// Rectangular (nk != n): the query-stationary sweeps run ceil(n / 64) workgroups per sample over ceil(nk / 32) key tiles, the key-stationary
+// ones ceil(nk / 64) workgroups over ceil(n / 32) query tiles; row bases and ragged-tile predicates are per side (Item).
 // Causal: key tiles above the diagonal are never staged; a wave skips tiles that lie wholly above its own 16 rows; the predicate is per element.
 // No atomics: dW_th / dnull_k / dnull_v leave as per-workgroup partials reduced in a fixed order (amdnuwa_colsum).
 #include "common.h"
@@ -40,17 +43,17 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 #define HEAD_FENCE() __builtin_amdgcn_sched_barrier(0)
 
 struct CArgs {
-    const uint16_t *q, *k, *v, *dO;          // [B*n, ld] 16-bit rows
+    const uint16_t *q, *k, *v, *dO;          // q / dO [B*n, ld], k / v [B*nk, ldkv] 16-bit rows
     int ldq, ldkv, lddo;
-    const uint8_t* mask;                     // [B][n] key mask or NULL
+    const uint8_t* mask;                     // [B][nk] key mask or NULL
     const float *null_k, *null_v, *wth;      // [heads][DH], [heads][DH], [heads][heads]
     uint16_t *o, *ol; int ldo, ol_f16;
     float* stats;                            // [B][heads][n][2] = (maximum in the log2 domain, 1 / sum of exp2)
     float* delta;                            // [B][heads][n]
     float *ds0, *a0;                         // [B*n][8]: scale * dS of the null key per head, mixed null probability per head
-    uint16_t *dq, *dk, *dv; int lddq, lddkv;
+    uint16_t *dq, *dk, *dv; int lddq, lddkv; // dq [B*n, lddq], dk / dv [B*nk, lddkv]
     float* part_th;                          // [workgroups][64]: dW_th partials, index 8 g + h
-    int B, n, heads, causal;
+    int B, n, nk, heads, causal;             // n query rows and nk key rows per sample (nk == n: self-attention; causal needs it)
     float c1, scale;                         // scale * log2(e), scale
 };
 
@@ -118,19 +121,22 @@ __device__ __forceinline__ void score8(const char* rm, int pitch, int h, int r16
 }
 
 // the work item of a workgroup: sample b, stationary rows [x0, x0 + 64), streamed tiles [y_begin, y_end)
-struct Item { int b, x0, y_begin, y_end; };
+// nx stationary and ny streamed rows per sample (query side: n and nk; key side: nk and n), rowx / rowy the sample's first row on each side
+struct Item { int b, x0, y_begin, y_end, nx, ny; long rowx, rowy; };
 template <bool KEYSIDE>
 __device__ __forceinline__ Item item_of(const CArgs& a) {
-    const int ntx = (a.n + XW - 1) / XW, NT = (a.n + YT - 1) / YT;
     Item it;
+    it.nx = KEYSIDE ? a.nk : a.n; it.ny = KEYSIDE ? a.n : a.nk;
+    const int ntx = (it.nx + XW - 1) / XW, NT = (it.ny + YT - 1) / YT;
     it.b = blockIdx.x % a.B;
     int t = blockIdx.x / a.B;
     if (!KEYSIDE) t = ntx - 1 - t;            // causal: the long items first (the key side's natural order already is)
     it.x0 = t * XW;
+    it.rowx = (long)it.b * it.nx; it.rowy = (long)it.b * it.ny;
     it.y_begin = 0; it.y_end = NT;
     if (a.causal) {
         if (KEYSIDE) it.y_begin = it.x0 / YT;
-        else { const int last = (it.x0 + XW < a.n ? it.x0 + XW : a.n) - 1; it.y_end = last / YT + 1; }
+        else { const int last = (it.x0 + XW < it.nx ? it.x0 + XW : it.nx) - 1; it.y_end = last / YT + 1; }
     }
     return it;
 }
@@ -139,7 +145,7 @@ __device__ __forceinline__ Item item_of(const CArgs& a) {
 __device__ __forceinline__ void stage_vbits(const CArgs& a, long rowb, int y0, uint32_t* svb, int tid) {
     if (tid < 64) {
         const int key = y0 + tid;
-        const bool ok = tid < YT && key < a.n && (!a.mask || a.mask[rowb + key] != 0);
+        const bool ok = tid < YT && key < a.nk && (!a.mask || a.mask[rowb + key] != 0);
         const unsigned long long bal = __ballot(ok);
         if (tid == 0) *svb = (uint32_t)bal;
     }
@@ -185,15 +191,15 @@ __global__ __launch_bounds__(256, 1) void cattn_apply_kernel(CArgs a) {
     float* sst = reinterpret_cast<float*>(tr + inner * TP);           // key side: [2][8][32] statistics of the streamed queries
     uint32_t* svb = reinterpret_cast<uint32_t*>(sst + 2 * NHM * YT);
     const Item it = item_of<KEYSIDE>(a);
-    const long rowb = (long)it.b * a.n;
+    const long rowb = it.rowx, rowy = it.rowy;
     const int xw = it.x0 + 16 * wave, x = xw + r16;
-    const bool xin = x < a.n;
+    const bool xin = x < it.nx;
     const bool xok = KEYSIDE ? (xin && (!a.mask || a.mask[rowb + (xin ? x : 0)] != 0)) : xin;
     const uint16_t* xsrc = KEYSIDE ? a.k : a.q;
     const int xld = KEYSIDE ? a.ldkv : a.ldq;
-    const uint16_t* ysrc_rm = (KEYSIDE ? a.q : a.k) + rowb * (KEYSIDE ? a.ldq : a.ldkv);
+    const uint16_t* ysrc_rm = (KEYSIDE ? a.q : a.k) + rowy * (KEYSIDE ? a.ldq : a.ldkv);
     const int yld_rm = KEYSIDE ? a.ldq : a.ldkv;
-    const uint16_t* ysrc_tr = (KEYSIDE ? a.dO : a.v) + rowb * (KEYSIDE ? a.lddo : a.ldkv);
+    const uint16_t* ysrc_tr = (KEYSIDE ? a.dO : a.v) + rowy * (KEYSIDE ? a.lddo : a.ldkv);
     const int yld_tr = KEYSIDE ? a.lddo : a.ldkv;
 
     bf16x8 xf[NHM][KS];
@@ -219,8 +225,8 @@ __global__ __launch_bounds__(256, 1) void cattn_apply_kernel(CArgs a) {
         for (int yt = it.y_begin; yt < it.y_end; ++yt) {
             const int y0 = yt * YT;
             __syncthreads();
-            stage_tile<true, false>(ysrc_rm, yld_rm, y0, a.n, inner, rm, pitch, nullptr, tid);
-            stage_vbits(a, rowb, y0, svb, tid);
+            stage_tile<true, false>(ysrc_rm, yld_rm, y0, it.ny, inner, rm, pitch, nullptr, tid);
+            stage_vbits(a, rowy, y0, svb, tid);
             __syncthreads();
             if (a.causal && y0 > xw + 15) continue;
             const unsigned vm = valid_bits<false>(a, x, xok, y0, g4, *svb);
@@ -271,15 +277,15 @@ __global__ __launch_bounds__(256, 1) void cattn_apply_kernel(CArgs a) {
     for (int yt = it.y_begin; yt < it.y_end; ++yt) {
         const int y0 = yt * YT;
         __syncthreads();
-        stage_tile<true, false>(ysrc_rm, yld_rm, y0, a.n, inner, rm, pitch, nullptr, tid);
-        stage_tile<false, true>(ysrc_tr, yld_tr, y0, a.n, inner, nullptr, 0, tr, tid);
+        stage_tile<true, false>(ysrc_rm, yld_rm, y0, it.ny, inner, rm, pitch, nullptr, tid);
+        stage_tile<false, true>(ysrc_tr, yld_tr, y0, it.ny, inner, nullptr, 0, tr, tid);
         if (KEYSIDE) {
             const int h = tid >> 5, r = tid & 31, qy = y0 + r;
             float mv = 0.f, iv = 0.f;
             if (h < heads && qy < a.n) { const float* st = a.stats + (((long)it.b * heads + h) * a.n + qy) * 2; mv = st[0]; iv = st[1]; }
             sst[h * YT + r] = mv; sst[NHM * YT + h * YT + r] = iv;
         } else {
-            stage_vbits(a, rowb, y0, svb, tid);
+            stage_vbits(a, rowy, y0, svb, tid);
         }
         __syncthreads();
         if (a.causal && (KEYSIDE ? (y0 + YT - 1 < xw) : (y0 > xw + 15))) continue;
@@ -382,13 +388,13 @@ __global__ __launch_bounds__(256, 1) void cattn_grad_kernel(CArgs a) {
     uint32_t* svb = reinterpret_cast<uint32_t*>(sst + 3 * NHM * YT);
     float* sred = reinterpret_cast<float*>(svb + 4);     // [4][64] dW_th of the four waves
     const Item it = item_of<KEYSIDE>(a);
-    const long rowb = (long)it.b * a.n;
+    const long rowb = it.rowx, rowy = it.rowy;
     const int xw = it.x0 + 16 * wave, x = xw + r16;
-    const bool xin = x < a.n;
+    const bool xin = x < it.nx;
     const bool xok = KEYSIDE ? (xin && (!a.mask || a.mask[rowb + (xin ? x : 0)] != 0)) : xin;
-    const uint16_t* ysrc1 = (KEYSIDE ? a.q : a.k) + rowb * (KEYSIDE ? a.ldq : a.ldkv);
+    const uint16_t* ysrc1 = (KEYSIDE ? a.q : a.k) + rowy * (KEYSIDE ? a.ldq : a.ldkv);
     const int yld1 = KEYSIDE ? a.ldq : a.ldkv;
-    const uint16_t* ysrc2 = (KEYSIDE ? a.dO : a.v) + rowb * (KEYSIDE ? a.lddo : a.ldkv);
+    const uint16_t* ysrc2 = (KEYSIDE ? a.dO : a.v) + rowy * (KEYSIDE ? a.lddo : a.ldkv);
     const int yld2 = KEYSIDE ? a.lddo : a.ldkv;
 
     bf16x8 xf1[NHM][KS], xf2[NHM][KS];
@@ -429,8 +435,8 @@ __global__ __launch_bounds__(256, 1) void cattn_grad_kernel(CArgs a) {
     for (int yt = it.y_begin; yt < it.y_end; ++yt) {
         const int y0 = yt * YT;
         __syncthreads();
-        stage_tile<true, MODE == 1>(ysrc1, yld1, y0, a.n, inner, rm1, pitch, tr, tid);
-        stage_tile<true, false>(ysrc2, yld2, y0, a.n, inner, rm2, pitch, nullptr, tid);
+        stage_tile<true, MODE == 1>(ysrc1, yld1, y0, it.ny, inner, rm1, pitch, tr, tid);
+        stage_tile<true, false>(ysrc2, yld2, y0, it.ny, inner, rm2, pitch, nullptr, tid);
         if (KEYSIDE) {
             const int h = tid >> 5, r = tid & 31, qy = y0 + r;
             float mv = 0.f, iv = 0.f, dv_ = 0.f;
@@ -440,7 +446,7 @@ __global__ __launch_bounds__(256, 1) void cattn_grad_kernel(CArgs a) {
             }
             sst[h * YT + r] = mv; sst[NHM * YT + h * YT + r] = iv; sst[2 * NHM * YT + h * YT + r] = dv_;
         } else {
-            stage_vbits(a, rowb, y0, svb, tid);
+            stage_vbits(a, rowy, y0, svb, tid);
         }
         __syncthreads();
         if (a.causal && (KEYSIDE ? (y0 + YT - 1 < xw) : (y0 > xw + 15))) continue;
@@ -571,11 +577,14 @@ __global__ __launch_bounds__(256) void cattn_null_grads_kernel(const uint16_t* _
     }
 }
 
+int keys_of(const amdnuwa_cattn_geom* g) { return g->n_keys ? g->n_keys : g->n; }      // 0 = self-attention
 int check_c(const amdnuwa_cattn_geom* g) {
     if (!g) return AMDNUWA_ERR_ARG;
     if (g->heads < 1 || g->heads > NHM || (g->dim_head != 32 && g->dim_head != 64)) return AMDNUWA_ERR_UNSUPPORTED;
-    if (g->B < 1 || g->n < 1) return AMDNUWA_ERR_ARG;
-    if ((long long)g->B * g->n > 0x7fffffffLL / 1024) return AMDNUWA_ERR_UNSUPPORTED;      // (row * ld stays far inside 63 bits; the grid inside 31)
+    if (g->B < 1 || g->n < 1 || g->n_keys < 0) return AMDNUWA_ERR_ARG;
+    if (g->causal && keys_of(g) != g->n) return AMDNUWA_ERR_UNSUPPORTED;                   // the causal predicate is defined for queries == keys only
+    if ((long long)g->B * g->n > 0x7fffffffLL / 1024 || (long long)g->B * keys_of(g) > 0x7fffffffLL / 1024)
+        return AMDNUWA_ERR_UNSUPPORTED;                                                      // (row * ld stays far inside 63 bits; the grid inside 31)
     return AMDNUWA_OK;
 }
 size_t lds_apply(const amdnuwa_cattn_geom* g) {
@@ -591,7 +600,9 @@ void launch(Kern kern, int grid, size_t lds, hipStream_t stream, const CArgs& a)
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
 }
+// workgroups of the query-stationary sweeps (the only ones that leave per-workgroup partials) and of the key-stationary sweeps
 long long wgs(const amdnuwa_cattn_geom* g) { return (long long)g->B * ((g->n + XW - 1) / XW); }
+long long wgs_k(const amdnuwa_cattn_geom* g) { return (long long)g->B * ((keys_of(g) + XW - 1) / XW); }
 long long null_chunks(const amdnuwa_cattn_geom* g) { return ((long long)g->B * g->n + 255) / 256; }
 size_t al(size_t v) { return (v + 255) / 256 * 256; }
 
@@ -610,7 +621,7 @@ extern "C" int amdnuwa_cattn_fwd(const amdnuwa_cattn_geom* g, const uint16_t* q1
     CArgs a{};
     a.q = q16; a.k = k16; a.v = v16; a.ldq = ldq; a.ldkv = ldkv; a.mask = key_mask;
     a.null_k = null_k; a.null_v = null_v; a.wth = w_th; a.o = o; a.ol = o_lo; a.ldo = ldo; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0; a.stats = stats;
-    a.B = g->B; a.n = g->n; a.heads = g->heads; a.causal = g->causal ? 1 : 0; a.scale = g->scale; a.c1 = g->scale * 1.4426950408889634f;
+    a.B = g->B; a.n = g->n; a.nk = keys_of(g); a.heads = g->heads; a.causal = g->causal ? 1 : 0; a.scale = g->scale; a.c1 = g->scale * 1.4426950408889634f;
     const int grid = (int)wgs(g);
     const size_t lds = lds_apply(g);
     if (g->dim_head == 64) {
@@ -657,8 +668,8 @@ extern "C" int amdnuwa_cattn_bwd(const amdnuwa_cattn_geom* g, const uint16_t* q,
     void* cws1 = take(cs1);
     void* cws2 = take(cs2);
     a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddkv = lddkv;
-    a.B = g->B; a.n = g->n; a.heads = g->heads; a.causal = g->causal ? 1 : 0; a.scale = g->scale; a.c1 = g->scale * 1.4426950408889634f;
-    const int grid = (int)wgs(g);
+    a.B = g->B; a.n = g->n; a.nk = keys_of(g); a.heads = g->heads; a.causal = g->causal ? 1 : 0; a.scale = g->scale; a.c1 = g->scale * 1.4426950408889634f;
+    const int grid = (int)wgs(g), grid_k = (int)wgs_k(g);
     const bool d64 = g->dim_head == 64;
     // 1. delta, the talking-heads partials and the null key's dS / A per query
     if (d64) launch(cattn_grad_kernel<64, false, 0>, grid, lds_grad(g, 0), stream, a);
@@ -668,11 +679,11 @@ extern "C" int amdnuwa_cattn_bwd(const amdnuwa_cattn_geom* g, const uint16_t* q,
     if (d64) launch(cattn_grad_kernel<64, false, 1>, grid, lds_grad(g, 1), stream, a);
     else launch(cattn_grad_kernel<32, false, 1>, grid, lds_grad(g, 1), stream, a);
     LAUNCH_CHECK();
-    if (d64) launch(cattn_grad_kernel<64, true, 1>, grid, lds_grad(g, 1), stream, a);
-    else launch(cattn_grad_kernel<32, true, 1>, grid, lds_grad(g, 1), stream, a);
+    if (d64) launch(cattn_grad_kernel<64, true, 1>, grid_k, lds_grad(g, 1), stream, a);
+    else launch(cattn_grad_kernel<32, true, 1>, grid_k, lds_grad(g, 1), stream, a);
     LAUNCH_CHECK();
-    if (d64) launch(cattn_apply_kernel<64, false, true>, grid, lds_apply(g), stream, a);
-    else launch(cattn_apply_kernel<32, false, true>, grid, lds_apply(g), stream, a);
+    if (d64) launch(cattn_apply_kernel<64, false, true>, grid_k, lds_apply(g), stream, a);
+    else launch(cattn_apply_kernel<32, false, true>, grid_k, lds_apply(g), stream, a);
     LAUNCH_CHECK();
     // 3. the small gradients: fixed-order reductions of the partials
     hipLaunchKernelGGL(cattn_null_grads_kernel, dim3((unsigned)null_chunks(g)), dim3(256), 0, stream, q, ldq, dO, lddo, a.ds0, a.a0, part_null, (long)rows,

@@ -83,7 +83,7 @@ class IncrementalDecoder:
                 if blk.xm is not None:
                     inner, fmap = mod.fn, None
                 else:
-                    found = mod._inner(ctx_arg, seq_len=max_rows)
+                    found = mod._inner(ctx_arg, seq_len=max_rows, batch=batch)
                     if found is None and isinstance(mod.fn, SparseCausal2DNA) and mod.fn._hip_ok():
                         found = (mod.fn, None)                         # audio tower built without the channel shift
                     if found is None:
@@ -114,6 +114,10 @@ class IncrementalDecoder:
                 if inner.causal:
                     # plain causal self-attention has no cached single-row path: generate() keeps the recompute loop for such stacks
                     raise NotImplementedError('IncrementalDecoder: no single-row path for plain (causal) self-attention')
+                if context.shape[1] + 1 > 288:
+                    # the single-query kernel (xattn_decode) reads packed key images of at most 288 keys; a longer context trains on the cattn
+                    # kernels, which have no cached single-row form: generate() keeps the recompute loop
+                    raise NotImplementedError('IncrementalDecoder: no single-row path for cross-attention over more than 287 context keys')
                 blk.kind = 'x'
                 p = inner._params()
                 W = ops.XInner.weights(inner._cache, p)

@@ -1405,13 +1405,19 @@ def xattn6_bwd(g, q, dO, pk, wth, stats):
 
 
 # ------------------------------------------------------------------------------------------------
-# plain (causal) self-attention with linear memory: the cattn family
+# plain attention with linear memory (causal self-attention; non-causal over any number of own or context keys): the cattn family
 # ------------------------------------------------------------------------------------------------
 
-def cattn_geom(B, n, heads, dim_head, causal=True):
+def cattn_geom(B, n, heads, dim_head, causal=True, n_keys=None):
+    """n query rows per sample; n_keys key rows taken from another tensor (None = the query rows: self-attention; non-causal only otherwise)"""
     g = CGeom()
     g.B, g.n, g.heads, g.dim_head, g.scale, g.causal = B, n, heads, dim_head, dim_head ** -0.5, 1 if causal else 0
+    g.n_keys = 0 if n_keys is None or n_keys == n else n_keys
     return g
+
+
+def cattn_keys(g):
+    return g.n_keys or g.n
 
 
 def cattn_supported(g):
@@ -1419,14 +1425,16 @@ def cattn_supported(g):
 
 
 def _c_work(kind):
-    """algorithmic MFMA work of the cattn cores over the VISIBLE (query, key) pairs only -- the causal half plus the null key (U = one
-    2 pairs d product): forward QK^T + A V + head mix; backward S, dA, dq, dk, dv + two mixes"""
+    """algorithmic MFMA work of the cattn cores over the VISIBLE (query, key) pairs only -- the causal half plus the null key, or all
+    n x (T + 1) pairs of the non-causal form (U = one 2 pairs d product): forward QK^T + A V + head mix; backward S, dA, dq, dk, dv + two mixes"""
     def w(a, k, r):
         g = a[0]
-        pairs = float(g.B) * g.heads * (g.n * (g.n + 1) / 2.0 + g.n if g.causal else g.n * (g.n + 1.0))
+        T = cattn_keys(g)
+        pairs = float(g.B) * g.heads * (g.n * (g.n + 1) / 2.0 + g.n if g.causal else g.n * (T + 1.0))
         U, mix = 2.0 * pairs * g.dim_head, 2.0 * pairs * g.heads
-        act = 2.0 * g.B * g.n * g.heads * g.dim_head                       # one 16-bit [B*n, inner] tensor
-        return ((2 * U + mix, 4 * act) if kind == 'fwd' else (5 * U + 2 * mix, 7 * act))
+        actq = 2.0 * g.B * g.n * g.heads * g.dim_head                      # one 16-bit [B*n, inner] tensor (q, o, dO, dq)
+        actk = 2.0 * g.B * T * g.heads * g.dim_head                        # ... and one [B*T, inner] (k, v, dk, dv)
+        return ((2 * U + mix, 2 * actq + 2 * actk) if kind == 'fwd' else (5 * U + 2 * mix, 3 * actq + 4 * actk))
     return w
 
 
@@ -1437,14 +1445,15 @@ def _rows16(t, inner):
 
 @_family('cattn', _c_work('fwd'))
 def cattn_fwd(g, q16, k16, v16, null_k, null_v, wth, mask_u8=None, o_f16=False, lo=True):
-    """the cattn forward core on 16-bit rows q16 / k16 / v16 [B*n, inner] (views with a row stride; k16 and v16 share theirs: the two
+    """the cattn forward core on 16-bit rows q16 [B*n, inner], k16 / v16 [B*T, inner] (T = the geometry's key count; views with a row stride; k16 and v16 share theirs: the two
     halves of to_kv's output).  fp16 rows: every MFMA the fp16 one; else bf16.  Returns o BF [B*n, inner] (hi + lo pair; with o_f16 a bf16
     copy + an fp16 copy; lo=False: the bf16 copy alone) and the softmax statistics [B, heads, n, 2]"""
     L = _lib.lib()
     inner = g.heads * g.dim_head
     f16 = q16.dtype == torch.float16
     _rows16(q16, inner), _rows16(k16, inner), _rows16(v16, inner)
-    assert k16.dtype == q16.dtype == v16.dtype and k16.stride(0) == v16.stride(0) and q16.shape[0] == g.B * g.n == k16.shape[0]
+    assert k16.dtype == q16.dtype == v16.dtype and k16.stride(0) == v16.stride(0) and q16.shape[0] == g.B * g.n
+    assert k16.shape[0] == v16.shape[0] == g.B * cattn_keys(g) and (mask_u8 is None or mask_u8.numel() == k16.shape[0])
     _chk_dev(q16, k16, v16, null_k, null_v, wth, mask_u8)
     dev = q16.device
     if o_f16:
@@ -1461,9 +1470,9 @@ def cattn_fwd(g, q16, k16, v16, null_k, null_v, wth, mask_u8=None, o_f16=False, 
 
 @_family('cattn', _c_work('bwd'))
 def cattn_bwd(g, q, k, v, dO, null_k, null_v, wth, stats, mask_u8=None):
-    """the recomputing cattn backward on bf16 rows (q / k / v / dO [B*n, inner] views) and the forward's statistics.  Returns dq BF
-    [B*n, inner], dkv BF [B*n, 2 inner] (dk | dv: the layout of to_kv's output), dw_th [heads, heads], dnull_k and dnull_v [heads, dim_head]
-    fp32.  No n x n array: the workspace is O(B n heads) floats"""
+    """the recomputing cattn backward on bf16 rows (q / dO [B*n, inner], k / v [B*T, inner] views) and the forward's statistics.  Returns dq BF
+    [B*n, inner], dkv BF [B*T, 2 inner] (dk | dv: the layout of to_kv's output), dw_th [heads, heads], dnull_k and dnull_v [heads, dim_head]
+    fp32.  No n x T array: the workspace is O(B n heads) floats"""
     L = _lib.lib()
     inner = g.heads * g.dim_head
     for t in (q, k, v, dO):
@@ -1471,9 +1480,10 @@ def cattn_bwd(g, q, k, v, dO, null_k, null_v, wth, stats, mask_u8=None):
     assert k.stride(0) == v.stride(0)
     _chk_dev(q, k, v, dO, null_k, null_v, wth, stats, mask_u8)
     dev = q.device
-    R = g.B * g.n
+    R, RK = g.B * g.n, g.B * cattn_keys(g)
+    assert q.shape[0] == dO.shape[0] == R and k.shape[0] == v.shape[0] == RK and (mask_u8 is None or mask_u8.numel() == RK)
     dq = torch.empty((R, inner), dtype=torch.bfloat16, device=dev)
-    dkv = torch.empty((R, 2 * inner), dtype=torch.bfloat16, device=dev)
+    dkv = torch.empty((RK, 2 * inner), dtype=torch.bfloat16, device=dev)
     small = torch.empty(64 + 2 * inner, dtype=torch.float32, device=dev)
     nb = L.amdnuwa_cattn_bwd_workspace_bytes(C.byref(g))
     ws = workspace(nb, dev)

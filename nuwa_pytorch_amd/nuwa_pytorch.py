@@ -158,9 +158,9 @@ class SandwichNorm(nn.Module):
         return ops.LayerNormFn.apply(x, self.postnorm.weight, self.postnorm.bias, False)
 
     # -- fused path -------------------------------------------------------------------------------
-    def _inner(self, context=None, seq_len=None):
+    def _inner(self, context=None, seq_len=None, batch=None):
         """(inner module, shift or None) when fn is one of the fusable hot modules, else None.
-        An Attention is fusable only as cross-attention (context given)."""
+        An Attention is fusable only as cross-attention (context given).  (batch: only the long-key route asks for it.)"""
         fn, shift = self.fn, None
         if isinstance(fn, ShiftVideoTokens):
             if fn.shift_time:
@@ -182,6 +182,9 @@ class SandwichNorm(nn.Module):
             return fn, shift                      # NUWASketch decoder: 2-D nearby cross-attention on the 3DNA kernels (row f4)
         if isinstance(fn, Attention) and context is None and seq_len is not None and fn._causal_hip_ok(seq_len):
             return fn, shift                      # plain causal self-attention (sparse_3dna_attn=False): the linear-memory kernels, any length
+        if isinstance(fn, Attention) and seq_len is not None and (context is not None or batch is not None) and \
+                fn._long_hip_ok(context.shape[1] if context is not None else seq_len, seq_len, context.shape[0] if context is not None else batch):
+            return fn, shift                      # non-causal attention over more than 287 keys (own rows or a context): the same kernels
         return None
 
     def fused_residual(self, x, resid=None, context=None, context_mask=None, mask=None, rotary_pos_emb=None, chain=None, minus=False):
@@ -191,7 +194,7 @@ class SandwichNorm(nn.Module):
         chain = (handoff_in or None, next SandwichNorm or None, next block's fmap, handoff_out dict): lets this block's post-norm
         kernel also emit the next block's pre-norm output (see ops.SandwichBlockFn)"""
         B, n, D = x.shape
-        inner, fmap = self._inner(context, seq_len=n)
+        inner, fmap = self._inner(context, seq_len=n, batch=B)
         meta = inner._meta(B, n, x.device, context=context, context_mask=context_mask, mask=mask, rotary_pos_emb=rotary_pos_emb)
         if fmap is not None:
             if D % 32:
@@ -349,9 +352,11 @@ class Attention(nn.Module):
     """np.py:290-379.  With `context` (the decoder's text cross-attention) and as non-causal self-attention (the text encoder, row f1:
     keys / values = the query rows, rotary on q, k and v) the core runs on the MFMA cross-attention kernels (xattn6; xattn2 / xattn for
     the shapes it does not take).  Causal self-attention (causal=True without a context: the decoder of `sparse_3dna_attn=False`) runs on
-    the linear-memory cattn kernels at any length (`_causal_hip_ok`; precision modes 'bf16x3-fwd' and 'bf16').  What still runs the
-    PyTorch-ROCm forward below: more than 8 heads, dim_head not 32 / 64, attention dropout > 0 in training, non-causal attention over more
-    than 287 keys, causal attention with a context, and causal self-attention in the 'bf16x3' parity mode."""
+    the linear-memory cattn kernels at any length (`_causal_hip_ok`; precision modes 'bf16x3-fwd' and 'bf16'), and so does non-causal
+    attention over more than 287 keys, its own rows or a context's (`_long_hip_ok`: the kernels' rectangular form, n queries x T keys)
+    wherever the shape is large enough for them to be the faster route (`long_pairs_min`, `long_wgs_min`; 0 routes every such shape).
+    What still runs the PyTorch-ROCm forward below: more than 8 heads, dim_head not 32 / 64, attention dropout > 0 in training, causal
+    attention with a context, and the 'bf16x3' parity mode wherever the cattn kernels would serve."""
 
     def __init__(self, *, dim, heads=8, dim_head=64, causal=False, dropout=0.):
         super().__init__()
@@ -382,6 +387,25 @@ class Attention(nn.Module):
         return self.causal and n >= 1 and self.dim_head in (32, 64) and self.heads <= 8 and not (self.training and self.dropout.p > 0) and \
             (K.get_precision() == 'bf16' or K.cores_f16())
 
+    # Where the rectangular cattn form is FASTER than the torch-op formulation (profiles/cattn_long_probe.txt): the kernels are
+    # latency-bound -- a workgroup walks its tiles at some 8 us each whatever the batch -- so they win once the torch ops have enough pairs to
+    # chew on and both sweeps fill the device.  Measured winners: b = 8, 1024 x 1024 (1.17 x), 2561 x 1024 (1.45 x); losers: everything
+    # measured below either bound (0.40 ... 1.04 x).  A user who needs the memory (nothing of size n x T is kept) lowers them: both to 0 routes
+    # every shape above 287 keys.
+    long_pairs_min = 1 << 23         # batch * queries * keys
+    long_wgs_min = 128               # workgroups of the query-stationary and of the key-stationary sweeps: batch * ceil(rows / 64), each
+
+    def _long_hip_ok(self, n_keys, n_queries=None, batch=None):
+        """non-causal attention over more keys than the cross-attention kernels take (self-attention: the query rows; else the context's
+        rows): the cattn kernels' rectangular form, in the precision modes they serve and -- the whole shape given -- where it is the
+        faster route"""
+        ok = (not self.causal) and n_keys > 287 and self.dim_head in (32, 64) and self.heads <= 8 and \
+            not (self.training and self.dropout.p > 0) and (K.get_precision() == 'bf16' or K.cores_f16())
+        if not ok or n_queries is None or batch is None:
+            return ok
+        return batch * n_queries * n_keys >= self.long_pairs_min and \
+            batch * min(-(-n_queries // 64), -(-n_keys // 64)) >= self.long_wgs_min
+
     def _meta(self, B, n, device, context=None, context_mask=None, mask=None, rotary_pos_emb=None, **_):
         assert not (self.training and self.dropout.p > 0)      # (_hip_ok routes attn_dropout > 0 in training to the torch-op forward)
         if self.causal:                               # plain causal self-attention: the cattn kernels (keys = the query rows, key mask = `mask`)
@@ -394,6 +418,12 @@ class Attention(nn.Module):
         self_kv = context is None
         T = n if self_kv else context.shape[1]
         key_mask = mask if self_kv else context_mask
+        if self._long_hip_ok(T, n, B):                # more keys than xattn6 takes: the cattn kernels, n query rows x T key rows
+            meta = dict(kind='cattn', cache=self._cache, cgeom=K.cattn_geom(B, n, self.heads, self.dim_head, causal=False, n_keys=T),
+                        mask_u8=key_mask.to(torch.uint8).contiguous() if exists(key_mask) else None, has_ctx=not self_kv)
+            if self_kv and exists(rotary_pos_emb):
+                meta['rotary'] = rotary_pos_emb.detach().float()
+            return meta
         g = K.x_geom(B, n, T, self.heads, self.dim_head)
         mask_u8 = key_mask.to(torch.uint8).contiguous() if exists(key_mask) else None
         meta = dict(kind='xattn', cache=self._cache, xgeom=g, mask_u8=mask_u8, save=torch.is_grad_enabled())
@@ -411,11 +441,14 @@ class Attention(nn.Module):
         if x.is_cuda and not exists(context) and self._causal_hip_ok(n):
             meta = self._meta(B, n, x.device, mask=mask, rotary_pos_emb=rotary_pos_emb)
             return ops.InnerFn.apply(x, None, meta, *self._params())
+        if x.is_cuda and self._long_hip_ok(context.shape[1] if exists(context) else n, n, B):
+            meta = self._meta(B, n, x.device, context, context_mask, mask=mask, rotary_pos_emb=rotary_pos_emb)
+            return ops.InnerFn.apply(x, context, meta, *self._params())
         return self._forward_torch(x, mask=mask, context=context, context_mask=context_mask, rotary_pos_emb=rotary_pos_emb)
 
     def _forward_torch(self, x, mask=None, context=None, context_mask=None, rotary_pos_emb=None):
-        """np.py:315-379 on PyTorch-ROCm ops, for what the kernels do not cover: causal self-attention, other head sizes, and
-        attn_dropout > 0 in training.  Keys = [null key | context or x]; one additive bias carries the key mask and the causal band."""
+        """np.py:315-379 on PyTorch-ROCm ops, for what the kernels do not cover: other head sizes or more than 8 heads, causal attention with
+        a context, the 'bf16x3' mode of the cattn shapes, and attn_dropout > 0 in training.  Keys = [null key | context or x]; one additive bias carries the key mask and the causal band."""
         b, n, h, dh = x.shape[0], x.shape[1], self.heads, self.dim_head
         src = x if context is None else context
         heads_of = lambda t: t.reshape(b, t.shape[1], -1, dh).transpose(1, 2)               # (b, heads, len, dh)
@@ -692,11 +725,11 @@ class Transformer(nn.Module):
         calls = []
         for attn, cross_attn, ff in self.layers:
             calls.append((attn, dict(mask=mask, rotary_pos_emb=rotary_pos_emb), dict(mask=mask, rotary_pos_emb=rotary_pos_emb),
-                          attn._inner(seq_len=n) if cuda else None))
+                          attn._inner(seq_len=n, batch=x.shape[0]) if cuda else None))
             if exists(cross_attn):
                 calls.append((cross_attn, dict(context=context, context_mask=context_mask),
                               dict(context=context, mask=mask, context_mask=context_mask),
-                              cross_attn._inner(context) if cuda else None))
+                              cross_attn._inner(context, seq_len=n if exists(context) else None) if cuda else None))
             calls.append((ff, {}, {}, ff._inner() if cuda else None))
         if cuda and K.mixed():
             # fp16 range verdicts of every weight the 'bf16x3-fwd' forward may run in fp16, in ONE device -> host transfer per step
@@ -761,7 +794,7 @@ class ReversibleBlock(nn.Module):
 
     def forward(self, x1, x2, f_args={}, g_args={}):
         f, g = self.f.net, self.g.net
-        if isinstance(f, SandwichNorm) and x1.is_cuda and f._inner(f_args.get('context'), seq_len=x2.shape[1]) is not None:
+        if isinstance(f, SandwichNorm) and x1.is_cuda and f._inner(f_args.get('context'), seq_len=x2.shape[1], batch=x2.shape[0]) is not None:
             y1 = f.fused_residual(x2, resid=x1, **{k: f_args.get(k) for k in ('context', 'context_mask', 'mask', 'rotary_pos_emb')})
         else:
             y1 = x1 + f(x2, **f_args)
@@ -775,7 +808,7 @@ class ReversibleBlock(nn.Module):
         """inputs and input-gradients of this block from its outputs and output-gradients (the role of rev.py:77-106);
         parameter gradients of f and g are accumulated by the two inner autograd calls"""
         f, g = self.f.net, self.g.net
-        fuse_f = isinstance(f, SandwichNorm) and y1.is_cuda and f._inner(f_args.get('context'), seq_len=y1.shape[1]) is not None
+        fuse_f = isinstance(f, SandwichNorm) and y1.is_cuda and f._inner(f_args.get('context'), seq_len=y1.shape[1], batch=y1.shape[0]) is not None
         fuse_g = isinstance(g, SandwichNorm) and g._inner() is not None and y1.is_cuda
         # g(y1) again.  Fused form: one node whose value is y2 - g(y1) = x2 (the post-norm kernel subtracts: no negation passes over the
         # stream -- four of them per block, 6 % of the cfg-4 step, in the (-y2) + g(y1) = -x2 form of rounds 2-4; the same bits) and whose

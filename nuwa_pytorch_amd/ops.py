@@ -426,8 +426,8 @@ class XInner:
 
 
 class CInner:
-    """to_q(x), to_kv(x) -> plain self-attention core with linear memory (cattn: causal or not, any length) -> to_out (np.py:315-379 with
-    `context is None`).  params: null_k, null_v, talking_heads.w, to_q.w, to_kv.w, to_out.w  (the layout and weight cache of XInner).
+    """to_q(x), to_kv(x or context) -> plain attention core with linear memory (cattn: causal self-attention, or non-causal attention of the
+    n rows over any number of keys -- their own or, with meta['has_ctx'], the T rows of meta['ctx_bf']) -> to_out (np.py:315-379).  params: null_k, null_v, talking_heads.w, to_q.w, to_kv.w, to_out.w  (the layout and weight cache of XInner).
     'bf16x3-fwd': hi + lo projections with an fp16 copy, the core on fp16 MFMAs, two-MFMA to_out; the backward on the bf16 hi parts.
     'bf16': bf16 throughout.  ('bf16x3' keeps the torch-op formulation: Attention._causal_hip_ok.)"""
     nparams = 6
@@ -447,9 +447,13 @@ class CInner:
         inner = g.heads * g.dim_head
         assert h.hi is not None, 'a bf16 backward needs the bf16 copy of the LayerNorm output'
         h = _f16_to_pair(h)
-        f16 = K.cores_f16() and h.lo is not None
+        has_ctx = bool(meta.get('has_ctx'))
+        ctx = meta['ctx_bf'] if has_ctx else h              # (the context's copy is hi-only or hi + lo as the precision mode wants: _ctx_to_bf)
+        assert not (has_ctx and rot is not None), 'rotary embeddings belong to self-attention'
+        assert K.bf_rows_cols(ctx)[0] == g.B * K.cattn_keys(g)
+        f16 = K.cores_f16() and h.lo is not None and ctx.lo is not None
         q = K.gemm_nt(h, W['q'], out_bf16=True, out_f16=f16 and rot is None)
-        kv = K.gemm_nt(h, W['kv'], out_bf16=True, out_f16=f16 and rot is None)
+        kv = K.gemm_nt(ctx, W['kv'], out_bf16=True, out_f16=f16 and rot is None)
         if rot is not None:
             q = _rotary_bf(q, rot, g.B, g.n, g.heads)
             kv = _rotary_bf(kv, rot, g.B, g.n, 2 * g.heads)
@@ -463,11 +467,11 @@ class CInner:
         else:
             o, stats = K.cattn_fwd(g, q.hi, kv.hi[:, :inner], kv.hi[:, inner:], nk2, nv2, wth2, meta['mask_u8'], lo=False)
         y = K.gemm_nt_f16x2(o.f16, W['out_16']) if o16 else K.gemm_nt(o, W['out'], out_bf16=_fast())
-        return y, (K.hi_only(h), K.hi_only(q), K.hi_only(kv), stats, K.hi_only(o))
+        return y, (K.hi_only(h), K.hi_only(ctx) if has_ctx else None, K.hi_only(q), K.hi_only(kv), stats, K.hi_only(o))
 
     @staticmethod
     def bwd(saved, dy, p, meta, need_dbias=False, dy_f32=None):
-        h, q, kv, stats, o = saved
+        h, ctx, q, kv, stats, o = saved
         W = XInner.weights(meta['cache'], p)
         nk, nv, wth, wq, wkv, wo = p
         g = meta['cgeom']
@@ -485,9 +489,11 @@ class CInner:
         dh = K.gemm_nt(dq, W['qT'], out_bf16=_fast_bwd())
         dwq, dwkv = torch.empty_like(wq), torch.empty_like(wkv)
         K.gemm_tn(dq, h, dwq)
-        K.gemm_tn(dkv, h, dwkv)
-        dh = _as_f32(dh) + K.gemm_nt(dkv, W['kvT'])          # the key / value rows ARE the query rows: one gradient for h
-        return dh, None, [dnk.reshape(nk.shape), dnv.reshape(nv.shape), dwth.reshape(wth.shape), dwq, dwkv, dwo]
+        K.gemm_tn(dkv, h if ctx is None else ctx, dwkv)
+        dctx = K.gemm_nt(dkv, W['kvT'])
+        if ctx is None:
+            dh, dctx = _as_f32(dh) + dctx, None             # the key / value rows ARE the query rows: one gradient for h
+        return dh, dctx, [dnk.reshape(nk.shape), dnv.reshape(nv.shape), dwth.reshape(wth.shape), dwq, dwkv, dwo]
 
 
 def _ff_keep_mask(R, C, p, device):
@@ -814,6 +820,18 @@ def _block_bwd16(kind, R, D, p, meta):
     return False
 
 
+def _takes_ctx(meta):
+    """does the inner stage project keys / values from a context tensor (and so want its BF copy in meta['ctx_bf'])?"""
+    return (meta['kind'] in ('xattn', 'xc2') and not meta.get('self_kv')) or (meta['kind'] == 'cattn' and bool(meta.get('has_ctx')))
+
+
+def _ctx_rows(meta):
+    """rows per sample of the context an inner stage read"""
+    if meta['kind'] == 'xc2':
+        return meta['ctx_T']
+    return K.cattn_keys(meta['cgeom']) if meta['kind'] == 'cattn' else meta['xgeom'].T
+
+
 _CTX_CAST = [None, -1, None]      # (weak reference to the context tensor, its version, its BF copy)
 
 
@@ -857,7 +875,7 @@ class SandwichBlockFn(Function):
         x2 = x.detach().contiguous().reshape(B * n, D)
         r2_ = x2 if resid is None else resid.detach().contiguous().reshape(B * n, D)
         meta = dict(meta)
-        if meta['kind'] in ('xattn', 'xc2') and not meta.get('self_kv'):
+        if _takes_ctx(meta):
             meta['ctx_bf'] = _ctx_to_bf(context)
         # the token shift is folded into the pre-LN's STORE: h = shift(LN(x)) is what the forward GEMM and the weight-gradient
         # GEMM consume (plain loaders); only the pre-LN backward still reads its incoming gradient through the inverse shift
@@ -955,8 +973,7 @@ class SandwichBlockFn(Function):
         ctx.prev_ctx = None
         dcontext = None
         if ctx.has_ctx:
-            T = meta['ctx_T'] if meta['kind'] == 'xc2' else meta['xgeom'].T
-            dcontext = dctx.reshape(B, T, D)
+            dcontext = dctx.reshape(B, _ctx_rows(meta), D)
         ctx.inner_saved = None
         dresid = g if ctx.has_resid else None
         return (dx.reshape(B, n, D), dresid, dcontext, None, dpre_w, dpre_b, dpost_w, dpost_b, *grads)
@@ -974,7 +991,7 @@ class InnerFn(Function):
         B, n, D = x.shape
         x2 = x.detach().contiguous().reshape(B * n, D)
         meta = dict(meta)
-        if meta['kind'] in ('xattn', 'xc2') and not meta.get('self_kv'):
+        if _takes_ctx(meta):
             meta['ctx_bf'] = _ctx_to_bf(context)
         h = K.empty_bf((B * n, D), x.device)
         K.cast_pad(x2, h)
@@ -996,7 +1013,7 @@ class InnerFn(Function):
         K.cast_pad(g2, dy)
         meta = dict(meta)
         dh, dctx, grads = inner.bwd(ctx.inner_saved, dy, p, meta, need_dbias=True, dy_f32=g2)
-        dcontext = dctx.reshape(B, meta['ctx_T'] if meta['kind'] == 'xc2' else meta['xgeom'].T, -1) if ctx.has_ctx else None
+        dcontext = dctx.reshape(B, _ctx_rows(meta), -1) if ctx.has_ctx else None
         ctx.inner_saved = None
         return (_as_f32(dh).reshape(B, n, D), dcontext, None, *grads)
 

@@ -1,11 +1,15 @@
 #!/usr/bin/env python
-"""Plain causal self-attention: the linear-memory cattn kernels against the torch-op formulation, in one process.
+"""Plain attention on the linear-memory cattn kernels against the torch-op formulation, in one process.
 
-Times forward + backward of ONE `Attention(dim=512, heads=8, dim_head=64, causal=True)` through the module's kernel path and through
-`Attention._forward_torch` (the PyTorch-ROCm formulation the module ran before the cattn kernels existed), alternating, after warm-up,
-device-synchronised (one HIP-event pair per iteration), and prints the peak memory of each above the baseline.
+Times forward + backward of ONE `Attention(dim=512, heads=8, dim_head=64)` through the module's kernel path and through
+`Attention._forward_torch` (the PyTorch-ROCm formulation the module ran before the cattn kernels took the shape), alternating, after
+warm-up, device-synchronised (one HIP-event pair per iteration), and prints the peak memory of each above the baseline.  Causal
+self-attention by default; --no-causal: non-causal self-attention over the n rows; --keys T (implies --no-causal): n queries over a
+context of T rows, with its gradient.  --layers L times a whole non-causal `Transformer(dim=512, depth=L)` over n tokens instead (the
+sketch encoder's stack), its long-key blocks as fused cattn nodes against the same stack on torch ops.
 
-    python tools/cattn_probe.py [--batch 8] [--n 2561] [--iters 20] [--warmup 3] [--mode bf16x3-fwd] [--kernels-only] [--json PATH]
+    python tools/cattn_probe.py [--batch 8] [--n 2561] [--keys T] [--no-causal] [--layers L] [--iters 20] [--warmup 3]
+                                [--mode bf16x3-fwd] [--kernels-only] [--json PATH]
 
 --kernels-only runs just the kernel path (e.g. under `rocprofv3 --kernel-trace --stats`).  The MFMA roof fraction quoted is the algorithmic
 FLOP count of the visible (query, key) pairs (kernels._c_work: 2 products forward, 5 backward) over 2.5 PFLOP/s dense bf16 / fp16."""
@@ -28,6 +32,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--n', type=int, default=2561)
+    ap.add_argument('--keys', type=int, default=None, help='rows of a context the n queries attend (non-causal)')
+    ap.add_argument('--no-causal', action='store_true')
+    ap.add_argument('--layers', type=int, default=0, help='time a non-causal Transformer of this depth instead of one module')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--mode', default='bf16x3-fwd')
@@ -37,18 +44,42 @@ def main():
     dev = 'cuda'
     torch.manual_seed(0)
     A.set_precision(args.mode)
-    m = A.Attention(dim=512, heads=8, dim_head=64, causal=True).to(dev)
+    causal = not (args.no_causal or args.keys is not None or args.layers)
     x = torch.randn(args.batch, args.n, 512, device=dev, requires_grad=True)
     dy = torch.randn(args.batch, args.n, 512, device=dev)
-    assert m._causal_hip_ok(args.n), 'the module would not take the kernel path in this mode'
+    ctx = torch.randn(args.batch, args.keys, 512, device=dev, requires_grad=True) if args.keys is not None else None
+    T = args.keys if args.keys is not None else args.n
+    from nuwa_pytorch_amd.nuwa_pytorch import Attention
+    shipped = (Attention.long_pairs_min, Attention.long_wgs_min)
+    Attention.long_pairs_min = Attention.long_wgs_min = 0        # the probe times the kernels at any shape; the shipped gate's verdict is printed
+    if args.layers:
+        assert ctx is None, '--layers times a self-attention stack'
+        m = A.Transformer(dim=512, depth=args.layers, heads=8, dim_head=64).to(dev)
+        routed = Attention._long_hip_ok
+
+        def torch_stack(t):
+            Attention._long_hip_ok = lambda self, *a, **k: False
+            try:
+                return m(t)
+            finally:
+                Attention._long_hip_ok = routed
+        kernel_fn, torch_fn = m, torch_stack
+        assert m.layers[0][0].fn._long_hip_ok(T), 'the stack would not take the kernel path at this length / in this mode'
+    else:
+        m = A.Attention(dim=512, heads=8, dim_head=64, causal=causal).to(dev)
+        assert m._causal_hip_ok(args.n) if causal else m._long_hip_ok(T), 'the module would not take the kernel path at this shape / in this mode'
+        kw = {} if ctx is None else dict(context=ctx)
+        kernel_fn, torch_fn = (lambda t: m(t, **kw)), (lambda t: m._forward_torch(t, **kw))
 
     def step(fn):
         m.zero_grad(set_to_none=True)
         x.grad = None
+        if ctx is not None:
+            ctx.grad = None
         y = fn(x)
         y.backward(dy)
 
-    paths = [('cattn', m)] + ([] if args.kernels_only else [('torch', m._forward_torch)])
+    paths = [('cattn', kernel_fn)] + ([] if args.kernels_only else [('torch', torch_fn)])
     times, peaks = {k: [] for k, _ in paths}, {}
     for name, fn in paths:                                   # warm-up + peak memory, one path at a time
         for _ in range(args.warmup):
@@ -67,9 +98,12 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             times[name].append(e0.elapsed_time(e1))
-    g = K.cattn_geom(args.batch, args.n, 8, 64, causal=True)
-    flops = K._c_work('fwd')((g,), {}, None)[0] + K._c_work('bwd')((g,), {}, None)[0]
-    res = dict(batch=args.batch, n=args.n, mode=args.mode, iters=args.iters, core_flops=flops)
+    g = K.cattn_geom(args.batch, args.n, 8, 64, causal=causal, n_keys=args.keys)
+    flops = (K._c_work('fwd')((g,), {}, None)[0] + K._c_work('bwd')((g,), {}, None)[0]) * max(args.layers, 1)
+    if not causal:
+        takes = args.batch * args.n * T >= shipped[0] and args.batch * min(-(-args.n // 64), -(-T // 64)) >= shipped[1]
+        print(f'the shipped gate (pairs >= {shipped[0]}, workgroups per side >= {shipped[1]}) routes this shape to: ' + ('the kernels' if takes else 'torch ops'))
+    res = dict(batch=args.batch, n=args.n, keys=T, causal=causal, layers=args.layers, mode=args.mode, iters=args.iters, core_flops=flops)
     for name, _ in paths:
         t = times[name]
         res[name] = dict(ms_median=statistics.median(t), ms_min=min(t), ms_max=max(t), peak_bytes=peaks[name])
@@ -78,9 +112,9 @@ def main():
     if 'torch' in res:
         res['ratio'] = res['torch']['ms_median'] / res['cattn']['ms_median']
         print(f"torch / cattn = {res['ratio']:.2f} x")
-    # the module time includes the three projections and their gradients; the per-kernel split comes from a profiler run (--kernels-only)
+    # the module time includes the three projections and their gradients (a stack's: the feed-forward blocks and the norms too); the per-kernel split comes from a profiler run (--kernels-only)
     res['roof_fraction_whole_module'] = flops / (res['cattn']['ms_median'] * 1e-3) / MFMA_ROOF
-    print(f"core FLOPs (visible pairs) {flops / 1e9:.1f} G  ->  {res['roof_fraction_whole_module'] * 100:.2f} % of the MFMA roof over the WHOLE module time")
+    print(f"core FLOPs (visible pairs) {flops / 1e9:.1f} G  ->  {res['roof_fraction_whole_module'] * 100:.2f} % of the MFMA roof over the WHOLE time")
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
         with open(args.json, 'w') as f:
