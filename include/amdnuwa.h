@@ -35,7 +35,8 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 *     o_lo_f16 on the two fp16 forward cores; 16: the fp16-gradient backward; 17: amdnuwa_gemm_desc.a_chunk32, amdnuwa_gemm_tn_chunked_a_supported,
                                                 *     amdnuwa_xattn2_bwd_ex, AMDNUWA_LN_RESID_MINUS, tuning key 25; 18: the amdnuwa_xattn6_* family; 19: amdnuwa_sparse3dna_bwd_f16, amdnuwa_xattn6_bwd_f16, amdnuwa_xattn6_pack_bwd_f16, o == NULL in the two fp16 forward cores,
                                                 *     ab_f16 on the whole-M TN kernel with alpha_dev in its direct epilogue, c_f16 on the two-MFMA NT product;
-                                                * 20: the amdnuwa_cattn_* family, 21: amdnuwa_cattn_geom.n_keys) */
+                                                * 20: the amdnuwa_cattn_* family, 21: amdnuwa_cattn_geom.n_keys; ABI 21 also accepts token grids of up to 64 columns in the
+                                                *     window kernels -- amdnuwa_s3_geom / amdnuwa_s3_supported below: a wider accepted range, no signature or struct change) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -302,7 +303,7 @@ typedef struct {
     int F, H, W;            /* token grid (max_frames, fmap, fmap) */
     int kf, kh, kw;         /* kernel size */
     int df, dh, dw;         /* dilation */
-    int heads, dim_head;    /* heads <= 8; dim_head in {32, 64}; W*heads*4 <= 512 */
+    int heads, dim_head;    /* heads 1..8; dim_head in {32, 64}; W*heads*4 <= 512 (one workgroup per grid row) or W <= 64 (column tiles) */
     float scale;            /* dim_head ** -0.5 */
     /* relative-position bias (Sparse3DNA(rel_pos_bias=True), np.py:512-516, 542): rel_bias[j][head] is added to the score of
      * key slot j (j = 0 is <bos>: pass 0 there), fp32 [kf*kh*kw + 1][heads] or NULL.  The backward writes its gradient
@@ -317,10 +318,12 @@ typedef struct {
 } amdnuwa_s3_geom;
 
 /* 1 when the window kernels (amdnuwa_sparse3dna_*, amdnuwa_cross2dna_*) take this geometry in the given operand form
- * (lo_operands != 0: bf16 hi + lo pairs): head size 32 / 64, <= 8 heads, W * heads * 4 <= 512, and the window's LDS tables
- * (they grow with J = kf*kh*kw + 1 key slots: Sparse3DNA / SparseCross2DNA kernel sizes, reference nuwa_pytorch.py:382-394,
- * 761-790) within the CU's 160 KiB for the forward AND both backward kernels.  The entry points themselves return
- * AMDNUWA_ERR_UNSUPPORTED for a geometry this query rejects. */
+ * (lo_operands != 0: bf16 hi + lo pairs): head size 32 / 64, 1..8 heads, W * heads * 4 <= 512 or W <= 64, and the window's LDS tables (they grow with
+ * J = kf*kh*kw + 1 key slots: Sparse3DNA / SparseCross2DNA kernel sizes, reference nuwa_pytorch.py:382-394, 761-790) within the
+ * CU's 160 KiB for the forward AND both backward kernels.  A row with W * heads * 4 <= 512 is one workgroup; a wider one is cut
+ * into NT = ceil(W / floor(128 / heads)) column tiles of TW = ceil(W / NT) queries, and the tables are those of ONE tile: TW
+ * queries, TW + (kw-1)*dw staged columns (the halo the kw taps reach, in the causal and the symmetric window alike).  The entry
+ * points themselves return AMDNUWA_ERR_UNSUPPORTED exactly for the geometries this query rejects. */
 int amdnuwa_s3_supported(const amdnuwa_s3_geom* g, int lo_operands);
 int amdnuwa_sparse3dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
                            const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,

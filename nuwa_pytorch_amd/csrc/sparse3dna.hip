@@ -10,6 +10,7 @@
 //
 // Thread map: t = ((w*NH + h)*4 + c): 4 lanes share one (query, head) and split the head dim in
 // chunks of DH/4 (a key/value row of one query position is read as one contiguous 2*NH*DH bytes).
+// A row with W*NH*4 > 512 does not fit one workgroup: it runs in column tiles (sparse3dna_wide.hip).
 //
 // Backward is split so that it needs no atomics and is bit-reproducible:
 //   bwd_q  (query-centric, per query row): recompute P, dP' = dO.V, dP = W^T dP', ds, dq; writes
@@ -20,129 +21,9 @@
 //
 // hi/lo: every bf16 input may come with a bf16 residual (value = hi + lo); arithmetic is fp32 FMA.
 #include "common.h"
-#include "../../include/amdnuwa.h"
+#include "s3_args.h"
 
 namespace {
-
-struct S3Args {
-    const bf16_t *q, *k, *v, *ql, *kl, *vl; int ld;       // q/k/v rows: [B*ntok, ld]
-    bf16_t *o, *ol; int ldo;                              // fwd out
-    int ol_f16;                                           // fp16 forward: ol receives the FP16 rendering of the output (the to_out GEMM's fp16 operand), not the bf16 residual
-    const bf16_t *dO, *dOl; int lddo;                     // bwd in
-    bf16_t *dq, *dk, *dv, *dql, *dkl, *dvl; int ldd;      // bwd out
-    const float* wth;                                     // [NH][NH] talking heads (g, h)
-    const float* bias;                                    // [J][NH] relative-position bias per key slot (or NULL)
-    float *ds, *pm;                                       // [B][nq][J][NH]
-    float* stats;                                         // recomputing key side (MFMA path): [B][nq][NH][4] = (row max, 1 / row sum, delta = sum_j P dP, -);
-                                                          // non-NULL = the query side writes these INSTEAD of the ds / pm workspace
-    float *part_th, *part_k0, *part_v0;                   // [B*F*H][NH*NH], [B*F*H][NH*DH] x2
-    float* dwth;                                          // [NH*NH] accumulated
-    int B, ntok, F, H, W, kf, kh, kw, df, dh, dw, NH;
-    int of, oh, ow;                                       // tap index of the query's own position per axis: k - 1 (causal) / (k - 1) / 2 (symmetric)
-    // key / value side.  Self-attention (Sparse3DNA): the query sequence itself, row 0 = <bos> = key slot 0.  xmode = 1 (SparseCross2DNA,
-    // np.py:761-901): keys / values are a context grid of FK = kf frames, tap a of the frame axis IS context frame a (absolute), slot 0
-    // is a learned null key / value, keys can be masked, and query row 0 (<bos>) is left to the host (it attends to everything).
-    int xmode, FK, kvrows, kvoff, ldk, lddk;              // rows per sample / first grid row / row strides of the k, v (dk, dv) tensors
-    const bf16_t *k0, *k0l, *v0, *v0l; long long k0_bs;   // slot-0 key / value rows [NH*DH] and their per-sample stride (elements)
-    const uint8_t* kmask;                                 // [B][kvrows] (1 = visible) or NULL
-    float *dnull_k, *dnull_v;                             // xmode: gradients of the null key / value [NH*DH] (fp32)
-    float scale;
-    int accumulate;
-    int dbg;                                              // probe only (tuning key 9): bit 0 / 1 / 2 skip phase 1 / 2 / 3 of the MFMA forward
-    int ymajor;                                           // MFMA kernels: workgroup order inside a sample is (y, f) instead of (f, y) (tuning key 3 bit 1 = old order)
-    int sep_passes;                                       // MFMA query-side backward: the three separate item passes instead of the fused one (tuning key 19 = 1)
-    int packed;                                           // MFMA backward (round 5): the ds / P' workspace is ONE array of (bf16 ds | bf16 P') words at `pm`
-    const float* gs2;                                     // fp16-gradient backward (round 6, amdnuwa_sparse3dna_bwd_f16): device {S, 1 / S}; q / k / v / dO hold fp16 values,
-                                                          // dO = fp16(S dO), dq / dk / dv leave as fp16(S gradient), the workspace words are (fp16 S ds | fp16 P'), dW_th leaves times 1 / S
-};
-// a 16-bit element of an operand array as fp32: bf16, or (F16) fp16
-template <bool F16> __device__ __forceinline__ float ld16_t(bf16_t v) { return F16 ? (float)__builtin_bit_cast(_Float16, v) : bf2f(v); }
-
-constexpr float NEG_MAX = -3.4028234663852886e38f;
-
-// Workgroups are handed to the 8 XCDs round-robin by linear id; every XCD has its own L2.  Consecutive query rows share
-// almost all of their key / value rows, so the logical row id is remapped to give each XCD one CONTIGUOUS range of rows
-// (whole samples): its L2 then holds the few frames in flight instead of an eighth of everything (bijective for any grid).
-__device__ __forceinline__ int xcd_row_id() {
-    const int nb = gridDim.x, id = blockIdx.x, per = nb >> 3, rem = nb & 7, x = id & 7, k = id >> 3;
-    return x * per + (x < rem ? x : rem) + k;
-}
-
-
-// hs = element stride between the 8-element halves of a chunk (8 = contiguous; the LDS stage keeps the two
-// 16-byte halves of every chunk in separate regions so that ds_read_b128 lanes are 16 bytes apart: no conflicts)
-template <int CH>
-__device__ __forceinline__ void load_chunk(const bf16_t* hi, const bf16_t* lo, float* f, int hs = 8) {
-#pragma unroll
-    for (int v8 = 0; v8 < CH / 8; ++v8) {
-        const uint4 u = *reinterpret_cast<const uint4*>(hi + v8 * hs);
-        f[v8 * 8 + 0] = lo_f(u.x); f[v8 * 8 + 1] = hi_f(u.x); f[v8 * 8 + 2] = lo_f(u.y); f[v8 * 8 + 3] = hi_f(u.y);
-        f[v8 * 8 + 4] = lo_f(u.z); f[v8 * 8 + 5] = hi_f(u.z); f[v8 * 8 + 6] = lo_f(u.w); f[v8 * 8 + 7] = hi_f(u.w);
-        if (lo) {
-            const uint4 l = *reinterpret_cast<const uint4*>(lo + v8 * hs);
-            f[v8 * 8 + 0] += lo_f(l.x); f[v8 * 8 + 1] += hi_f(l.x); f[v8 * 8 + 2] += lo_f(l.y); f[v8 * 8 + 3] += hi_f(l.y);
-            f[v8 * 8 + 4] += lo_f(l.z); f[v8 * 8 + 5] += hi_f(l.z); f[v8 * 8 + 6] += lo_f(l.w); f[v8 * 8 + 7] += hi_f(l.w);
-        }
-    }
-}
-template <int CH>
-__device__ __forceinline__ void store_chunk(bf16_t* hi, bf16_t* lo, const float* f) {
-#pragma unroll
-    for (int v8 = 0; v8 < CH / 8; ++v8) {
-        bf16_t h[8], l[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f2bf_hilo(f[v8 * 8 + e], h[e], l[e]);
-        *reinterpret_cast<uint4*>(hi + v8 * 8) = make_uint4(pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7]));
-        if (lo) *reinterpret_cast<uint4*>(lo + v8 * 8) = make_uint4(pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7]));
-    }
-}
-// reductions over the 4 lanes of a (query, head) group with DPP quad permutes (no LDS traffic)
-__device__ __forceinline__ float dpp_quad(float v, int ctrl_b1) {
-    const int i = __builtin_bit_cast(int, v);
-    const int r = ctrl_b1 ? __builtin_amdgcn_mov_dpp(i, 0xB1, 0xF, 0xF, true)     // quad_perm [1,0,3,2]
-                          : __builtin_amdgcn_mov_dpp(i, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    return __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float quad_sum(float v) {
-    v += dpp_quad(v, 1);
-    v += dpp_quad(v, 0);
-    return v;
-}
-__device__ __forceinline__ float quad_max(float v) {
-    v = fmaxf(v, dpp_quad(v, 1));
-    v = fmaxf(v, dpp_quad(v, 0));
-    return v;
-}
-
-// packed bf16 arithmetic (bf16 operand mode): v_dot2_f32_bf16 multiplies two bf16 pairs and accumulates in fp32
-template <int CH>
-__device__ __forceinline__ void load_pk(const bf16_t* p, uint32_t* pk, int hs = 8) {
-#pragma unroll
-    for (int v8 = 0; v8 < CH / 8; ++v8) {
-        const uint4 u = *reinterpret_cast<const uint4*>(p + v8 * hs);
-        pk[v8 * 4 + 0] = u.x; pk[v8 * 4 + 1] = u.y; pk[v8 * 4 + 2] = u.z; pk[v8 * 4 + 3] = u.w;
-    }
-}
-__device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a), __builtin_bit_cast(bf16x2, b), c, false);
-}
-template <int CH>
-__device__ __forceinline__ float dot_pk(const uint32_t* a, const uint32_t* b) {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int i = 0; i < CH / 2; i += 2) { s0 = dot2(a[i], b[i], s0); s1 = dot2(a[i + 1], b[i + 1], s1); }
-    return s0 + s1;
-}
-// acc[e] += coef * v[e] with coef rounded to bf16: one dot2 per element, no unpacking
-template <int CH>
-__device__ __forceinline__ void axpy_pk(float* acc, float coef, const uint32_t* v) {
-    const uint32_t clo = f2bf(coef), chi = clo << 16;
-#pragma unroll
-    for (int i = 0; i < CH / 2; ++i) {
-        acc[2 * i] = dot2(v[i], clo, acc[2 * i]);
-        acc[2 * i + 1] = dot2(v[i], chi, acc[2 * i + 1]);
-    }
-}
 
 // Sweep over all causal taps of one query row.  One key/value grid row (all heads) is staged in LDS per
 // round; the NEXT valid row is fetched into registers while the current one is consumed.  The tap planes
@@ -676,7 +557,7 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_kv_kernel(S3Args a) {
 // grid = B * ceil(inner/64) blocks for the <bos> k/v rows + ceil(NH*NH/16) blocks for dW_th.
 __global__ __launch_bounds__(1024) void s3_bwd_fin_kernel(S3Args a, int DH) {
     __shared__ float red[2][16][64];
-    const int rows = a.F * a.H, inner = a.NH * DH;
+    const int rows = a.F * a.H * a.NT, inner = a.NH * DH;     // partials per sample: one per (query row, column tile), NT = 1 on rows of one tile
     const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
     const int nchunk = (inner + 63) / 64;
     if ((int)blockIdx.x >= a.B * nchunk) {
@@ -776,27 +657,33 @@ __global__ __launch_bounds__(1024) void s3_bwd_fin_kernel(S3Args a, int DH) {
 int check_geom(const amdnuwa_s3_geom* g) {
     if (!g) return AMDNUWA_ERR_ARG;
     if (g->dim_head != 32 && g->dim_head != 64) return AMDNUWA_ERR_UNSUPPORTED;
-    if (g->heads < 1 || g->heads > 8 || g->W < 1 || g->W * g->heads * 4 > 512) return AMDNUWA_ERR_UNSUPPORTED;
+    // a row of W * heads * 4 <= 512 threads is one workgroup; wider rows run in column tiles (sparse3dna_wide.hip), up to 64 columns
+    if (g->heads < 1 || g->heads > 8 || g->W < 1 || (g->W * g->heads * 4 > 512 && g->W > 64)) return AMDNUWA_ERR_UNSUPPORTED;
     if (g->kf < 1 || g->kh < 1 || g->kw < 1 || g->df < 1 || g->dh < 1 || g->dw < 1) return AMDNUWA_ERR_ARG;
     if (g->ntok < 1 || g->ntok - 1 > g->F * g->H * g->W) return AMDNUWA_ERR_ARG;
     return AMDNUWA_OK;
 }
-// Dynamic LDS of the window kernels grows with the window: J = kf*kh*kw + 1 key slots per query.  The largest request over the
+// Dynamic LDS of the window kernels grows with the window: J = kf*kh*kw + 1 key slots per query, and is that of the column tile
+// actually launched (s3_tile: tw queries, sw = tw + halo staged columns; tw = sw = W on a row of one tile).  The largest request over the
 // forward, the query-side and the key-side backward in the given operand form (lo = hi + lo pairs); the MFMA band kernels of
 // the causal decoder shapes need less.  A launch above the CU's 160 KiB would fail inside hipLaunchKernel -- typically in the
 // backward, after the forward succeeded -- so the entry points refuse the geometry up front (AMDNUWA_ERR_UNSUPPORTED) and
 // amdnuwa_s3_supported() lets the host route such windows to its PyTorch-op formulation.
 constexpr size_t S3_LDS_MAX = 160 * 1024 - 2048;        // leaves room for the kernels' static __shared__ arrays
-size_t s3_lds_need(const amdnuwa_s3_geom* g, bool lo) {
-    const size_t J = (size_t)g->kf * g->kh * g->kw + 1, inner = (size_t)g->heads * g->dim_head, W = (size_t)g->W;
-    const size_t stage = W * inner * (lo ? 4 : 2), nsp = W * J * g->heads;
-    const size_t fwd = stage + nsp * 4;
+struct S3Lds { size_t fwd, bq, bkv; };                  // dynamic LDS bytes of the forward, the query-side and the key-side backward
+S3Lds s3_lds(const amdnuwa_s3_geom* g, bool lo) {
+    const S3Tile tl = s3_tile(g);
+    const size_t J = (size_t)g->kf * g->kh * g->kw + 1, inner = (size_t)g->heads * g->dim_head, tw = (size_t)tl.tw, sw = (size_t)tl.sw;
+    const size_t stage = sw * inner * (lo ? 4 : 2), nsp = tw * J * g->heads;
+    // bwd_q: stage (hi + lo) + SP + DP + RED(8*64); the <bos> partial reduction reuses SP + DP: needs tw*inner <= 2*nsp floats
     size_t spdp = 2 * nsp;
-    if (spdp < W * inner) spdp = W * inner;
-    const size_t bq = stage + (spdp + 8 * 64) * 4;
-    const size_t bkv = W * inner * 8;
-    size_t m = fwd > bq ? fwd : bq;
-    return m > bkv ? m : bkv;
+    if (spdp < tw * inner) spdp = tw * inner;
+    return {stage + nsp * 4, stage + (spdp + 8 * 64) * 4, sw * inner * 8};
+}
+size_t s3_lds_need(const amdnuwa_s3_geom* g, bool lo) {
+    const S3Lds l = s3_lds(g, lo);
+    const size_t m = l.fwd > l.bq ? l.fwd : l.bq;
+    return m > l.bkv ? m : l.bkv;
 }
 // ---------------------------------------------------------------------------------------------
 // MFMA forward (fast bf16 mode, W == 16, 8 heads x 64): one workgroup = one query row of the grid, wave h = head h.
@@ -2855,6 +2742,8 @@ void fill_geom(S3Args& a, const amdnuwa_s3_geom* g) {
     a.oh = g->noncausal ? (g->kh - 1) / 2 : g->kh - 1;
     a.ow = g->noncausal ? (g->kw - 1) / 2 : g->kw - 1;
     a.xmode = 0; a.FK = g->F; a.kvrows = g->ntok; a.kvoff = 1; a.kmask = nullptr;
+    const S3Tile tl = s3_tile(g);
+    a.NT = tl.nt; a.TW = tl.tw; a.SW = tl.sw;
 }
 // self-attention: keys / values are the query sequence, slot 0 = its <bos> row
 void self_kv(S3Args& a) {
@@ -2908,8 +2797,9 @@ extern "C" int amdnuwa_sparse3dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* 
     if ((k_lo != nullptr) && (!q_lo || !v_lo)) return AMDNUWA_ERR_ARG;
     // tuning key 3: 0 = one key row per staging round (measured faster: 4 resident workgroups per CU),
     //               1 = stage the kh rows of a tap frame at once (needs kh <= KHMAX)
-    const bool slab = false;   // (slab staging of a whole tap frame measured slower than row staging: retired)
-    const size_t lds = (size_t)g->W * g->heads * g->dim_head * (k_lo ? 4 : 2) * (slab ? g->kh : 1) + (size_t)g->W * J * g->heads * 4;
+    // (slab staging of a whole tap frame measured slower than row staging: retired)
+    const size_t lds = s3_lds(g, k_lo != nullptr).fwd;
+    if (a.NT > 1) return s3w_fwd_launch(a, g->dim_head, k_lo != nullptr, lds, stream);      // column tiles of a wide row
     dim3 grid(g->B * g->F * g->H), block(block_threads(g));
 #define S3F(DH_, LO_)                                                                                             \
     do {                                                                                                          \
@@ -2975,7 +2865,8 @@ extern "C" int amdnuwa_s3_supported(const amdnuwa_s3_geom* g, int lo_operands) {
 
 extern "C" size_t amdnuwa_sparse3dna_bwd_workspace_bytes(const amdnuwa_s3_geom* g) {
     if (check_geom(g)) return 0;
-    const size_t J = (size_t)g->kf * g->kh * g->kw + 1, nq = g->ntok - 1, rows = (size_t)g->B * g->F * g->H;
+    // ds + P' [B][nq][J][heads], then the per-workgroup partials (dW_th, <bos> / null dk and dv): one per (query row, column tile)
+    const size_t J = (size_t)g->kf * g->kh * g->kw + 1, nq = g->ntok - 1, rows = (size_t)g->B * g->F * g->H * s3_tile(g).nt;
     const size_t inner = (size_t)g->heads * g->dim_head;
     return (2 * (size_t)g->B * nq * J * g->heads + rows * g->heads * g->heads + 2 * rows * inner) * sizeof(float) + 256 +
            amdnuwa_colsum_workspace_bytes((long long)g->B * nq, (int)(J * g->heads));
@@ -3007,19 +2898,14 @@ extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* 
     float* ws = (float*)workspace;
     a.ds = ws; ws += (size_t)g->B * nq * J * g->heads;
     a.pm = ws; ws += (size_t)g->B * nq * J * g->heads;
-    a.part_th = ws; ws += rows * g->heads * g->heads;
-    a.part_k0 = ws; ws += rows * inner;
+    const size_t parts = rows * a.NT;                                              // workgroups of the query side: (query row, column tile)
+    a.part_th = ws; ws += parts * g->heads * g->heads;
+    a.part_k0 = ws; ws += parts * inner;
     a.part_v0 = ws;
-    const size_t nsp = (size_t)g->W * J * g->heads;
-    // bwd_q LDS: stage (hi+lo) + SP + DP + RED(8*64); the <bos> partial reduction reuses SP+DP: needs 2*W*inner <= 2*nsp
-    size_t spdp = 2 * nsp;
-    if (spdp < (size_t)g->W * inner) spdp = (size_t)g->W * inner;
     const bool has_lo = k_lo != nullptr;
     if (has_lo && (!q_lo || !v_lo)) return AMDNUWA_ERR_ARG;
-    // tuning key 4: 1 = slab staging in bwd_q too (more LDS -> one workgroup per CU), 0 = one row per round
-    const bool slab = false;
-    const size_t lds_q = (size_t)g->W * g->heads * g->dim_head * (has_lo ? 4 : 2) * (slab ? g->kh : 1) + (spdp + 8 * 64) * 4;
-    const size_t lds_kv = (size_t)g->W * g->heads * g->dim_head * 8;
+    const S3Lds l = s3_lds(g, has_lo);
+    const size_t lds_q = l.bq, lds_kv = l.bkv;
     dim3 grid((unsigned)rows), block(block_threads(g));
     // MFMA query-side kernel (tuning key 4: 1 = keep the dot2 kernel): bf16 operands, 16 queries per grid row, 8 heads x 64
     const bool q_mfma = !has_lo && !dO_lo && !g->noncausal && g_amdnuwa_tuning[4] != 1 && g->W == 16 && g->heads == 8 && g->dim_head == 64 &&
@@ -3062,14 +2948,17 @@ extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* 
     } while (0)
     const bool lo_mode = has_lo || dO_lo != nullptr;
     if (lo_mode && (!has_lo || !dO_lo)) return AMDNUWA_ERR_ARG;     // parity mode needs lo parts for q/k/v AND dO
-    if (g->dim_head == 64) { if (lo_mode) S3B(64, true); else S3B(64, false); }
+    if (a.NT > 1) {                                                 // column tiles of a wide row
+        const int rcw = s3w_bwd_launch(a, g->dim_head, lo_mode, lds_q, lds_kv, stream);
+        if (rcw) return rcw;
+    } else if (g->dim_head == 64) { if (lo_mode) S3B(64, true); else S3B(64, false); }
     else { if (lo_mode) S3B(32, true); else S3B(32, false); }
 #undef S3B
     LAUNCH_CHECK();
     hipLaunchKernelGGL(s3_bwd_fin_kernel, dim3(g->B * (((int)inner + 63) / 64) + (g->heads * g->heads + 15) / 16), dim3(1024), 0, stream, a, g->dim_head);
     LAUNCH_CHECK();
     if (g->d_rel_bias) {         // d(bias)[j][h] = sum over every (sample, query) of ds[.][j][h]: fixed-order column sums of the ds workspace
-        float* cws = a.part_v0 + rows * inner;
+        float* cws = a.part_v0 + parts * inner;
         const int rc2 = amdnuwa_colsum(a.ds, g->d_rel_bias, (long long)g->B * nq, (int)(J * g->heads), 0, cws,
                                        amdnuwa_colsum_workspace_bytes((long long)g->B * nq, (int)(J * g->heads)), stream);
         if (rc2) return rc2;
@@ -3164,9 +3053,9 @@ extern "C" int amdnuwa_cross2dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q
     if (!q || !w_th || !o || ldq % 8 || ldo % 8 || (k_lo != nullptr) != (q_lo != nullptr)) return AMDNUWA_ERR_ARG;
     if (g->B <= 0) return AMDNUWA_OK;
     a.q = q; a.ql = q_lo; a.ld = ldq; a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th;
-    const int J = g->kf * g->kh * g->kw + 1;
     const bool lo_mode = k_lo != nullptr;
-    const size_t lds = (size_t)g->W * g->heads * g->dim_head * (lo_mode ? 4 : 2) + (size_t)g->W * J * g->heads * 4;
+    const size_t lds = s3_lds(g, lo_mode).fwd;
+    if (a.NT > 1) return s3w_fwd_launch(a, g->dim_head, lo_mode, lds, stream);
     dim3 grid(g->B * g->F * g->H), block(block_threads(g));
 #define S3F(DH_, LO_)                                                                                             \
     do {                                                                                                          \
@@ -3207,14 +3096,12 @@ extern "C" int amdnuwa_cross2dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q
     float* ws = (float*)workspace;
     a.ds = ws; ws += (size_t)g->B * nq * J * g->heads;
     a.pm = ws; ws += (size_t)g->B * nq * J * g->heads;
-    a.part_th = ws; ws += rows * g->heads * g->heads;
-    a.part_k0 = ws; ws += rows * inner;
+    const size_t parts = rows * a.NT;
+    a.part_th = ws; ws += parts * g->heads * g->heads;
+    a.part_k0 = ws; ws += parts * inner;
     a.part_v0 = ws;
-    const size_t nsp = (size_t)g->W * J * g->heads;
-    size_t spdp = 2 * nsp;
-    if (spdp < (size_t)g->W * inner) spdp = (size_t)g->W * inner;
-    const size_t lds_q = (size_t)g->W * g->heads * g->dim_head * (lo_mode ? 4 : 2) + (spdp + 8 * 64) * 4;
-    const size_t lds_kv = (size_t)g->W * g->heads * g->dim_head * 8;
+    const S3Lds l = s3_lds(g, lo_mode);
+    const size_t lds_q = l.bq, lds_kv = l.bkv;
     dim3 grid_q((unsigned)rows), grid_kv((unsigned)(g->B * g->kf * g->H)), block(block_threads(g));
 #define S3XB(DH_, LO_)                                                                                            \
     do {                                                                                                          \
@@ -3224,7 +3111,10 @@ extern "C" int amdnuwa_cross2dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q
         (void)hipFuncSetAttribute((const void*)s3_bwd_kv_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv); \
         hipLaunchKernelGGL((s3_bwd_kv_kernel<DH_, LO_>), grid_kv, block, lds_kv, stream, a);                      \
     } while (0)
-    if (g->dim_head == 64) { if (lo_mode) S3XB(64, true); else S3XB(64, false); }
+    if (a.NT > 1) {
+        const int rcw = s3w_bwd_launch(a, g->dim_head, lo_mode, lds_q, lds_kv, stream);
+        if (rcw) return rcw;
+    } else if (g->dim_head == 64) { if (lo_mode) S3XB(64, true); else S3XB(64, false); }
     else { if (lo_mode) S3XB(32, true); else S3XB(32, false); }
 #undef S3XB
     LAUNCH_CHECK();

@@ -527,8 +527,9 @@ class Sparse3DNA(nn.Module):
         return dict(kind='s3', cache=self._cache, geom=g)
 
     def _hip_ok(self):
-        """geometry the 3DNA kernels take.  The causal decoder path never falls back (an unsupported shape raises from the library);
-        the symmetric variant keeps its PyTorch-op formulation for head sizes / widths outside the kernels"""
+        """geometry the 3DNA kernels take: head size 32 / 64, up to 8 heads, feature maps up to 64 wide (rows of more than 128 / heads
+        columns run in column tiles).  The causal decoder path never falls back (an unsupported shape raises from the library); the
+        symmetric variant keeps its PyTorch-op formulation for head sizes / widths / windows outside the kernels"""
         if self.causal:
             return True
         if self.training and self.dropout.p > 0:
