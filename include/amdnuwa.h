@@ -36,7 +36,8 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 *     amdnuwa_xattn2_bwd_ex, AMDNUWA_LN_RESID_MINUS, tuning key 25; 18: the amdnuwa_xattn6_* family; 19: amdnuwa_sparse3dna_bwd_f16, amdnuwa_xattn6_bwd_f16, amdnuwa_xattn6_pack_bwd_f16, o == NULL in the two fp16 forward cores,
                                                 *     ab_f16 on the whole-M TN kernel with alpha_dev in its direct epilogue, c_f16 on the two-MFMA NT product;
                                                 * 20: the amdnuwa_cattn_* family, 21: amdnuwa_cattn_geom.n_keys; ABI 21 also accepts token grids of up to 64 columns in the
-                                                *     window kernels -- amdnuwa_s3_geom / amdnuwa_s3_supported below: a wider accepted range, no signature or struct change) */
+                                                *     window kernels -- amdnuwa_s3_geom / amdnuwa_s3_supported below: a wider accepted range, no signature or struct change;
+                                                *     amdnuwa_attn_decode_rows and its _workspace_bytes were added at 21 as well: purely additive) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -578,6 +579,23 @@ int amdnuwa_cattn_bwd(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, c
 int amdnuwa_xattn_decode(const amdnuwa_xattn_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq,
                          const amdnuwa_xattn_kv* packed, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo,
                          amdnuwa_stream stream);
+/* Single-query attention over ANY number of cached rows: Attention.forward with context (np.py:339-378) and one chunk of
+ * CrossModalityCrossAttention (np.py:908-1067) for ONE query row per sample (added at ABI 21, purely additive).  Slot 0 is the learned null
+ * key (null_k / null_v [heads][dim_head] fp32, always visible); slot 1 + t is row first_row[0] + t of the cache kv [B][cache_rows][2 * inner]
+ * (k | v, bf16 hi with an optional lo image: the layout amdnuwa_s3_decode keeps), t < T.  first_row lives in DEVICE memory so that a captured
+ * launch can be replayed for another window; a window that leaves [0, cache_rows) writes nothing.  key_mask [B][T] (0 = hidden) or NULL.
+ * Scores q . k * scale, fp32 softmax over the T + 1 slots, P'[g][j] = sum_h w_th[g][h] P[h][j] + th_bias[g] (th_bias [heads] or NULL: the
+ * bias of the reference's Conv3d talking heads reaches every slot, null and masked ones included), o[g] = sum_j P'[g][j] v_j[g].
+ * q [B, ldq] unscaled and o [B, ldo] are bf16 hi (+ lo) rows.  heads 1..8, dim_head 32 / 64, any T >= 1; otherwise AMDNUWA_ERR_UNSUPPORTED.
+ * The T + 1 slots are cut into splits of 128, one workgroup per (split, sample); the split count depends on T alone, partial results meet
+ * in index order and there are no atomics: two runs are bit-identical.  workspace: >= _workspace_bytes =
+ * 4 * B * (heads * (T + 1) + ceil((T + 1) / 128) * (2 * heads + heads * dim_head)) bytes (scores, per-split statistics, per-split partial
+ * rows), AMDNUWA_ERR_WORKSPACE otherwise. */
+size_t amdnuwa_attn_decode_rows_workspace_bytes(int B, int T, int heads, int dim_head);
+int amdnuwa_attn_decode_rows(int B, int T, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo, int ldq,
+                             const uint16_t* kv, const uint16_t* kv_lo, int cache_rows, const int* first_row, const uint8_t* key_mask,
+                             const float* null_k, const float* null_v, const float* w_th, const float* th_bias, uint16_t* o,
+                             uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
 
 /* ---- frozen VQGanVAE tokenizer (VQGanVAE.get_video_indices -> encode, reference vqgan_vae.py:431-435, 452-458), exact fp32 ---- */
 typedef struct {

@@ -398,7 +398,212 @@ __global__ __launch_bounds__(1024) void xattn_decode_kernel(XDecArgs a) {
     }
 }
 
+// ---- single-query attention over ANY number of cached rows (Attention / CrossModalityCrossAttention, np.py:339-378, 908-1067) ----
+// The keys of a sample are cut into splits of ROWS_SPLIT slots (slot 0 = the learned null key, slot 1 + t = cache row first + t), one
+// workgroup per (split, sample).  The talking-heads mix sits between the softmax and P.V, so a split cannot finish on its own maximum:
+//   rows_stats_kernel  : scores of the split (kept in the workspace, [B][J][NH] fp32) and its per-head (max, sum of exponentials)
+//   rows_apply_kernel  : merges the statistics of all splits IN INDEX ORDER, P = exp(s - M) / Z, P' = W P + bias, partial o of the split
+//   rows_reduce_kernel : sums the partial rows in index order and rounds the output
+// No atomics, the split count depends on T alone: two runs are bit-identical.  The first row comes from device memory (graph replay).
+constexpr int ROWS_SPLIT = 128;
+constexpr float ROWS_NEG = -3.4028234663852886e38f;
+
+struct RowsArgs {
+    const bf16_t *q, *ql;            // [B, ldq] unscaled
+    const bf16_t *kv, *kvl;          // [B, cache_rows, 2*inner]: k | v
+    const int* first;                // device: cache row of slot 1
+    const uint8_t* mask;             // [B, T] or NULL
+    const float *nk, *nv, *wth, *bias;
+    bf16_t *o, *ol;                  // [B, ldo]
+    float *sc, *st, *part;           // workspace: scores [B][J][NH] | stats [B][nsplit][NH][2] | partial rows [B][nsplit][inner]
+    int ldq, ldo, cache_rows, T, heads, dim_head, nsplit;
+    float scale;
+};
+
+__device__ __forceinline__ bool rows_window_ok(const RowsArgs& a, int first) {
+    return first >= 0 && (long long)first + a.T <= (long long)a.cache_rows;
+}
+
+template <int DHT>
+__global__ __launch_bounds__(256) void rows_stats_kernel(RowsArgs a) {
+    __shared__ float qs[8 * 65];
+    __shared__ float s[8 * ROWS_SPLIT];
+    __shared__ int ok[ROWS_SPLIT];
+    const int NH = a.heads, DH = a.dim_head, inner = NH * DH, QS = DH + 1, J = a.T + 1;
+    const int sp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, first = a.first[0];
+    if (!rows_window_ok(a, first)) return;
+    const int j0 = sp * ROWS_SPLIT, Jl = min(ROWS_SPLIT, J - j0);
+    for (int c = tid; c < inner; c += blockDim.x) qs[(c / DH) * QS + c % DH] = ld_hl(a.q, a.ql, (size_t)b * a.ldq + c) * a.scale;
+    for (int j = tid; j < Jl; j += blockDim.x) {
+        const int jg = j0 + j;
+        ok[j] = jg == 0 || !a.mask || a.mask[(size_t)b * a.T + jg - 1] != 0;
+    }
+    __syncthreads();
+    const size_t kvb = (size_t)b * a.cache_rows * 2 * inner;
+    for (int idx = tid; idx < NH * Jl; idx += blockDim.x) {       // consecutive threads: the heads of one key row (contiguous)
+        const int j = idx / NH, h = idx - j * NH, jg = j0 + j;
+        float sc = ROWS_NEG;
+        if (ok[j]) {
+            if (jg == 0) {
+                sc = 0.f;
+                for (int d = 0; d < DH; ++d) sc = fmaf(qs[h * QS + d], a.nk[h * DH + d], sc);
+            } else {
+                const size_t base = kvb + (size_t)(first + jg - 1) * 2 * inner + (size_t)h * DH;
+                sc = dot_q_k<DHT>(qs + h * QS, a.kv + base, a.kvl ? a.kvl + base : nullptr, DH);
+            }
+        }
+        s[h * ROWS_SPLIT + j] = sc;
+        a.sc[((size_t)b * J + jg) * NH + h] = sc;
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    for (int h = wave; h < NH; h += nw) {
+        float m = ROWS_NEG;
+        for (int j = lane; j < Jl; j += 64) m = fmaxf(m, s[h * ROWS_SPLIT + j]);
+        m = wave_max(m);
+        float sum = 0.f;
+        for (int j = lane; j < Jl; j += 64) sum += ok[j] ? __expf(s[h * ROWS_SPLIT + j] - m) : 0.f;
+        sum = wave_sum(sum);
+        if (lane == 0) {
+            float* st = a.st + (((size_t)b * a.nsplit + sp) * NH + h) * 2;
+            st[0] = m;
+            st[1] = sum;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void rows_apply_kernel(RowsArgs a) {
+    __shared__ float pr[8 * ROWS_SPLIT];
+    __shared__ float pm[8 * ROWS_SPLIT];
+    __shared__ float red[2048];                                   // [slot group][inner]: 256 / (inner / 8) groups
+    __shared__ float mz[16];
+    __shared__ int ok[ROWS_SPLIT];
+    const int NH = a.heads, DH = a.dim_head, inner = NH * DH, J = a.T + 1;
+    const int sp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, first = a.first[0];
+    if (!rows_window_ok(a, first)) return;
+    const int j0 = sp * ROWS_SPLIT, Jl = min(ROWS_SPLIT, J - j0);
+    if (tid < NH) {                                               // the statistics of all splits meet in index order (eight loads in
+        const float* st = a.st + ((size_t)b * a.nsplit * NH + tid) * 2;   // flight at a time: one thread walks a chain of latencies)
+        float M = ROWS_NEG;
+        for (int i0 = 0; i0 < a.nsplit; i0 += 8) {
+            float mv[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) mv[k] = i0 + k < a.nsplit ? st[(size_t)(i0 + k) * NH * 2] : ROWS_NEG;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) M = fmaxf(M, mv[k]);
+        }
+        float Z = 0.f;
+        for (int i0 = 0; i0 < a.nsplit; i0 += 8) {
+            float mv[8], zv[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const bool in = i0 + k < a.nsplit;
+                mv[k] = in ? st[(size_t)(i0 + k) * NH * 2] : ROWS_NEG;
+                zv[k] = in ? st[(size_t)(i0 + k) * NH * 2 + 1] : 0.f;
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) Z = fmaf(zv[k], __expf(mv[k] - M), Z);
+        }
+        mz[tid] = M;
+        mz[8 + tid] = 1.f / Z;                                    // (the null key is always visible: Z >= 1 term)
+    }
+    for (int j = tid; j < Jl; j += blockDim.x) {
+        const int jg = j0 + j;
+        ok[j] = jg == 0 || !a.mask || a.mask[(size_t)b * a.T + jg - 1] != 0;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < NH * Jl; idx += blockDim.x) {
+        const int j = idx / NH, h = idx - j * NH;
+        const float sv = a.sc[((size_t)b * J + j0 + j) * NH + h];
+        pr[h * ROWS_SPLIT + j] = ok[j] ? __expf(sv - mz[h]) * mz[8 + h] : 0.f;
+    }
+    __syncthreads();
+    // talking heads + the Conv3d bias, which reaches EVERY slot (null and masked ones included), as the reference's biased mix does
+    for (int idx = tid; idx < NH * Jl; idx += blockDim.x) {
+        const int g = idx / Jl, j = idx - g * Jl;
+        float acc = 0.f;
+        for (int h = 0; h < NH; ++h) acc = fmaf(a.wth[g * NH + h], pr[h * ROWS_SPLIT + j], acc);
+        pm[g * ROWS_SPLIT + j] = a.bias ? acc + a.bias[g] : acc;
+    }
+    __syncthreads();
+    const int nchunk = inner / 8, ngrp = blockDim.x / nchunk;
+    const int ch = tid % nchunk, grp = tid / nchunk, c0 = ch * 8, g = c0 / DH;
+    const int off = sp == 0 ? 1 : 0;                              // slot 0 is the fp32 null value, added below
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (grp < ngrp) {
+        const bf16_t* vb = a.kv + (size_t)b * a.cache_rows * 2 * inner;
+        const bf16_t* vlb = a.kvl ? a.kvl + (size_t)b * a.cache_rows * 2 * inner : nullptr;
+        const size_t r0 = (size_t)(first + j0 + off - 1);
+        pv_chunk(acc, pm + g * ROWS_SPLIT + off, vb, vlb, grp, ngrp, Jl - off, [&](int j) { return (r0 + j) * 2 * inner + inner + c0; });
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[grp * inner + c0 + e] = acc[e];
+    }
+    __syncthreads();
+    for (int c = tid; c < inner; c += blockDim.x) {
+        float t = 0.f;
+        for (int gi = 0; gi < ngrp; ++gi) t += red[gi * inner + c];
+        if (sp == 0) t = fmaf(pm[(c / DH) * ROWS_SPLIT], a.nv[c], t);
+        a.part[((size_t)b * a.nsplit + sp) * inner + c] = t;
+    }
+}
+
+__global__ __launch_bounds__(256) void rows_reduce_kernel(RowsArgs a) {
+    const int inner = a.heads * a.dim_head, b = blockIdx.x;
+    if (!rows_window_ok(a, a.first[0])) return;
+    for (int c = threadIdx.x; c < inner; c += blockDim.x) {
+        const float* part = a.part + (size_t)b * a.nsplit * inner + c;
+        float t = 0.f;
+        for (int i0 = 0; i0 < a.nsplit; i0 += 8) {                // index order, eight loads in flight
+            float pv[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) pv[k] = i0 + k < a.nsplit ? part[(size_t)(i0 + k) * inner] : 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t += pv[k];
+        }
+        st_hl(a.o, a.ol, (size_t)b * a.ldo + c, t);
+    }
+}
+
+size_t rows_ws_floats(int B, int T, int heads, int dim_head, int& nsplit) {
+    nsplit = (T + 1 + ROWS_SPLIT - 1) / ROWS_SPLIT;
+    return (size_t)B * ((size_t)heads * (T + 1) + (size_t)nsplit * (2 * heads + heads * dim_head));
+}
+
 }  // namespace
+
+extern "C" size_t amdnuwa_attn_decode_rows_workspace_bytes(int B, int T, int heads, int dim_head) {
+    if (B <= 0 || T < 1 || heads <= 0 || dim_head <= 0) return 0;
+    int nsplit;
+    return rows_ws_floats(B, T, heads, dim_head, nsplit) * sizeof(float);
+}
+
+extern "C" int amdnuwa_attn_decode_rows(int B, int T, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo,
+                                        int ldq, const uint16_t* kv, const uint16_t* kv_lo, int cache_rows, const int* first_row,
+                                        const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th,
+                                        const float* th_bias, uint16_t* o, uint16_t* o_lo, int ldo, void* workspace,
+                                        size_t workspace_bytes, hipStream_t stream) {
+    if (!q || !kv || !first_row || !null_k || !null_v || !w_th || !o) return AMDNUWA_ERR_ARG;
+    if (heads <= 0 || dim_head <= 0 || T < 1 || cache_rows < T) return AMDNUWA_ERR_ARG;
+    if (heads > 8 || (dim_head != 32 && dim_head != 64)) return AMDNUWA_ERR_UNSUPPORTED;
+    if (ldq < heads * dim_head || ldo < heads * dim_head) return AMDNUWA_ERR_ARG;
+    if (B <= 0) return AMDNUWA_OK;
+    RowsArgs a{};
+    const size_t nf = rows_ws_floats(B, T, heads, dim_head, a.nsplit);
+    if (!workspace || workspace_bytes < nf * sizeof(float)) return AMDNUWA_ERR_WORKSPACE;
+    a.q = q; a.ql = q_lo; a.kv = kv; a.kvl = kv_lo; a.first = first_row; a.mask = key_mask; a.nk = null_k; a.nv = null_v;
+    a.wth = w_th; a.bias = th_bias; a.o = o; a.ol = o_lo; a.ldq = ldq; a.ldo = ldo; a.cache_rows = cache_rows; a.T = T;
+    a.heads = heads; a.dim_head = dim_head; a.scale = scale;
+    a.sc = static_cast<float*>(workspace);
+    a.st = a.sc + (size_t)B * heads * (T + 1);
+    a.part = a.st + (size_t)B * a.nsplit * heads * 2;
+    const dim3 grid(a.nsplit, B);
+    if (dim_head == 64) hipLaunchKernelGGL((rows_stats_kernel<64>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((rows_stats_kernel<32>), grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(rows_apply_kernel, grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(rows_reduce_kernel, dim3(B), dim3(256), 0, stream, a);
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
 
 extern "C" int amdnuwa_decode_shift(const uint16_t* h_hi, const uint16_t* h_lo, uint16_t* cache_hi, uint16_t* cache_lo,
                                     uint16_t* out_hi, uint16_t* out_lo, const int* pos, int B, int cache_rows, int D,

@@ -392,7 +392,8 @@ __global__ __launch_bounds__(256) void rows_l2norm_kernel(float* __restrict__ x,
     for (int i = lane; i < len; i += 64) p[i] *= inv;
 }
 
-// one workgroup per (image, head), one thread per query position i (P <= 256 positions, c <= 64 channels per head):
+// one workgroup per (image, head), one thread per query position i (c <= 64 channels per head; beyond 256 positions a thread takes
+// positions i, i + 256, ... in turn -- a 17 x 17 token map has 289):
 //   s_ij = (sum_c qn[c][i] kn[c][j]) * exp(scale[head]) + bias[head][i][j];  softmax over j;  out[c][i] = sum_j p_ij v[c][j]
 // kn and v of the head sit in LDS and are read by all threads at the same address (broadcast).  Two passes over j (row max,
 // then exp / sum / PV) -- the whole block is < 0.5 % of the tokenizer, clarity over speed.
@@ -402,14 +403,14 @@ __global__ __launch_bounds__(256) void vqattn_core_kernel(const float* __restric
     extern __shared__ float sm[];
     float* ks = sm;                     // [c][P]
     float* vs = sm + c * P;             // [c][P]
-    const int n = blockIdx.x / heads, hh = blockIdx.x % heads, i = threadIdx.x;
+    const int n = blockIdx.x / heads, hh = blockIdx.x % heads;
     const size_t img = (size_t)n * 3 * heads * c * P;
     const float* q = qkv + img + (size_t)hh * c * P;
     const float* k = qkv + img + (size_t)(heads + hh) * c * P;
     const float* v = qkv + img + (size_t)(2 * heads + hh) * c * P;
     for (int e = threadIdx.x; e < c * P; e += blockDim.x) { ks[e] = k[e]; vs[e] = v[e]; }
     __syncthreads();
-    if (i >= P) return;
+    for (int i = threadIdx.x; i < P; i += blockDim.x) {       // (more than 256 positions: a thread takes several queries in turn)
     float qv[64], acc[64];
 #pragma unroll
     for (int cc = 0; cc < 64; ++cc) { qv[cc] = cc < c ? q[(size_t)cc * P + i] : 0.f; acc[cc] = 0.f; }
@@ -468,6 +469,7 @@ __global__ __launch_bounds__(256) void vqattn_core_kernel(const float* __restric
     float* o = out + ((size_t)n * heads + hh) * c * P;
 #pragma unroll
     for (int cc = 0; cc < 64; ++cc) if (cc < c) o[(size_t)cc * P + i] = acc[cc] * il;
+    }
 }
 
 // The same block on the f32 MFMA for the cfg-3 shape (64 channels per head, 256 positions).  Workgroup = (image, head, half of the
@@ -662,7 +664,7 @@ extern "C" int amdnuwa_rows_l2norm(float* x, int groups, int rows_per_group, int
 extern "C" int amdnuwa_vqattn_core(const float* qkv, const float* bias, const float* scale, float* out, int N, int heads, int dim_head,
                                    int P, hipStream_t stream) {
     if (!qkv || !bias || !scale || !out || heads <= 0) return AMDNUWA_ERR_ARG;
-    if (dim_head < 1 || dim_head > 64 || P < 1 || P > 256) return AMDNUWA_ERR_UNSUPPORTED;
+    if (dim_head < 1 || dim_head > 64 || P < 1 || (size_t)2 * dim_head * P * sizeof(float) > 160 * 1024) return AMDNUWA_ERR_UNSUPPORTED;
     if (N <= 0) return AMDNUWA_OK;
     if (dim_head == VA_C && P == VA_P && g_amdnuwa_tuning[15] != 1) {
         const size_t lds2 = (size_t)(VA_C * VA_P + VA_C * VA_LDV) * sizeof(float);

@@ -280,12 +280,16 @@ class _XmDirection:
     token) belongs to frame (r - 1) // chunk_size and attends a learned null key + context frame f of the sequence
     [context_chunk_size - 1 zero rows, the context stream's rows]: i.e. the other stream one frame EARLIER (frame 0: zero rows + its
     start token), complete by the time any query row of frame f exists.  The start-token row outputs 0.  The Conv3d talking heads
-    carry a BIAS: it adds bias[g] * (null_v[g] + sum_j v_j[g]) to the head output, a per-frame constant kept as a correction row."""
+    carry a BIAS: it adds bias[g] * (null_v[g] + sum_j v_j[g]) to the head output, a per-frame constant kept as a correction row.
+
+    A frame of more than 287 context rows (context_chunk_size + 1 > 288 slots: a token map of 17 x 17 or more) does not fit the packed
+    key images of the short kernel: those rows are attended IN PLACE by amdnuwa_attn_decode_rows, which reads the window of self.kv that
+    starts at the device-side row f * cc and takes the bias inside its mix -- no pack, no correction row."""
 
     def __init__(self, mod, batch, ctx_rows, dev, lo):
         from torch import nn
         if not (isinstance(mod.norm, nn.Identity) and isinstance(mod.context_norm, nn.Identity) and mod.has_start_token and
-                mod.context_has_start_token and mod.dim_head in (32, 64) and mod.heads <= 8 and mod.context_chunk_size + 1 <= 288):
+                mod.context_has_start_token and mod.dim_head in (32, 64) and mod.heads <= 8):
             raise NotImplementedError('cached decoding: this CrossModalityCrossAttention configuration is not on the libamdnuwa path')
         self.mod, self.B, self.lo = mod, batch, lo
         self.c, self.cc = mod.chunk_size, mod.context_chunk_size
@@ -293,12 +297,17 @@ class _XmDirection:
         # context rows under mod.to_kv: cc - 1 zero rows (to_kv has no bias), then context row r at cc - 1 + r, so that context
         # frame f is rows [f * cc, (f + 1) * cc)
         self.kv = K.zeros_bf((batch, self.cc - 1 + ctx_rows, 2 * self.inner), dev, lo=lo)
-        self.g = K.x_geom(batch, 1, self.cc, mod.heads, mod.dim_head)
         # n_ctx / n_q: HOST row counters (advanced by the decoder that owns the streams, never inside a captured graph);
-        # pk / corr: persistent buffers, re-packed in place at every frame border (a captured step keeps reading them)
+        # pk / corr: persistent buffers, re-packed in place at every frame border (a captured step keeps reading them);
+        # first: the long form's window start f * cc, rewritten in place at every frame border for the same reason
         self.n_ctx, self.n_q, self.frame = 0, 0, -1
-        self.pk = K.PackedKV(self.g, dev, lo)
-        self.corr = torch.zeros((batch, mod.to_out.weight.shape[0]), dtype=torch.float32, device=dev)
+        self.long = self.cc + 1 > 288
+        if self.long:
+            self.first = torch.zeros(1, dtype=torch.int32, device=dev)
+        else:
+            self.g = K.x_geom(batch, 1, self.cc, mod.heads, mod.dim_head)
+            self.pk = K.PackedKV(self.g, dev, lo)
+            self.corr = torch.zeros((batch, mod.to_out.weight.shape[0]), dtype=torch.float32, device=dev)
 
     def _weights(self):
         m, h = self.mod, self.mod.heads
@@ -319,6 +328,10 @@ class _XmDirection:
         m, cc = self.mod, self.cc
         if self.n_ctx < f * cc + 1:
             raise RuntimeError('cached decoding: the other stream has not produced the frame this row attends')
+        if self.long:
+            self.first.fill_(f * cc)
+            self.frame = f
+            return
         sl = slice(f * cc, (f + 1) * cc)
         kv = K.BF(self.kv.hi[:, sl].reshape(self.B * cc, 2 * self.inner).contiguous(),
                   self.kv.lo[:, sl].reshape(self.B * cc, 2 * self.inner).contiguous() if self.kv.lo is not None else None)
@@ -332,7 +345,7 @@ class _XmDirection:
         self.frame = f
 
     def needs_eager_row(self, r):
-        """query row r cannot be replayed from the graph of an ordinary row: the start token (outputs 0) or the first row of a frame (packs)"""
+        """query row r cannot be replayed from the graph of an ordinary row: the start token (outputs 0) or the first row of a frame (packs, or moves the window)"""
         return r == 0 or (r - 1) // self.c != self.frame
 
     def attend(self, h):
@@ -345,7 +358,12 @@ class _XmDirection:
             self._pack(f)
         W = self._weights()
         q = K.gemm_nt(h, W['q'], out_bf16=True)
-        o = K.xattn_decode(self.g, q, self.pk, m.talking_heads.weight.detach().reshape(m.heads, m.heads).contiguous())
+        wth = m.talking_heads.weight.detach().reshape(m.heads, m.heads).contiguous()
+        if self.long:
+            o = K.attn_decode_rows(q, self.kv, self.first, self.cc, m.heads, m.dim_head, m.null_k.detach().reshape(m.heads, -1).contiguous(),
+                                   m.null_v.detach().reshape(m.heads, -1).contiguous(), wth, th_bias=m.talking_heads.bias.detach().contiguous())
+            return K.gemm_nt(o, W['out'], out_bf16=False)
+        o = K.xattn_decode(self.g, q, self.pk, wth)
         return K.gemm_nt(o, W['out'], out_bf16=False) + self.corr
 
 

@@ -1180,6 +1180,32 @@ def xattn_decode(g, q, pk, wth):
     return o
 
 
+ATTN_DECODE_ROWS_SPLIT = 128     # slots (null key + T rows) per workgroup of amdnuwa_attn_decode_rows: a function of T alone
+
+
+def attn_decode_rows_splits(T):
+    return (T + 1 + ATTN_DECODE_ROWS_SPLIT - 1) // ATTN_DECODE_ROWS_SPLIT
+
+
+def attn_decode_rows(q, kv, first_dev, T, heads, dim_head, null_k, null_v, wth, th_bias=None, mask_u8=None, scale=None):
+    """single-query attention over T cached rows: q BF [B, inner] (unscaled); kv BF [B, cache_rows, 2 * inner] (k | v); first_dev int32
+    [1] on the device: the cache row of the first key; null_k / null_v fp32 [heads, dim_head]; wth fp32 [heads, heads]; th_bias fp32
+    [heads] or None; mask_u8 [B, T] or None.  Returns o BF [B, inner]"""
+    L = _lib.lib()
+    _chk_dev(q.hi, kv.hi, first_dev, null_k, null_v, wth, th_bias, mask_u8)
+    B, inner = q.hi.shape[0], heads * dim_head
+    assert kv.hi.dim() == 3 and kv.hi.is_contiguous() and kv.hi.shape[0] == B and kv.hi.shape[2] == 2 * inner
+    assert first_dev.dtype == torch.int32 and (mask_u8 is None or (mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (B, T) and mask_u8.is_contiguous()))
+    o = empty_bf((B, inner), q.hi.device, lo=q.lo is not None)
+    nb = L.amdnuwa_attn_decode_rows_workspace_bytes(B, T, heads, dim_head)
+    ws = workspace(nb, q.hi.device)
+    check(L.amdnuwa_attn_decode_rows(B, T, heads, dim_head, dim_head ** -0.5 if scale is None else scale, _p(q.hi), _p(q.lo),
+                                     q.hi.stride(0), _p(kv.hi), _p(kv.lo), kv.hi.shape[1], _p(first_dev), _p(mask_u8), _p(null_k),
+                                     _p(null_v), _p(wth), _p(th_bias), _p(o.hi), _p(o.lo), inner, _p(ws), nb, _stream()),
+          'amdnuwa_attn_decode_rows')
+    return o
+
+
 def x_geom(B, n, T, heads, dim_head):
     g = XGeom()
     g.B, g.n, g.T = B, n, T

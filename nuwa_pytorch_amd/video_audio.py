@@ -150,6 +150,19 @@ class CrossModalityCrossAttention(nn.Module):
         self._cache = ops.WeightCache()
         self.use_hip = True            # False: the torch-op formulation (kept for head sizes the kernels do not cover)
 
+    # Context frames of more than 287 rows (a token map of 17 x 17 or more) do not fit the packed key images of the cross-attention kernels:
+    # they run on the rectangular cattn kernels (every (sample, frame) pair one sample of c queries x cc keys) where that is the faster
+    # route -- the thresholds of Attention._long_hip_ok, measured on these kernels for this shape class; both 0
+    # routes every such shape.
+    long_pairs_min = 1 << 23         # (b * frames) * chunk_size * context_chunk_size
+    long_wgs_min = 128               # workgroups of the query-stationary and of the key-stationary sweeps, each
+
+    def _long_hip_ok(self, batch, n_queries, n_keys):
+        from . import kernels as K
+        ok = n_keys > 287 and self.dim_head in (32, 64) and self.heads <= 8 and (K.get_precision() == 'bf16' or K.cores_f16())
+        return ok and batch * n_queries * n_keys >= self.long_pairs_min and \
+            batch * min(-(-n_queries // 64), -(-n_keys // 64)) >= self.long_wgs_min
+
     def forward(self, seq, context, mask=None, context_mask=None):
         if self.training and self.dropout.p > 0:
             raise NotImplementedError('attention dropout inside CrossModalityCrossAttention is not built')
@@ -170,15 +183,19 @@ class CrossModalityCrossAttention(nn.Module):
             return torch.zeros_like(seq)
         qf = self.norm(body[:, :nf * c].reshape(b, nf, c, dim))
         cf = self.context_norm(ctx[:, :nf * cc].reshape(b, nf, cc, -1))
-        if self.use_hip and seq.is_cuda and self.dim_head in (32, 64) and h <= 8 and cc + 1 <= 288:
-            # every (sample, frame) pair is one sample of the libamdnuwa cross-attention kernels (null k/v, key mask, talking heads);
+        if self.use_hip and seq.is_cuda and self.dim_head in (32, 64) and h <= 8 and (cc + 1 <= 288 or self._long_hip_ok(b * nf, c, cc)):
+            # every (sample, frame) pair is one sample of the libamdnuwa cross-attention kernels (null k/v, key mask, talking heads) -- of
+            # the linear-memory cattn kernels when a context frame has more rows than those take;
             # the Conv3d BIAS adds bias[g] to every attention weight, i.e. bias[g] * (null_v[g] + sum_j v_j[g]) to the head output
             from . import kernels as K
             inner = h * self.dim_head
             xq, xc = qf.reshape(b * nf, c, dim), cf.reshape(b * nf, cc, -1)
-            g = K.x_geom(b * nf, c, cc, h, self.dim_head)
             km = cmask[:, :nf * cc].reshape(b * nf, cc).to(torch.uint8).contiguous() if exists(cmask) else None
-            meta = dict(kind='xattn', cache=self._cache, xgeom=g, mask_u8=km, save=torch.is_grad_enabled())
+            if cc + 1 <= 288:
+                meta = dict(kind='xattn', cache=self._cache, xgeom=K.x_geom(b * nf, c, cc, h, self.dim_head), mask_u8=km, save=torch.is_grad_enabled())
+            else:
+                meta = dict(kind='cattn', cache=self._cache, cgeom=K.cattn_geom(b * nf, c, h, self.dim_head, causal=False, n_keys=cc),
+                            mask_u8=km, has_ctx=True)
             out = ops.InnerFn.apply(xq, xc, meta, self.null_k.reshape(h, 1, -1), self.null_v.reshape(h, 1, -1),
                                     self.talking_heads.weight.reshape(h, h, 1, 1), self.to_q.weight, self.to_kv.weight, self.to_out.weight)
             vsum = self.null_v[None] + F.linear(xc.sum(1), self.to_kv.weight[inner:]).reshape(b * nf, h, -1)
