@@ -53,7 +53,7 @@ const char* amdnuwa_error_string(int code);
  *   key 8  TN 256x256 ring: 2 = staggered wave rows instead of the lock-step schedule
  *   key 9  3DNA MFMA forward probe: bits 0 / 1 / 2 skip the score / softmax+mix / apply phase (garbage results), bit 3 = fragment-shaped
  *          key loads in the score pass instead of the staged ones
- *   key 14 NT start-phase step in ~0.25 us units (0 = off)        key 15 VAE kernels: 1 = first (VALU) forms
+ *   key 14 NT start-phase step in ~0.25 us units (0 = off)        key 15 VAE kernels: 1 = first (VALU) forms, 2 = tiled vqattn
  *   key 16 Sparse3DNA MFMA forward: query rows per workgroup (0 = auto = 2 where H splits into dh * rows; 1 / 2 / 4 forced): a tile of rows
  *          of one residue class of y stages every key / value row once for the rows that tap it
  *   key 17 3DNA backward timing probes (garbage results): bit 0 no score sweeps, 1 no ds / P' workspace stores, 2 no dq apply sweep,
@@ -624,8 +624,18 @@ int amdnuwa_vq_argmax_ws(const float* x, const float* codebook, long long* indic
  * module's parameters and the learned log-scale, and LayerNormChan (+ residual) over the channel axis of an NCHW tensor. */
 /* rows: `groups` groups of rows_per_group consecutive rows of length len, group g starting at row g * group_stride_rows */
 int amdnuwa_rows_l2norm(float* x, int groups, int rows_per_group, int group_stride_rows, int len, amdnuwa_stream stream);
+/* attention core: qkv [N][3 heads dim_head][P] (q, k already normalised), bias [heads][P][P], scale [heads], out [N][heads dim_head][P].
+ * Envelope: dim_head 1 ... 64 (more: UNSUPPORTED), ANY P >= 1.  Where k and v of one head fit LDS (2 dim_head P 4 B <= 160 KiB, i.e.
+ * P <= 320 at dim_head 64) the resident kernels run (P = 256, dim_head = 64: f32 MFMA; else VALU); every other shape runs the
+ * query-tiled, key-streaming f32 MFMA kernel (online softmax, keys in index order: deterministic, an image's bits do not depend on N).
+ * Tuning key 15 = 2 sends every shape to the tiled kernel. */
 int amdnuwa_vqattn_core(const float* qkv, const float* bias, const float* scale, float* out, int N, int heads, int dim_head,
                         int P, amdnuwa_stream stream);
+/* the same core on a square side x side map (P = side^2) with the bias as a relative-offset table [heads][2 side - 1][2 side - 1]:
+ * bias(i, j) = table[h][y_i - y_j + side - 1][x_i - x_j + side - 1].  Always the tiled kernel, the head's table in LDS.
+ * Envelope: dim_head 1 ... 64, side 1 ... 64 (beyond either: UNSUPPORTED). */
+int amdnuwa_vqattn_core_rel(const float* qkv, const float* table, const float* scale, float* out, int N, int heads, int dim_head,
+                            int side, amdnuwa_stream stream);
 int amdnuwa_chan_layernorm(const float* x, const float* g, const float* b, const float* resid, float* y, int N, int C, int HW,
                            float eps, amdnuwa_stream stream);
 

@@ -163,6 +163,7 @@ SIGNATURES = {
     'amdnuwa_adamw_step': (I, [P, I, F, F, F, F, P, P]),
     'amdnuwa_rows_l2norm': (I, [P, I, I, I, I, P]),
     'amdnuwa_vqattn_core': (I, [P, P, P, P, I, I, I, I, P]),
+    'amdnuwa_vqattn_core_rel': (I, [P, P, P, P, I, I, I, I, P]),
     'amdnuwa_chan_layernorm': (I, [P, P, P, P, P, I, I, I, F, P]),
     'amdnuwa_comm_available': (I, []),
     'amdnuwa_comm_last_error': (C.c_char_p, []),

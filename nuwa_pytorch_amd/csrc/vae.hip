@@ -552,6 +552,168 @@ __global__ __launch_bounds__(256) void vqattn_mfma_kernel(const float* __restric
         for (int r = 0; r < 16; ++r) op[(size_t)(32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi) * VA_P] = o[t][r] * il;
 }
 
+// The same block for ANY number of positions: query-tiled, keys and values streamed through LDS, nothing of size P resident.
+// Workgroup = (image, head, 128 queries), wave = 32 queries, the transposed formulation of vqattn_mfma_kernel (a lane owns one
+// query).  Keys come in tiles of 64 in index order; the softmax is rescaled online (running maximum m, partial sum l and the
+// accumulators times exp(m_old - m_new) per tile): one sweep over the keys, where a max pass first would compute S = K^T Q twice
+// (+50 % matrix work) to save 32 multiplies per 128 MFMAs.  A padded key gets the score -3e38, hence probability 0, and its k / v
+// are zeros in LDS; a padded query computes on the last real one and is not stored.  Channels are padded with zero rows to 2 KK
+// (k steps of S) and 32 OT (row tiles of O).  No atomics, no workspace: the bits depend on (image, head, query) alone.
+//   REL = false: bias[heads][P][P] from memory (four consecutive keys per load where P % 4 == 0)
+//   REL = true : tab[heads][2S-1][2S-1] of a square S x S map, the head's table in LDS behind the tiles;
+//                bias(i, j) = tab[(y_i - y_j + S-1) (2S-1) + x_i - x_j + S-1]
+// LDS: k tile [2 KK][64], v tile [32 OT][65] (lanes along c: conflict-free): 33 KB at dim_head 64; the table form adds the rows
+// of the table that 128 consecutive queries reach, at most S + 2 of the 2S-1 (33 KB of the 63 KB table of a 64 x 64 map: two
+// workgroups per CU, which is also what the registers allow).
+constexpr int VT_KT = 64, VT_LDV = 65, VT_QB = 128;
+// 128 consecutive positions touch at most 127 / S + 2 rows of an S-wide map; rows ylo ... yhi reach yhi - ylo + S table rows
+static inline int vt_tab_rows(int S) {
+    const int span = (VT_QB - 1) / S + 2 < S ? (VT_QB - 1) / S + 2 : S;
+    return S - 1 + span;
+}
+template <int KK, int OT, bool REL>
+__global__ __launch_bounds__(256) void vqattn_tiled_kernel(const float* __restrict__ qkv, const float* __restrict__ bias,
+                                                           const float* __restrict__ scale, float* __restrict__ out, int heads, int c,
+                                                           int P, int S, int qblocks) {
+    extern __shared__ float sm[];
+    float* ks = sm;                         // [2 KK][64]
+    float* vs = sm + 2 * KK * VT_KT;        // [32 OT][65]
+    float* tab = vs + 32 * OT * VT_LDV;     // [<= vt_tab_rows(S)][2S-1]: the table rows this workgroup's queries reach (REL)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, ln = lane & 31;
+    const int qb_i = blockIdx.x % qblocks, nh = blockIdx.x / qblocks, n = nh / heads, hh = nh % heads;
+    const size_t img = (size_t)n * 3 * heads * c * P;
+    const float* q = qkv + img + (size_t)hh * c * P;
+    const float* k = qkv + img + (size_t)(heads + hh) * c * P;
+    const float* v = qkv + img + (size_t)(2 * heads + hh) * c * P;
+    const int i_raw = qb_i * VT_QB + wave * 32 + ln;
+    const int i = i_raw < P ? i_raw : P - 1;
+    const int W = 2 * S - 1;
+    // the 128 queries of a workgroup lie on rows ylo ... yhi of the map: of the 2S-1 table rows (dy + S-1) they reach ylo ... yhi + S-1
+    const int ylo = REL ? qb_i * VT_QB / S : 0;
+    if (REL) {
+        const int ilast = qb_i * VT_QB + VT_QB - 1 < P ? qb_i * VT_QB + VT_QB - 1 : P - 1;
+        const int nrows = ilast / S - ylo + S;
+        const float* t = bias + ((size_t)hh * W + ylo) * W;
+        for (int e = tid; e < nrows * W; e += 256) tab[e] = t[e];
+    }
+    float qb[KK];
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) { const int cc = 2 * kk + hi; qb[kk] = cc < c ? q[(size_t)cc * P + i] : 0.f; }
+    const float se = expf(scale[hh]);
+    const float* brow = bias + ((size_t)hh * P + i) * P;             // !REL
+    const int ibase = REL ? (i / S + S - 1 - ylo) * W + i % S + S - 1 : 0;
+    const float invS = REL ? 1.f / (float)S : 0.f;
+    // four keys per load: rows of P floats stay 16-byte aligned only where P % 4 == 0 and the tensors themselves are
+    const bool vec = (P & 3) == 0 && ((uintptr_t)qkv & 15) == 0 && (REL || ((uintptr_t)bias & 15) == 0);
+    f32x16 o[OT];
+#pragma unroll
+    for (int t = 0; t < OT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
+    float m = -3.0e38f, l = 0.f;
+    for (int j0 = 0; j0 < P; j0 += VT_KT) {
+        __syncthreads();                    // the previous tile is consumed (first trip: nothing)
+        if (vec) {
+            for (int e = tid; e < 2 * KK * (VT_KT / 4); e += 256) {
+                const int cc = e >> 4, j4 = (e & 15) * 4;
+                float4 k4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (cc < c && j0 + j4 < P) k4 = *reinterpret_cast<const float4*>(k + (size_t)cc * P + j0 + j4);
+                *reinterpret_cast<float4*>(ks + cc * VT_KT + j4) = k4;
+            }
+            for (int e = tid; e < 32 * OT * (VT_KT / 4); e += 256) {
+                const int cc = e >> 4, j4 = (e & 15) * 4;
+                float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (cc < c && j0 + j4 < P) v4 = *reinterpret_cast<const float4*>(v + (size_t)cc * P + j0 + j4);
+                float* d = vs + cc * VT_LDV + j4;
+                d[0] = v4.x; d[1] = v4.y; d[2] = v4.z; d[3] = v4.w;
+            }
+        } else {
+            for (int e = tid; e < 2 * KK * VT_KT; e += 256) {
+                const int cc = e >> 6, jj = e & 63;
+                ks[cc * VT_KT + jj] = (cc < c && j0 + jj < P) ? k[(size_t)cc * P + j0 + jj] : 0.f;
+            }
+            for (int e = tid; e < 32 * OT * VT_KT; e += 256) {
+                const int cc = e >> 6, jj = e & 63;
+                vs[cc * VT_LDV + jj] = (cc < c && j0 + jj < P) ? v[(size_t)cc * P + j0 + jj] : 0.f;
+            }
+        }
+        __syncthreads();
+        f32x16 st[2];
+#pragma unroll
+        for (int T = 0; T < 2; ++T) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) st[T][r] = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk)
+                st[T] = __builtin_amdgcn_mfma_f32_32x32x2f32(ks[(2 * kk + hi) * VT_KT + 32 * T + ln], qb[kk], st[T], 0, 0, 0);
+        }
+        // st[T][r] = s(i, j) with j = j0 + 32 T + (r & 3) + 8 (r >> 2) + 4 hi: four consecutive keys per register quad
+        float mt = -3.0e38f;
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int jq = j0 + 32 * T + 8 * g + 4 * hi;
+                float b[4];
+                if (REL) {
+                    int yj = (int)(((float)jq + 0.5f) * invS), xj = jq - yj * S;      // exact: S <= 64, jq < 4096 + 64
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (xj >= S) { xj -= S; ++yj; }
+                        b[e] = tab[jq + e < P ? ibase - yj * W - xj : 0];
+                        ++xj;
+                    }
+                } else if (vec) {
+                    float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (jq < P) b4 = *reinterpret_cast<const float4*>(brow + jq);
+                    b[0] = b4.x; b[1] = b4.y; b[2] = b4.z; b[3] = b4.w;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) b[e] = jq + e < P ? brow[jq + e] : 0.f;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float s = jq + e < P ? st[T][4 * g + e] * se + b[e] : -3.0e38f;
+                    st[T][4 * g + e] = s;
+                    mt = fmaxf(mt, s);
+                }
+            }
+        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+        const float mn = fmaxf(m, mt);
+        const float alpha = expf(m - mn);   // first tile: exp(-3e38 - mn) = 0 on l = 0, o = 0
+        m = mn;
+        float lt = 0.f;
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { st[T][r] = expf(st[T][r] - mn); lt += st[T][r]; }
+        l = l * alpha + lt;                 // per half-wave partial sum: both halves share m, they meet after the last tile
+#pragma unroll
+        for (int t = 0; t < OT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int jj = 32 * T + (r & 3) + 8 * (r >> 2) + 4 * hi;
+#pragma unroll
+                for (int t = 0; t < OT; ++t) o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vs[(32 * t + ln) * VT_LDV + jj], st[T][r], o[t], 0, 0, 0);
+            }
+    }
+    l += __shfl_xor(l, 32, 64);
+    if (i_raw >= P) return;
+    const float il = 1.f / l;
+    float* op = out + ((size_t)n * heads + hh) * c * P + i;
+#pragma unroll
+    for (int t = 0; t < OT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int cc = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            if (cc < c) op[(size_t)cc * P] = o[t][r] * il;
+        }
+}
+
 // LayerNormChan (vq.py:178-190) over the channel axis of an NCHW tensor, + residual.  A workgroup = 64 consecutive positions of one
 // image x 4 channel quarters: each thread keeps its C / 4 values in registers (one HBM read), statistics meet in LDS.
 template <int CQ>
@@ -661,11 +823,35 @@ extern "C" int amdnuwa_rows_l2norm(float* x, int groups, int rows_per_group, int
     return AMDNUWA_OK;
 }
 
+// launches the tiled kernel: full bias (side == 0) or relative-offset table (side > 0, P = side^2)
+static int vqattn_tiled_launch(const float* qkv, const float* bias, const float* scale, float* out, int N, int heads, int dim_head, int P,
+                               int side, hipStream_t stream) {
+    const int qblocks = (P + VT_QB - 1) / VT_QB;
+    const long long grid = (long long)N * heads * qblocks;
+    if (grid > 0x7fffffffLL) return AMDNUWA_ERR_UNSUPPORTED;
+    const int KK = dim_head <= 32 ? 16 : 32, OT = dim_head <= 32 ? 1 : 2;
+    const size_t lds = ((size_t)2 * KK * VT_KT + (size_t)32 * OT * VT_LDV + (side > 0 ? (size_t)vt_tab_rows(side) * (2 * side - 1) : 0)) * sizeof(float);
+#define VT_LAUNCH(KK_, OT_, REL_)                                                                                                       \
+    do {                                                                                                                                \
+        (void)hipFuncSetAttribute((const void*)vqattn_tiled_kernel<KK_, OT_, REL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((vqattn_tiled_kernel<KK_, OT_, REL_>), dim3((unsigned)grid), dim3(256), lds, stream, qkv, bias, scale, out,  \
+                           heads, dim_head, P, side, qblocks);                                                                          \
+    } while (0)
+    if (side > 0) { if (KK == 16) VT_LAUNCH(16, 1, true); else VT_LAUNCH(32, 2, true); }
+    else { if (KK == 16) VT_LAUNCH(16, 1, false); else VT_LAUNCH(32, 2, false); }
+#undef VT_LAUNCH
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+
 extern "C" int amdnuwa_vqattn_core(const float* qkv, const float* bias, const float* scale, float* out, int N, int heads, int dim_head,
                                    int P, hipStream_t stream) {
     if (!qkv || !bias || !scale || !out || heads <= 0) return AMDNUWA_ERR_ARG;
-    if (dim_head < 1 || dim_head > 64 || P < 1 || (size_t)2 * dim_head * P * sizeof(float) > 160 * 1024) return AMDNUWA_ERR_UNSUPPORTED;
+    if (dim_head < 1 || dim_head > 64 || P < 1) return AMDNUWA_ERR_UNSUPPORTED;
     if (N <= 0) return AMDNUWA_OK;
+    // keys and values of a head resident in LDS (P <= 320 at dim_head 64): the kernels of before; everything else, or tuning 15 = 2: tiled
+    const bool resident = (size_t)2 * dim_head * P * sizeof(float) <= 160 * 1024;
+    if (!resident || g_amdnuwa_tuning[15] == 2) return vqattn_tiled_launch(qkv, bias, scale, out, N, heads, dim_head, P, 0, stream);
     if (dim_head == VA_C && P == VA_P && g_amdnuwa_tuning[15] != 1) {
         const size_t lds2 = (size_t)(VA_C * VA_P + VA_C * VA_LDV) * sizeof(float);
         (void)hipFuncSetAttribute((const void*)vqattn_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
@@ -678,6 +864,14 @@ extern "C" int amdnuwa_vqattn_core(const float* qkv, const float* bias, const fl
     hipLaunchKernelGGL(vqattn_core_kernel, dim3(N * heads), dim3(256), lds, stream, qkv, bias, scale, out, heads, dim_head, P);
     LAUNCH_CHECK();
     return AMDNUWA_OK;
+}
+
+extern "C" int amdnuwa_vqattn_core_rel(const float* qkv, const float* table, const float* scale, float* out, int N, int heads, int dim_head,
+                                       int side, hipStream_t stream) {
+    if (!qkv || !table || !scale || !out || heads <= 0) return AMDNUWA_ERR_ARG;
+    if (dim_head < 1 || dim_head > 64 || side < 1 || side > 64) return AMDNUWA_ERR_UNSUPPORTED;
+    if (N <= 0) return AMDNUWA_OK;
+    return vqattn_tiled_launch(qkv, table, scale, out, N, heads, dim_head, side * side, side, stream);
 }
 
 extern "C" int amdnuwa_chan_layernorm(const float* x, const float* g, const float* b, const float* resid, float* y, int N, int C, int HW,

@@ -1788,9 +1788,36 @@ def vq_argmax(x, codebook, want_sim=False):
     return (idx, sim) if want_sim else idx
 
 
-def vqgan_attention(x, qkv_w, out_w, out_b, bias, scale, ln_g, ln_b, heads, eps):
+def vqattn_core(qkv, scale, heads, bias=None, rel_table=None):
+    """the attention core of VQGanAttention alone: qkv [N, 3*heads*c, ...positions] fp32 with q and k already l2-normalised, scale the
+    learned log-scale [heads]; out[n, h*c + cc, i] = sum_j softmax_j(q_i . k_j * exp(scale_h) + bias_h(i, j)) v[cc, j].  The bias is
+    EITHER `bias` [heads, P, P] (any P) OR `rel_table` [heads, 2S-1, 2S-1] of a square S x S map (P = S*S, S <= 64):
+    bias_h(i, j) = rel_table[h, y_i - y_j + S-1, x_i - x_j + S-1] (ContinuousPositionBias.table)."""
+    assert (bias is None) != (rel_table is None), 'give exactly one of bias / rel_table'
+    L = _lib.lib()
+    qkv = _f32c(qkv)
+    N, P_ = qkv.shape[0], qkv[0, 0].numel()
+    assert qkv.shape[1] % (3 * heads) == 0, (qkv.shape, heads)
+    c = qkv.shape[1] // (3 * heads)
+    scale = _f32c(scale).reshape(-1)
+    assert scale.numel() == heads, (scale.shape, heads)
+    out = torch.empty((N, heads * c) + tuple(qkv.shape[2:]), dtype=torch.float32, device=qkv.device)
+    if bias is not None:
+        bias = _f32c(bias)
+        assert tuple(bias.shape) == (heads, P_, P_), (bias.shape, heads, P_)
+        check(L.amdnuwa_vqattn_core(_p(qkv), _p(bias), _p(scale), _p(out), N, heads, c, P_, _stream()), 'amdnuwa_vqattn_core')
+    else:
+        tab = _f32c(rel_table)
+        side = (tab.shape[-1] + 1) // 2
+        assert tuple(tab.shape) == (heads, 2 * side - 1, 2 * side - 1) and side * side == P_, (tab.shape, heads, P_)
+        check(L.amdnuwa_vqattn_core_rel(_p(qkv), _p(tab), _p(scale), _p(out), N, heads, c, side, _stream()), 'amdnuwa_vqattn_core_rel')
+    return out
+
+
+def vqgan_attention(x, qkv_w, out_w, out_b, bias, scale, ln_g, ln_b, heads, eps, rel_table=None):
     """VQGanAttention.forward (reference vqgan_vae.py:263-286) on NCHW fp32 x: returns post_norm(to_out(attn)) + x.
-    bias: continuous-position bias [heads, P, P] (parameters only); scale: the learned log-scale [heads]."""
+    bias: continuous-position bias [heads, P, P] (parameters only), or None with rel_table [heads, 2S-1, 2S-1], its relative-offset
+    form on a square map (vqattn_core); scale: the learned log-scale [heads]."""
     L = _lib.lib()
     x = _f32c(x)
     N, Cc, H, W = x.shape
@@ -1799,9 +1826,8 @@ def vqgan_attention(x, qkv_w, out_w, out_b, bias, scale, ln_g, ln_b, heads, eps)
     c = qkv.shape[1] // (3 * heads)
     # q and k = the first 2*heads*c of the 3*heads*c channel rows of every image
     check(L.amdnuwa_rows_l2norm(_p(qkv), N, 2 * heads * c, 3 * heads * c, P_, _stream()), 'amdnuwa_rows_l2norm')
-    out = torch.empty((N, heads * c, H, W), dtype=torch.float32, device=x.device)
-    check(L.amdnuwa_vqattn_core(_p(qkv), _p(_f32c(bias)), _p(_f32c(scale).reshape(-1)), _p(out), N, heads, c, P_, _stream()),
-          'amdnuwa_vqattn_core')
+    assert rel_table is None or H == W, 'the relative-offset table is for square maps'
+    out = vqattn_core(qkv, scale, heads, bias=bias, rel_table=rel_table)
     o = conv2d_fwd(out, out_w, out_b, 1, 0)
     y = torch.empty_like(o)
     check(L.amdnuwa_chan_layernorm(_p(o), _p(_f32c(ln_g).reshape(-1)), _p(_f32c(ln_b).reshape(-1)), _p(x), _p(y), N, o.shape[1], P_,

@@ -204,6 +204,16 @@ class ContinuousPositionBias(nn.Module):
             h = layer(h)
         return x + h.movedim(-1, 0)                                           # (i, j, heads) -> (heads, i, j)
 
+    def table(self, side, device=None):
+        """the bias as a function of the offset alone: [heads, 2*side-1, 2*side-1] with table[h, dy + side-1, dx + side-1] = the bias
+        forward() adds at every pair (i, j) with y_i - y_j = dy, x_i - x_j = dx -- the same MLP over (2*side-1)^2 rows instead of side^4"""
+        ax = torch.arange(-(side - 1), side, device=device)
+        delta = torch.cartesian_prod(ax, ax).reshape(-1, 2).float()
+        h = delta.sign() * (delta.abs() + 1).log()
+        for layer in self.net:
+            h = layer(h)
+        return h.reshape(2 * side - 1, 2 * side - 1, -1).movedim(-1, 0)
+
 
 def _res_body(chan, groups, glu):
     """conv3x3 -> [GLU | GroupNorm + LeakyReLU] twice, then conv1x1: GLUResBlock keeps (conv, GLU, GroupNorm) order, ResBlock
@@ -390,10 +400,18 @@ class VQGanVAE(nn.Module):
         if isinstance(m, VQGanAttention):
             B, _, height, width = x.shape
             P_ = height * width
-            # continuous position bias: a function of the module's parameters only (vq.py:192-226) -> [heads, P, P]
-            bias = m.cpb(torch.zeros(1, m.heads, P_, P_, device=x.device))[0]
+            # continuous position bias: a function of the module's parameters only (vq.py:192-226).  Maps whose keys and values fit
+            # LDS (the kernels of amdnuwa_vqattn_core that keep a head resident: P <= 320 at dim_head 64) take it as [heads, P, P];
+            # wider square maps up to 64 x 64 take the (2S-1)^2 offsets it really depends on (the tiled kernel, table in LDS) --
+            # [heads, P, P] costs an MLP over P^2 pairs, 16.7 M rows at 64 x 64; beyond that side the full bias again
+            dim_head = m.to_qkv.out_channels // (3 * m.heads)
+            bias = table = None
+            if 2 * dim_head * P_ * 4 <= 160 * 1024 or height != width or height > 64:
+                bias = m.cpb(torch.zeros(1, m.heads, P_, P_, device=x.device))[0]
+            else:
+                table = m.cpb.table(height, x.device)
             return K.vqgan_attention(x, m.to_qkv.weight, m.to_out.weight, m.to_out.bias, bias, m.scale, m.post_norm.g, m.post_norm.b,
-                                     m.heads, m.post_norm.eps)
+                                     m.heads, m.post_norm.eps, rel_table=table)
         if isinstance(m, GLUResBlock):                     # decoder (vq.py:212-226)
             c1, _, g1, c2, _, g2, c3 = m.net
             h = K.groupnorm_fwd(K.glu_chan(K.conv2d_fwd(x, c1.weight, c1.bias, 1, 1)), g1.weight, g1.bias, g1.num_groups, g1.eps)
