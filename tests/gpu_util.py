@@ -34,12 +34,12 @@ def report(name, got, ref, tol):
     return e
 
 
-def record(name, rel_max, l2, tol):
+def record(name, rel_max, l2, tol, finite=True):
     """log an already computed error pair (same file / format as report())"""
     try:
         os.makedirs(os.path.dirname(LOG), exist_ok=True)
         with open(LOG, 'a') as f:
-            f.write(json.dumps(dict(name=name, rel_max=rel_max, rel_l2=l2, tol=tol, finite=True)) + '\n')
+            f.write(json.dumps(dict(name=name, rel_max=rel_max, rel_l2=l2, tol=tol, finite=finite)) + '\n')
     except OSError:
         pass
 
