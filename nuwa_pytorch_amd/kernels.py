@@ -1104,6 +1104,8 @@ def cross2dna_fwd(g, q, kv, null_k, null_v, mask_u8, wth, ctx_rows):
     or None.  Returns o BF [B*ntok, inner] whose rows b*ntok (<bos>) are left for the caller."""
     L = _lib.lib()
     inner = g.heads * g.dim_head
+    # deliberately not written and never read here: row b * ntok (<bos>) of every sample, which the module fills with its own glue
+    # arithmetic (under the NaN-prefill guard of tests/guard_util.py those rows stay NaN: compare rows 1 .. ntok - 1)
     o = empty_bf((g.B * g.ntok, inner), q.hi.device, lo=q.lo is not None)
     k, v = (view(kv, cols=slice(i * inner, (i + 1) * inner)) for i in range(2))
     check(L.amdnuwa_cross2dna_fwd(C.byref(g), _p(q.hi), _p(q.lo), q.hi.stride(0), ctx_rows, _p(k.hi), _p(v.hi), _p(k.lo), _p(v.lo),
@@ -1118,7 +1120,7 @@ def cross2dna_bwd(g, q, kv, null_k, null_v, mask_u8, wth, dO, ctx_rows):
     inner = g.heads * g.dim_head
     dev = q.hi.device
     lo = q.lo is not None
-    dq = empty_bf((g.B * g.ntok, inner), dev, lo=lo)
+    dq = empty_bf((g.B * g.ntok, inner), dev, lo=lo)          # rows b * ntok (<bos>) deliberately unwritten, as in cross2dna_fwd
     dkv = empty_bf((g.B * ctx_rows, 2 * inner), dev, lo=lo)
     dnk = torch.empty(inner, dtype=torch.float32, device=dev)
     dnv = torch.empty(inner, dtype=torch.float32, device=dev)
@@ -1706,6 +1708,7 @@ def xattn_kv_grads(g, dS, Pm, q, dO):
     dev = q.hi.device
     cm = dS.hi.dim() == 5                      # chunk-major dS / Pm (xattn2_bwd)
     Mx = xattn_permuted_extent(g) if cm else dS.hi.shape[-1]      # (xattn2_bwd hands out only the columns that hold a key)
+    # deliberately unwritten and never read (xattn_unpack takes the key rows only): rows Mx .. JP - 1 of both results
     dKp = torch.empty((g.B, g.heads, g.JP, g.dim_head), dtype=torch.float32, device=dev)
     dVp = torch.empty_like(dKp)
     for (A, Bm, out, alpha) in ((dS, q, dKp, g.scale), (Pm, dO, dVp, 1.0)):
