@@ -255,6 +255,25 @@ int amdnuwa_geglu_il_bwd(const uint16_t* u_hi, const uint16_t* u_lo, const uint1
                          uint16_t* du_hi, uint16_t* du_lo, long long R, int FP, amdnuwa_stream stream);
 int amdnuwa_geglu_bwd(const uint16_t* u_hi, const uint16_t* u_lo, const uint16_t* d_hi, const uint16_t* d_lo,
                       uint16_t* du_hi, uint16_t* du_lo, long long R, int FP, amdnuwa_stream stream);
+/* FeedForward dropout (np.py:276: nn.Dropout on the GEGLU output, between the two products), csrc/dropout.hip.
+ * out = keep ? in * scale : 0 over an [R, C] view.  keep: one byte per element (non-zero = kept; a torch.bool tensor) with its own
+ * row pitch ld_keep (bytes); scale = 1 / (1 - p), finite and >= 1.  Two forms:
+ *   in_f16 != 0: `in` holds fp16 values; out_f16 (required, may be `in` itself) receives the fp16 copy -- saturating at +-65504,
+ *                NaN kept -- and `out` the bf16 copy, both rounded from the same fp32 product; in_lo and out_lo must be NULL;
+ *   in_f16 == 0: `in` (+ in_lo, optional) is a bf16 hi[/lo] pair, `out` (+ out_lo, optional) receives the hi[/lo] split of
+ *                amdnuwa_cast_pad; out_f16 must be NULL.
+ * C % 8 == 0; every row pitch (elements; ld_keep in bytes) >= C and a multiple of 8; the 16-bit tensors 16-byte aligned, keep 8-byte
+ * aligned (16-byte accesses of the tensors, 8 mask bytes next to them).  A dropped element is exactly +0 whatever its input. */
+int amdnuwa_geglu_dropout_fwd(const uint16_t* in, const uint16_t* in_lo, int ld_in, int in_f16, const uint8_t* keep, int ld_keep,
+                              float scale, uint16_t* out, uint16_t* out_lo, int ld_out, uint16_t* out_f16, int ld_f16,
+                              long long R, int C, amdnuwa_stream stream);
+/* amdnuwa_geglu_il_bwd with that mask folded in: d_hi[/d_lo] is the UNDROPPED gradient dgg [R, FP] of the dropout's output; the kernel
+ * forms dgd = round(keep ? dgg * scale : 0) in registers -- rounded to bf16 hi, or to the hi + lo pair when the lo parts are given, the
+ * form a separate mask pass would have stored -- and writes du from u (interleaved-by-8) and dgd.  u_lo, d_lo and du_lo: all or none.
+ * FP % 8 == 0; ld_keep (bytes) >= FP and a multiple of 8. */
+int amdnuwa_geglu_il_bwd_dropout(const uint16_t* u_hi, const uint16_t* u_lo, const uint16_t* d_hi, const uint16_t* d_lo,
+                                 const uint8_t* keep, int ld_keep, float scale, uint16_t* du_hi, uint16_t* du_lo,
+                                 long long R, int FP, amdnuwa_stream stream);
 /* dst[r][c<C] = bf16(src[r][c]), zero for C <= c < Cp */
 int amdnuwa_cast_pad(const float* src, int ld_src, uint16_t* hi, uint16_t* lo, int ld_dst, long long R, int C, int Cp,
                      amdnuwa_stream stream);

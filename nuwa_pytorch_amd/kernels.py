@@ -877,6 +877,60 @@ def geglu_bwd(u, dgg, FP, interleaved=False):
     return du
 
 
+_FF_DROP_TORCH = os.environ.get('AMDNUWA_FF_DROP_TORCH', '0') == '1'
+
+
+def set_ff_drop_torch(on):
+    """FeedForward dropout: apply the keep mask with torch element-wise passes in fp32 (the formulation before csrc/dropout.hip) instead of the
+    two mask kernels (A/B switch; the two sides give the same bits)"""
+    global _FF_DROP_TORCH
+    _FF_DROP_TORCH = bool(on)
+
+
+def ff_drop_torch():
+    return _FF_DROP_TORCH
+
+
+def _keep_u8(keep, R, Cc):
+    assert keep.dtype in (torch.bool, torch.uint8) and tuple(keep.shape) == (R, Cc) and keep.stride(1) == 1, 'keep mask: bool [R, C], unit inner stride'
+    _chk_dev(keep)
+    return keep
+
+
+def geglu_dropout_fwd_f16(g16, keep, scale, out16=None):
+    """nn.Dropout on the fp16 gate output g16 [R, C] (np.py:276): (fp16 copy, bf16 copy) of keep ? g16 * scale : 0, both rounded from the same
+    fp32 product.  out16: where the fp16 copy goes (default: in place, over g16)"""
+    R, Cc = g16.shape
+    assert g16.dtype == torch.float16
+    keep = _keep_u8(keep, R, Cc)
+    out16 = g16 if out16 is None else out16
+    ob = torch.empty((R, Cc), dtype=torch.bfloat16, device=g16.device)
+    check(_lib.lib().amdnuwa_geglu_dropout_fwd(_p(g16), None, _ld(g16), 1, _p(keep), keep.stride(0), float(scale), _p(ob), None, _ld(ob),
+                                               _p(out16), _ld(out16), R, Cc, _stream()), 'amdnuwa_geglu_dropout_fwd')
+    return out16, ob
+
+
+def geglu_dropout_fwd(g, keep, scale, lo=None):
+    """nn.Dropout on the gate output g (BF hi[/lo], [R, C]): keep ? value * scale : 0 as a new BF pair (lo: with a lo part; default as g)"""
+    R, Cc = g.hi.shape
+    keep = _keep_u8(keep, R, Cc)
+    out = empty_bf((R, Cc), g.hi.device, lo=(g.lo is not None) if lo is None else lo)
+    check(_lib.lib().amdnuwa_geglu_dropout_fwd(_p(g.hi), _p(g.lo), _ld(g.hi), 0, _p(keep), keep.stride(0), float(scale), _p(out.hi), _p(out.lo),
+                                               _ld(out.hi), None, 0, R, Cc, _stream()), 'amdnuwa_geglu_dropout_fwd')
+    return out
+
+
+def geglu_il_bwd_dropout(u, dgg, keep, scale, FP):
+    """geglu_bwd(u, dropped dgg, FP, interleaved=True) from the UNDROPPED dgg: the mask and its rounding happen in registers"""
+    R = u.hi.shape[0]
+    keep = _keep_u8(keep, R, FP)
+    assert u.hi.is_contiguous() and dgg.hi.is_contiguous() and tuple(dgg.hi.shape) == (R, FP) and tuple(u.hi.shape) == (R, 2 * FP)
+    du = empty_bf((R, 2 * FP), u.hi.device, lo=u.lo is not None)
+    check(_lib.lib().amdnuwa_geglu_il_bwd_dropout(_p(u.hi), _p(u.lo), _p(dgg.hi), _p(dgg.lo), _p(keep), keep.stride(0), float(scale),
+                                                  _p(du.hi), _p(du.lo), R, FP, _stream()), 'amdnuwa_geglu_il_bwd_dropout')
+    return du
+
+
 def geglu_interleave(t, FP, dim=0):
     """[a (FP) | gate (FP)] along `dim` -> the interleaved-by-8 order: 8 values, their 8 gates, the next 8 values, ...
     (FP % 8 == 0).  geglu_deinterleave is the inverse."""

@@ -9,6 +9,7 @@ Scope: decoder stack, embeddings, logits/loss = HIP.  The 
 256 tokens once per step) runs its attention / FeedForward blocks through the same kernels.  NUWAVideoAudio (cfg 5) lives in
 video_audio.py; NUWASketch (row f4) shares the decoder kernels, with SparseCross2DNA and the sketch encoder on PyTorch-ROCm ops.
 """
+import contextlib
 import functools
 from functools import partial
 
@@ -172,7 +173,7 @@ class SandwichNorm(nn.Module):
             shift, fn = -1, fn.fn
             if isinstance(fn, SparseCausal2DNA) and fn._hip_ok():
                 return fn, shift
-        if (isinstance(fn, FeedForward) and not fn._dropout_active()) or (isinstance(fn, Sparse3DNA) and fn._hip_ok()):
+        if isinstance(fn, FeedForward) or (isinstance(fn, Sparse3DNA) and fn._hip_ok()):      # (a FeedForward with live dropout too: its meta carries drop_p)
             return fn, shift
         if isinstance(fn, Attention) and context is not None and fn._hip_ok(context.shape[1]):
             return fn, shift
@@ -211,7 +212,7 @@ class SandwichNorm(nn.Module):
                 nxt_fn = nxt.fn.fn if isinstance(nxt.fn, (ShiftVideoTokens,)) else nxt.fn
                 nxt_kind = None                  # what the next block's first GEMM is (it may want an fp16 copy of its input: ops.SandwichBlockFn)
                 if isinstance(nxt_fn, FeedForward):
-                    nxt_kind = ('ff', nxt_fn.net[3].weight.shape[1], (nxt_fn.net[0].weight, nxt_fn.net[3].weight))
+                    nxt_kind = ('ff', nxt_fn.net[3].weight.shape[1], (nxt_fn.net[0].weight, nxt_fn.net[3].weight), nxt_fn._dropout_active())
                 elif isinstance(nxt_fn, Sparse3DNA) and nxt_fn.causal:
                     nxt_kind = ('s3', nxt_fn.to_q.weight.shape[0], nxt_fn._meta(B, n, x.device)['geom'], (nxt_fn.to_q.weight, nxt_fn.to_kv.weight),
                                 nxt_fn.to_out.weight, nxt_fn.rel_pos_bias is not None)
@@ -327,20 +328,17 @@ class FeedForward(nn.Module):
         return self.training and self.net[2].p > 0
 
     def _meta(self, B, n, device, **_):
-        assert not self._dropout_active()
-        return dict(kind='ff', cache=self._cache)
+        meta = dict(kind='ff', cache=self._cache)
+        if self._dropout_active():
+            meta['drop_p'] = float(self.net[2].p)
+        return meta
 
     def forward(self, x):
         B, n, D = x.shape
-        if self._dropout_active() and x.is_cuda:
-            # ff_dropout > 0 in training (np.py:276): the GEGLU output passes through nn.Dropout.  Both products, the gate and its backward stay on
-            # libamdnuwa (standalone node, bf16 backward; the mask comes from torch's RNG stream and is kept for the backward); the block is not
-            # part of the fused / chained stack (SandwichNorm._inner).  Inside a reversible stack the forward runs twice per step and there is no
-            # RNG replay here (Deterministic): those modules keep the torch-op forward.  Every BASELINE config trains with dropout 0.
-            if getattr(self, '_no_hip_dropout', False):
-                return self.net(x)
-            meta = dict(kind='ff', cache=self._cache, drop_p=float(self.net[2].p))
-            return ops.InnerFn.apply(x, None, meta, *self._params())
+        # ff_dropout > 0 in training (np.py:276): the GEGLU output passes through nn.Dropout (meta['drop_p']).  Both products, the gate, the mask
+        # and their backward run on libamdnuwa (ops.FFInner: mask kernels of csrc/dropout.hip, bf16 backward); the mask comes from torch's RNG
+        # stream (ops._ff_keep_mask) and is kept for the backward.  The same inner stage serves this standalone node, the fused / chained block
+        # of the plain stacks and the blocks of the reversible stacks, whose recomputing backward replays the RNG state of the forward (RngReplay).
         return ops.InnerFn.apply(x, None, self._meta(B, n, x.device), *self._params())
 
 
@@ -774,8 +772,9 @@ def route_args(router, args, depth):
 
 
 class Deterministic(nn.Module):
-    """rev.py:20-50: keeps the `.net` level of the state-dict key hierarchy.  No dropout on this path,
-    so there is no RNG to record/replay."""
+    """rev.py:20-50: keeps the `.net` level of the state-dict key hierarchy.  The RNG record / replay of the reference's class lives in
+    RngReplay below: the recorded states belong to one forward of the stack, so they are kept on its autograd node, not on this module
+    (two forwards in flight would overwrite each other's)."""
 
     def __init__(self, net):
         super().__init__()
@@ -783,6 +782,49 @@ class Deterministic(nn.Module):
 
     def forward(self, *args, **kwargs):
         return self.net(*args, **kwargs)
+
+
+class RngReplay:
+    """The RNG states a sub-block of a reversible stack saw in the forward, for its recomputation in the backward (the role of
+    rev.py:27-50): `record(device)` captures the CPU generator's state and the HIP generator's of that device; `replay()` forks both
+    (torch.random.fork_rng), sets the recorded states and restores the live ones on exit -- the recomputed sub-block draws the dropout
+    masks of the forward and the main stream comes out of the backward where it went in."""
+
+    __slots__ = ('index', 'cpu_state', 'dev_state')
+
+    @classmethod
+    def record(cls, device=None):
+        self = cls()
+        device = torch.device('cpu') if device is None else torch.device(device)
+        self.cpu_state = torch.get_rng_state()
+        self.index = self.dev_state = None
+        if device.type == 'cuda':
+            self.index = device.index if device.index is not None else torch.cuda.current_device()
+            self.dev_state = torch.cuda.get_rng_state(self.index)
+        return self
+
+    @contextlib.contextmanager
+    def replay(self):
+        with torch.random.fork_rng(devices=[] if self.index is None else [self.index]):
+            torch.set_rng_state(self.cpu_state)
+            if self.index is not None:
+                torch.cuda.set_rng_state(self.dev_state, self.index)
+            yield
+
+
+def draws_dropout(module):
+    """does a call of `module` draw a dropout mask now: does it hold an nn.Dropout with p > 0 in training mode?"""
+    return module.training and any(isinstance(m, nn.Dropout) and m.p > 0 and m.training for m in module.modules())
+
+
+def rng_record(module, x, on=True):
+    """the RngReplay for one forward call of a reversible sub-block, or None when the call draws nothing (dropout 0, eval) or nobody asked
+    (`on`): then nothing is recorded, forked or set"""
+    return RngReplay.record(x.device) if on and draws_dropout(module) else None
+
+
+def rng_replay(rec):
+    return contextlib.nullcontext() if rec is None else rec.replay()
 
 
 class ReversibleBlock(nn.Module):
@@ -793,28 +835,35 @@ class ReversibleBlock(nn.Module):
         self.f = Deterministic(f)
         self.g = Deterministic(g)
 
-    def forward(self, x1, x2, f_args={}, g_args={}):
+    def forward(self, x1, x2, f_args={}, g_args={}, rng=None):
+        """rng: a list (the recomputing stack's: _ReversibleStackFn) that receives this block's (RngReplay or None for f, for g)"""
         f, g = self.f.net, self.g.net
+        rec_f = rng_record(f, x2, rng is not None)
         if isinstance(f, SandwichNorm) and x1.is_cuda and f._inner(f_args.get('context'), seq_len=x2.shape[1], batch=x2.shape[0]) is not None:
             y1 = f.fused_residual(x2, resid=x1, **{k: f_args.get(k) for k in ('context', 'context_mask', 'mask', 'rotary_pos_emb')})
         else:
             y1 = x1 + f(x2, **f_args)
+        rec_g = rng_record(g, y1, rng is not None)
         if isinstance(g, SandwichNorm) and g._inner() is not None and x1.is_cuda:
             y2 = g.fused_residual(y1, resid=x2)
         else:
             y2 = x2 + g(y1, **g_args)
+        if rng is not None:
+            rng.append((rec_f, rec_g))
         return y1, y2
 
-    def backward_pass(self, y1, y2, dy1, dy2, f_args={}, g_args={}):
+    def backward_pass(self, y1, y2, dy1, dy2, f_args={}, g_args={}, rng=(None, None)):
         """inputs and input-gradients of this block from its outputs and output-gradients (the role of rev.py:77-106);
-        parameter gradients of f and g are accumulated by the two inner autograd calls"""
+        parameter gradients of f and g are accumulated by the two inner autograd calls.  rng = the block's entry of the forward's list:
+        f and g are recomputed under the RNG states their forward calls saw"""
         f, g = self.f.net, self.g.net
+        rec_f, rec_g = rng
         fuse_f = isinstance(f, SandwichNorm) and y1.is_cuda and f._inner(f_args.get('context'), seq_len=y1.shape[1], batch=y1.shape[0]) is not None
         fuse_g = isinstance(g, SandwichNorm) and g._inner() is not None and y1.is_cuda
         # g(y1) again.  Fused form: one node whose value is y2 - g(y1) = x2 (the post-norm kernel subtracts: no negation passes over the
         # stream -- four of them per block, 6 % of the cfg-4 step, in the (-y2) + g(y1) = -x2 form of rounds 2-4; the same bits) and whose
         # gradient w.r.t. y1 and g's parameters is g's.
-        with torch.enable_grad():
+        with torch.enable_grad(), rng_replay(rec_g):
             y1g = y1.detach().requires_grad_(True)
             if fuse_g:
                 x2n = g.fused_residual(y1g, resid=y2, minus=True)
@@ -826,7 +875,7 @@ class ReversibleBlock(nn.Module):
         with torch.no_grad():
             x2 = x2n.detach() if fuse_g else y2 - gy1.detach()
             dx1 = y1g.grad if fuse_g else dy1 + y1g.grad
-        with torch.enable_grad():
+        with torch.enable_grad(), rng_replay(rec_f):
             x2g = x2.detach().requires_grad_(True)
             if fuse_f:
                 x1n = f.fused_residual(x2g, resid=y1, minus=True, **{k: f_args.get(k) for k in ('context', 'context_mask', 'mask', 'rotary_pos_emb')})
@@ -854,9 +903,10 @@ class _ReversibleStackFn(torch.autograd.Function):
         x1 = x2 = x.detach()
         cdet = context.detach() if context is not None else None
         args = [tuple({k: (cdet if k == 'context' else v) for k, v in a.items()} for a in pair) for pair in args]
+        rng = []                 # per block the RNG states its f / g calls saw (None where no dropout mask is drawn): kept on THIS node
         for block, (f_args, g_args) in zip(seq.blocks, args):
-            x1, x2 = block(x1, x2, f_args=f_args, g_args=g_args)
-        ctx.seq, ctx.args, ctx.cdet = seq, args, cdet
+            x1, x2 = block(x1, x2, f_args=f_args, g_args=g_args, rng=rng)
+        ctx.seq, ctx.args, ctx.cdet, ctx.rng = seq, args, cdet, rng
         ctx.save_for_backward(x1, x2)
         return x1 + x2
 
@@ -865,13 +915,13 @@ class _ReversibleStackFn(torch.autograd.Function):
         y1, y2 = ctx.saved_tensors
         dy1 = dy2 = dy
         dctx = None
-        for block, (f_args, g_args) in reversed(list(zip(ctx.seq.blocks, ctx.args))):
+        for block, (f_args, g_args), rng in reversed(list(zip(ctx.seq.blocks, ctx.args, ctx.rng))):
             leaf = None
             if ctx.cdet is not None and ('context' in f_args or 'context' in g_args):
                 leaf = ctx.cdet.detach().requires_grad_(True)
                 f_args = {k: (leaf if k == 'context' else v) for k, v in f_args.items()}
                 g_args = {k: (leaf if k == 'context' else v) for k, v in g_args.items()}
-            y1, y2, dy1, dy2 = block.backward_pass(y1, y2, dy1, dy2, f_args=f_args, g_args=g_args)
+            y1, y2, dy1, dy2 = block.backward_pass(y1, y2, dy1, dy2, f_args=f_args, g_args=g_args, rng=rng)
             if leaf is not None and leaf.grad is not None:
                 dctx = leaf.grad if dctx is None else dctx + leaf.grad
         return dy1 + dy2, dctx, None, None
@@ -947,9 +997,6 @@ class ReversibleTransformer(nn.Module):
         attn_route_map = {'mask': route_attn, 'rotary_pos_emb': route_attn}
         self.net = ReversibleSequence(self.layers, args_route={**context_route_map, **attn_route_map})
         self.norm = StableLayerNorm(dim)
-        for m in self.modules():                 # a reversible block's forward runs twice per step without RNG replay: no kept dropout mask here
-            if isinstance(m, FeedForward):
-                m._no_hip_dropout = True
 
     def forward_layers(self, x, **kwargs):
         return self.net(x, **kwargs)

@@ -575,12 +575,19 @@ class FFInner:
                 y = K.gemm_nt_f16ops(gg16, W['w2_16'])
                 return y, (K.BF(None, None, h16), K.BF(u, None), K.BF(None, None, gg16))
             assert h.hi is not None, 'a bf16 backward needs the bf16 copy of the LayerNorm output'
-            u, gg16, ggb = K.gemm_nt_f16ops(h16, W['w1_16'], out_bf16=True, gate=True)
             if drop_p:          # ff_dropout > 0 in training (np.py:276): nn.Dropout on the GEGLU output, between the two products
-                keep = _ff_keep_mask(R, W['FP'], drop_p, gg16.device)
-                gf = _ff_drop(gg16.float(), keep, drop_p)
-                gg16, ggb = gf.to(torch.float16), gf.to(torch.bfloat16)
+                keep = _ff_keep_mask(R, W['FP'], drop_p, h16.device)
+                if K.ff_drop_torch():        # (A/B switch: the torch element-wise formulation, the same bits)
+                    u, gg16, ggb = K.gemm_nt_f16ops(h16, W['w1_16'], out_bf16=True, gate=True)
+                    gf = _ff_drop(gg16.float(), keep, drop_p)
+                    gg16, ggb = gf.to(torch.float16), gf.to(torch.bfloat16)
+                else:
+                    # one mask kernel: the dropped fp16 copy in place and the dropped bf16 copy from the same fp32 product (the GEMM's own --
+                    # undropped -- bf16 copy of the gate output would have no reader: not written)
+                    u, gg16, _ = K.gemm_nt_f16ops(h16, W['w1_16'], out_bf16=True, gate=True, gate_bf16=False)
+                    gg16, ggb = K.geglu_dropout_fwd_f16(gg16, keep, 1.0 / (1.0 - drop_p))
                 return K.gemm_nt_f16ops(gg16, W['w2_16']), (K.BF(h.hi, None), K.BF(u, None), K.BF(ggb, None), keep)
+            u, gg16, ggb = K.gemm_nt_f16ops(h16, W['w1_16'], out_bf16=True, gate=True)
             y = K.gemm_nt_f16ops(gg16, W['w2_16'])
             return y, (K.BF(h.hi, None), K.BF(u, None), K.BF(ggb, None))
         h = _f16_to_pair(h)
@@ -588,8 +595,11 @@ class FFInner:
         u = K.gemm_nt(h, W['w1'], out_bf16=True, shift=meta.get('shift'), geglu_out=gg)   # u (interleaved layout) and a * gelu(gate)
         if drop_p:
             keep = _ff_keep_mask(R, W['FP'], drop_p, h.hi.device)
-            ggd = K.empty_bf((h.hi.shape[0], W['FP']), h.hi.device)
-            K.cast_pad(_ff_drop(_bf_val(gg), keep, drop_p).contiguous(), ggd)
+            if K.ff_drop_torch():
+                ggd = K.empty_bf((h.hi.shape[0], W['FP']), h.hi.device)
+                K.cast_pad(_ff_drop(_bf_val(gg), keep, drop_p).contiguous(), ggd)
+            else:
+                ggd = K.geglu_dropout_fwd(gg, keep, 1.0 / (1.0 - drop_p))
             return K.gemm_nt(ggd, W['w2'], out_bf16=_fast()), (*_sv(h, u, ggd), keep)
         y = K.gemm_nt(gg, W['w2'], out_bf16=_fast())
         return y, _sv(h, u, gg)
@@ -615,9 +625,12 @@ class FFInner:
         if keep is not None:
             assert not isinstance(dy, K.G16)
             dgg = K.gemm_nt(dy, W['w2T'], out_bf16=True)
-            dgd = K.empty_bf(tuple(dgg.hi.shape), dgg.hi.device)
-            K.cast_pad(_ff_drop(_bf_val(dgg), keep, float(meta['drop_p'])).contiguous(), dgd)
-            du = K.geglu_bwd(u, dgd, FP, interleaved=True)
+            if K.ff_drop_torch():
+                dgd = K.empty_bf(tuple(dgg.hi.shape), dgg.hi.device)
+                K.cast_pad(_ff_drop(_bf_val(dgg), keep, float(meta['drop_p'])).contiguous(), dgd)
+                du = K.geglu_bwd(u, dgd, FP, interleaved=True)
+            else:               # the mask, its rounding and the gate's backward in one pass over u and the undropped dgg
+                du = K.geglu_il_bwd_dropout(u, dgg, keep, 1.0 / (1.0 - float(meta['drop_p'])), FP)
         elif FUSE_GEGLU_BWD:
             du = K.gemm_nt_geglu_bwd(dy, W['w2T'], u, FP)      # dgg = dy W2 and the gate's backward in one pass
         else:
@@ -908,7 +921,7 @@ class SandwichBlockFn(Function):
             nxt16 = nk is not None and ((nk[0] == 'ff' and FFInner.f16_ok(B * n, D, _ru(nk[1], 32), nk[2])) or
                                         (nk[0] == 's3' and S3Inner.f16_proj_ok(B * n, D, nk[1], nk[2], nk[3])) or
                                         (nk[0] == 'x' and XInner.f16x2_ok(B * n, D, nk[1], nk[2], nk[3], nk[4])))
-            if nxt16 and ((nk[0] == 'ff' and FFInner.bwd16_ok(B * n, D, _ru(nk[1], 32), nk[1], nk[2])) or
+            if nxt16 and ((nk[0] == 'ff' and not (len(nk) > 3 and nk[3]) and FFInner.bwd16_ok(B * n, D, _ru(nk[1], 32), nk[1], nk[2])) or     # (nk[3]: live dropout -> bf16 backward)
                           (nk[0] == 's3' and len(nk) > 5 and S3Inner.bwd16_ok(B * n, D, nk[1], nk[2], nk[3], nk[4], nk[5])) or
                           (nk[0] == 'x' and XInner.bwd16_ok(B * n, D, nk[1], nk[2], nk[3], nk[4]))):
                 nxt16 = 'only'                    # the next block keeps ONE (fp16) copy of its LayerNorm input: fp16-gradient backward

@@ -22,7 +22,7 @@ from torch import nn, einsum
 from . import ops
 from .nuwa_pytorch import (MList, exists, default, eval_decorator, bernoulli_rows, SandwichNorm, ShiftVideoTokens, FeedForward, Deterministic,
                            Attention, Sparse3DNA, StableLayerNorm, Transformer, ReversibleTransformer, Embedding,
-                           AxialPositionalEmbedding, RotaryEmbedding)
+                           AxialPositionalEmbedding, RotaryEmbedding, rng_record, rng_replay)
 
 NEG = -torch.finfo(torch.float32).max
 
@@ -309,29 +309,49 @@ class DualReversibleBlock(nn.Module):
         self.kind = kind
         self.f, self.g, self.j, self.k = (Deterministic(t) for t in (f, g, j, k))
 
-    def forward(self, x1, x2, m1, m2, *, context, context_mask, video_mask=None, audio_mask=None):
+    def forward(self, x1, x2, m1, m2, *, context, context_mask, video_mask=None, audio_mask=None, rng=None):
+        """rng: a list (the recomputing stack's: _DualReversibleStackFn) that receives this block's {'f', 'g', 'j', 'k'} -> RngReplay or None,
+        each recorded right before that sub-block's call"""
         f, g, j, k = self.f.net, self.g.net, self.j.net, self.k.net
+        rec = {}
+        on = rng is not None
         if self.kind == 'intra_modality_self_attn':
+            rec['f'] = rng_record(f, x2, on)
             y1 = _residual_to(f, x2, x1, mask=video_mask)
+            rec['g'] = rng_record(g, y1, on)
             y2 = _residual_to(g, y1, x2)
+            rec['j'] = rng_record(j, m2, on)
             n1 = _residual_to(j, m2, m1, mask=audio_mask)
+            rec['k'] = rng_record(k, n1, on)
             n2 = _residual_to(k, n1, m2)
         elif self.kind == 'intra_modality_cross_attn':
+            rec['f'] = rng_record(f, x2, on)
             y1 = _residual_to(f, x2, x1, context=context, context_mask=context_mask, mask=video_mask)
+            rec['g'] = rng_record(g, y1, on)
             y2 = _residual_to(g, y1, x2)
+            rec['j'] = rng_record(j, m2, on)
             n1 = _residual_to(j, m2, m1, context=context, context_mask=context_mask, mask=audio_mask)
+            rec['k'] = rng_record(k, n1, on)
             n2 = _residual_to(k, n1, m2)
         else:
+            rec['f'] = rng_record(f, x2, on)
             y1 = x1 + f(x2, m2, mask=video_mask, context_mask=audio_mask)
+            rec['k'] = rng_record(k, y1, on)
             y2 = _residual_to(k, y1, x2)
+            rec['j'] = rng_record(j, m2, on)
             n1 = m1 + j(m2, y2, mask=audio_mask, context_mask=video_mask)       # the audio side sees the UPDATED video half
+            rec['g'] = rng_record(g, n1, on)
             n2 = _residual_to(g, n1, m2)
+        if on:
+            rng.append(rec)
         return y1, y2, n1, n2
 
-    def backward_pass(self, y1, y2, n1, n2, dy1, dy2, dn1, dn2, *, context, context_mask, video_mask=None, audio_mask=None):
+    def backward_pass(self, y1, y2, n1, n2, dy1, dy2, dn1, dn2, *, context, context_mask, video_mask=None, audio_mask=None, rng=None):
         """inputs and input-gradients of this block from its outputs and output-gradients; parameter (and text-context) gradients
-        accumulate through the inner autograd calls"""
+        accumulate through the inner autograd calls.  rng = the block's entry of the forward's list: every sub-block is recomputed under
+        the RNG state its forward call saw"""
         f, g, j, k = self.f.net, self.g.net, self.j.net, self.k.net
+        rng = rng or {}
         leaf = lambda t: t.detach().requires_grad_(True)
         gr = lambda t: t.grad if t.grad is not None else torch.zeros_like(t)      # (a sub-block may ignore an input, e.g. no context frame yet)
         if self.kind != 'inter_modality_cross_attn':
@@ -339,39 +359,40 @@ class DualReversibleBlock(nn.Module):
             # video halves: y2 = x2 + g(y1), y1 = x1 + f(x2)
             # (add = the gradient the step's input gradient is summed with: on the fused node it rides in as the pre-norm backward's accumulator)
             y1g = leaf(y1)
-            x2, dx1 = _rev_step(g, y1g, y2, dy2, add=dy1)
+            x2, dx1 = _rev_step(g, y1g, y2, dy2, add=dy1, rng=rng.get('g'))
             x2g = leaf(x2)
-            x1, dx2 = _rev_step(f, x2g, y1, dx1, add=dy2, mask=video_mask, **ckw)
+            x1, dx2 = _rev_step(f, x2g, y1, dx1, add=dy2, rng=rng.get('f'), mask=video_mask, **ckw)
             # audio halves: n2 = m2 + k(n1), n1 = m1 + j(m2)
             n1g = leaf(n1)
-            m2, dm1 = _rev_step(k, n1g, n2, dn2, add=dn1)
+            m2, dm1 = _rev_step(k, n1g, n2, dn2, add=dn1, rng=rng.get('k'))
             m2g = leaf(m2)
-            m1, dm2 = _rev_step(j, m2g, n1, dm1, add=dn2, mask=audio_mask, **ckw)
+            m1, dm2 = _rev_step(j, m2g, n1, dm1, add=dn2, rng=rng.get('j'), mask=audio_mask, **ckw)
             return x1, x2, m1, m2, dx1, dx2, dm1, dm2
         # cross-modality block: y1 = x1 + f(x2, m2); y2 = x2 + k(y1); n1 = m1 + j(m2, y2); n2 = m2 + g(n1)
         n1g = leaf(n1)
-        m2, dm1 = _rev_step(g, n1g, n2, dn2, add=dn1)
+        m2, dm1 = _rev_step(g, n1g, n2, dn2, add=dn1, rng=rng.get('g'))
         m2g, y2g = leaf(m2), leaf(y2)
-        m1 = _rev_step(j, m2g, n1, dm1, extra=(y2g,), mask=audio_mask, context_mask=video_mask)
+        m1 = _rev_step(j, m2g, n1, dm1, extra=(y2g,), rng=rng.get('j'), mask=audio_mask, context_mask=video_mask)
         dm2 = dn2 + gr(m2g)
         dy2t = dy2 + gr(y2g)                              # the audio side looked at the updated video half
         y1g = leaf(y1)
-        x2, dx1 = _rev_step(k, y1g, y2, dy2t, add=dy1)
+        x2, dx1 = _rev_step(k, y1g, y2, dy2t, add=dy1, rng=rng.get('k'))
         x2g, m2h = leaf(x2), leaf(m2)
-        x1 = _rev_step(f, x2g, y1, dx1, extra=(m2h,), mask=video_mask, context_mask=audio_mask)
+        x1 = _rev_step(f, x2g, y1, dx1, extra=(m2h,), rng=rng.get('f'), mask=video_mask, context_mask=audio_mask)
         dx2 = dy2t + gr(x2g)
         dm2 = dm2 + gr(m2h)
         return x1, x2, m1, m2, dx1, dx2, dm1, dm2
 
 
-def _rev_step(block, xg, y, dy, extra=(), add=None, **kw):
+def _rev_step(block, xg, y, dy, extra=(), add=None, rng=None, **kw):
     """One reversal step of a reversible half: y = x_prev + block(xg, *extra, **kw).  Returns x_prev (no graph) after
     back-propagating dy through a freshly recomputed block: gradients land in xg.grad, in the .grad of any `extra` / `context`
     leaf, and accumulate into the block's parameters (the role of reversible_video_audio.py:246-327).  add: also returns add + xg.grad.
     On the fused libamdnuwa
-    node the recomputation and the subtraction are one pass: the node's value is y - block(xg) = x_prev (`minus`)."""
+    node the recomputation and the subtraction are one pass: the node's value is y - block(xg) = x_prev (`minus`).
+    rng: the RngReplay of the block's forward call (None: it drew no dropout mask) -- the recomputation runs under it."""
     inner_kw = {a: b for a, b in kw.items() if a in ('context', 'context_mask')}
-    with torch.enable_grad():
+    with torch.enable_grad(), rng_replay(rng):
         if not extra and isinstance(block, SandwichNorm) and xg.is_cuda and block._inner(inner_kw.get('context')) is not None:
             xp = block.fused_residual(xg, resid=y, minus=True, **inner_kw)
             if add is not None:
@@ -405,9 +426,10 @@ class _DualReversibleStackFn(torch.autograd.Function):
         x1 = x2 = video.detach()
         m1 = m2 = audio.detach()
         cdet = context.detach() if context is not None else None
+        rng = []                 # per block the RNG states its sub-block calls saw (None where no dropout mask is drawn): kept on THIS node
         for block in seq.blocks:
-            x1, x2, m1, m2 = block(x1, x2, m1, m2, context=cdet, **kw)
-        ctx.seq, ctx.kw, ctx.cdet = seq, kw, cdet
+            x1, x2, m1, m2 = block(x1, x2, m1, m2, context=cdet, rng=rng, **kw)
+        ctx.seq, ctx.kw, ctx.cdet, ctx.rng = seq, kw, cdet, rng
         ctx.save_for_backward(x1, x2, m1, m2)
         return (x1 + x2) * 0.5, (m1 + m2) * 0.5
 
@@ -417,9 +439,9 @@ class _DualReversibleStackFn(torch.autograd.Function):
         dy1 = dy2 = dv * 0.5
         dn1 = dn2 = da * 0.5
         dctx = None
-        for block in reversed(list(ctx.seq.blocks)):
+        for block, rng in reversed(list(zip(ctx.seq.blocks, ctx.rng))):
             leaf = ctx.cdet.detach().requires_grad_(True) if (ctx.cdet is not None and block.kind == 'intra_modality_cross_attn') else None
-            y1, y2, n1, n2, dy1, dy2, dn1, dn2 = block.backward_pass(y1, y2, n1, n2, dy1, dy2, dn1, dn2, context=leaf, **ctx.kw)
+            y1, y2, n1, n2, dy1, dy2, dn1, dn2 = block.backward_pass(y1, y2, n1, n2, dy1, dy2, dn1, dn2, context=leaf, rng=rng, **ctx.kw)
             if leaf is not None and leaf.grad is not None:
                 dctx = leaf.grad if dctx is None else dctx + leaf.grad
         return dy1 + dy2, dn1 + dn2, dctx, None, None
@@ -496,9 +518,6 @@ class ReversibleDualModalityDecoder(nn.Module):
         self.net = DualModalityReversibleSequence(self.layers, self.layer_types)
         self.video_norm = StableLayerNorm(dim)
         self.audio_norm = StableLayerNorm(dim)
-        for m in self.modules():                 # (see ReversibleTransformer: no kept dropout mask where the forward is recomputed)
-            if isinstance(m, FeedForward):
-                m._no_hip_dropout = True
 
     def forward_layers(self, video, audio, *, context, audio_mask=None, video_mask=None, context_mask=None, **kwargs):
         return self.net(video, audio, context=context, audio_mask=audio_mask, video_mask=video_mask, context_mask=context_mask)
