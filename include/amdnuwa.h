@@ -37,7 +37,8 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 *     ab_f16 on the whole-M TN kernel with alpha_dev in its direct epilogue, c_f16 on the two-MFMA NT product;
                                                 * 20: the amdnuwa_cattn_* family, 21: amdnuwa_cattn_geom.n_keys; ABI 21 also accepts token grids of up to 64 columns in the
                                                 *     window kernels -- amdnuwa_s3_geom / amdnuwa_s3_supported below: a wider accepted range, no signature or struct change;
-                                                *     amdnuwa_attn_decode_rows and its _workspace_bytes were added at 21 as well: purely additive) */
+                                                *     amdnuwa_attn_decode_rows and its _workspace_bytes were added at 21 as well: purely additive; so were amdnuwa_prefill_ln and
+                                                *     amdnuwa_prefill_kv, the cache prefill of a sliding generate() window) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -423,6 +424,23 @@ int amdnuwa_decode_ln(const void* y, int y_is_bf16, const float* resid, const fl
 int amdnuwa_s3_decode(const amdnuwa_s3_geom* g, const uint16_t* qkv, const uint16_t* qkv_lo, uint16_t* kv_cache,
                       uint16_t* kv_cache_lo, int cache_rows, const int* pos, const float* w_th, uint16_t* o,
                       uint16_t* o_lo, amdnuwa_stream stream);
+/* Cache prefill (added at ABI 21, purely additive): what R successive single-row calls at pos = 0 .. R-1 leave behind, for R rows per
+ * sample at once -- the pass NUWA.generate runs when its frame window slides (np.py:1873-1881): every kept token moves one frame earlier,
+ * so every cached row changes.  Rows are sample-major: row = sample * R + i.
+ * amdnuwa_prefill_ln is amdnuwa_decode_ln without `pos`: y / resid / x_new / out are [B*R, D]; with cache_hi != NULL exactly rows [0, R) of
+ * cache [B, cache_rows, D] (R <= cache_rows) become h and out = shift(h) (fmap as in amdnuwa_decode_ln), else out = h.  Per row the arithmetic
+ * and its order are those of amdnuwa_decode_ln: x_new, the cache rows and out are BIT-IDENTICAL to the R single-row calls.  The shift of row i
+ * reads the h of rows i - 1 and i - fmap, which other workgroups write: the entry point runs two stream-ordered launches (norms + cache
+ * write, then the gather); no atomics, two runs are bit-identical.  AMDNUWA_ERR_ARG: a null or non-positive argument, R > cache_rows;
+ * AMDNUWA_ERR_UNSUPPORTED: D % 16 != 0 or D > 4096. */
+int amdnuwa_prefill_ln(const void* y, int y_is_bf16, const float* resid, const float* w, const float* b, const float* next_w,
+                       const float* next_b, float* x_new, uint16_t* cache_hi, uint16_t* cache_lo, uint16_t* out_hi,
+                       uint16_t* out_lo, int B, int R, int cache_rows, int D, int fmap, float eps, amdnuwa_stream stream);
+/* amdnuwa_prefill_kv copies the k | v columns of qkv [B*R, 3*inner] (bf16 hi, lo image optional: NULL on both sides or on neither) into
+ * rows [0, R) of kv_cache [B, cache_rows, 2*inner], the layout amdnuwa_s3_decode keeps; 16-byte vectors, inner % 8 == 0
+ * (AMDNUWA_ERR_UNSUPPORTED otherwise).  AMDNUWA_ERR_ARG: a null or non-positive argument, R > cache_rows. */
+int amdnuwa_prefill_kv(const uint16_t* qkv, const uint16_t* qkv_lo, uint16_t* kv_cache, uint16_t* kv_cache_lo, int B, int R,
+                       int cache_rows, int inner, amdnuwa_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Text cross-attention core (Attention.forward with context, np.py:339-378): learned null key/value

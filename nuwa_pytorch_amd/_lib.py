@@ -118,6 +118,8 @@ SIGNATURES = {
     'amdnuwa_decode_shift': (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     'amdnuwa_decode_ln': (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, P]),
     'amdnuwa_s3_decode': (I, [SG, P, P, P, P, I, P, P, P, P, P]),
+    'amdnuwa_prefill_ln': (I, [P, I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P]),
+    'amdnuwa_prefill_kv': (I, [P, P, P, P, I, I, I, I, P]),
     'amdnuwa_xattn_decode': (I, [XG, P, P, I, XK, P, P, P, I, P]),
     'amdnuwa_attn_decode_rows_workspace_bytes': (SZ, [I, I, I, I]),
     'amdnuwa_attn_decode_rows': (I, [I, I, I, I, F, P, P, I, P, P, I, P, P, P, P, P, P, P, P, I, P, SZ, P]),

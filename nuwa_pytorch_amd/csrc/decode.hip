@@ -6,6 +6,10 @@
 //   * decode_shift_kernel : caches the new pre-norm row and emits its token-shifted form
 //   * s3_decode_kernel    : caches the new key / value row and runs the 3DNA attention of the single new query
 // The position is read from DEVICE memory so that one captured HIP graph serves every token of the sequence.
+// Past max_video_frames generate() slides its frame window (np.py:1873-1881): every kept token moves one frame earlier and every cached row
+// changes.  The caches are then rebuilt by one full-sequence pass whose norms / shift / cache writes are the ROWS forms of the kernels above:
+//   * prefill_ln_kernel + prefill_shift_kernel : decode_ln_kernel for rows 0 .. R-1 of every sample at once, bit-identical to it
+//   * prefill_kv_kernel                        : the k | v columns of R projected rows into the 3DNA cache
 #include "common.h"
 #include "../../include/amdnuwa.h"
 
@@ -564,6 +568,155 @@ __global__ __launch_bounds__(256) void rows_reduce_kernel(RowsArgs a) {
     }
 }
 
+// ---- cache prefill: the norms, the token shift and the key / value rows of R rows per sample at once --------------------------
+// When generate() slides its frame window every kept token moves one frame earlier, so every cached row changes.  The kept rows are
+// recomputed in ONE full-sequence pass; these kernels leave the caches exactly as R single-row steps at pos = 0 .. R-1 would have.
+//
+// prefill_ln_kernel is decode_ln_kernel for row (sample, i) = (blockIdx.x / R, blockIdx.x % R): the same loads, the same expression
+// trees and the same block reduction, so every value is bit-identical to the row step's.  It writes h to the cache row AND to out
+// un-shifted; the shifted channel quarters of out are other rows' h, which other workgroups of this launch write -- they are gathered
+// by prefill_shift_kernel in a second, stream-ordered launch.
+template <bool YBF>
+__global__ __launch_bounds__(256) void prefill_ln_kernel(const void* __restrict__ y_, const float* __restrict__ resid,
+                                                         const float* __restrict__ w, const float* __restrict__ b,
+                                                         const float* __restrict__ w2, const float* __restrict__ b2,
+                                                         float* __restrict__ x_new, bf16_t* __restrict__ c_hi,
+                                                         bf16_t* __restrict__ c_lo, bf16_t* __restrict__ o_hi,
+                                                         bf16_t* __restrict__ o_lo, int R, int cache_rows, int D, float eps) {
+    __shared__ float red[8];
+    constexpr int MAXI = 4;                         // 4 x 256 threads x 4 elements = 4096
+    const int bidx = blockIdx.x, tid = threadIdx.x;
+    const size_t row = (size_t)bidx * D;
+    float4 v[MAXI];
+    float s = 0.f;
+#pragma unroll
+    for (int it = 0; it < MAXI; ++it) {
+        const int e = (tid + it * 256) * 4;
+        v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (e < D) {
+            if (YBF) {
+                const uint2 u = *reinterpret_cast<const uint2*>((const bf16_t*)y_ + row + e);
+                v[it] = make_float4(lo_f(u.x), hi_f(u.x), lo_f(u.y), hi_f(u.y));
+            } else {
+                v[it] = *reinterpret_cast<const float4*>((const float*)y_ + row + e);
+            }
+            s += (v[it].x + v[it].y) + (v[it].z + v[it].w);
+        }
+    }
+    if (resid) {
+        const float mean = block_sum(s, red) / D;
+        float q = 0.f;
+#pragma unroll
+        for (int it = 0; it < MAXI; ++it) {
+            const int e = (tid + it * 256) * 4;
+            if (e < D) {
+                const float a = v[it].x - mean, b_ = v[it].y - mean, c = v[it].z - mean, d = v[it].w - mean;
+                q += (a * a + b_ * b_) + (c * c + d * d);
+            }
+        }
+        const float rstd = rsqrtf(block_sum(q, red) / D + eps);
+        s = 0.f;
+#pragma unroll
+        for (int it = 0; it < MAXI; ++it) {
+            const int e = (tid + it * 256) * 4;
+            if (e < D) {
+                const float4 wv = *reinterpret_cast<const float4*>(w + e), bv = *reinterpret_cast<const float4*>(b + e);
+                const float4 rv = *reinterpret_cast<const float4*>(resid + row + e);
+                v[it] = make_float4(rv.x + ((v[it].x - mean) * rstd * wv.x + bv.x), rv.y + ((v[it].y - mean) * rstd * wv.y + bv.y),
+                                    rv.z + ((v[it].z - mean) * rstd * wv.z + bv.z), rv.w + ((v[it].w - mean) * rstd * wv.w + bv.w));
+                *reinterpret_cast<float4*>(x_new + row + e) = v[it];
+                s += (v[it].x + v[it].y) + (v[it].z + v[it].w);
+            }
+        }
+    }
+    if (!w2) return;                                 // last block of the stack: no next pre-norm
+    const float mean2 = block_sum(s, red) / D;
+    float q2 = 0.f;
+#pragma unroll
+    for (int it = 0; it < MAXI; ++it) {
+        const int e = (tid + it * 256) * 4;
+        if (e < D) {
+            const float a = v[it].x - mean2, b_ = v[it].y - mean2, c = v[it].z - mean2, d = v[it].w - mean2;
+            q2 += (a * a + b_ * b_) + (c * c + d * d);
+        }
+    }
+    const float rstd2 = rsqrtf(block_sum(q2, red) / D + eps);
+    const size_t crow = ((size_t)(bidx / R) * cache_rows + bidx % R) * D;
+#pragma unroll
+    for (int it = 0; it < MAXI; ++it) {
+        const int e = (tid + it * 256) * 4;
+        if (e >= D) continue;
+        const float4 wv = *reinterpret_cast<const float4*>(w2 + e), bv = *reinterpret_cast<const float4*>(b2 + e);
+        const float h[4] = {(v[it].x - mean2) * rstd2 * wv.x + bv.x, (v[it].y - mean2) * rstd2 * wv.y + bv.y,
+                            (v[it].z - mean2) * rstd2 * wv.z + bv.z, (v[it].w - mean2) * rstd2 * wv.w + bv.w};
+        bf16_t hh[4], hl[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (o_lo) f2bf_hilo(h[i], hh[i], hl[i]);
+            else { hh[i] = f2bf(h[i]); hl[i] = 0; }
+        }
+        const uint2 oh = make_uint2(pack2(hh[0], hh[1]), pack2(hh[2], hh[3])), ol = make_uint2(pack2(hl[0], hl[1]), pack2(hl[2], hl[3]));
+        if (c_hi) {
+            *reinterpret_cast<uint2*>(c_hi + crow + e) = oh;
+            if (c_lo) *reinterpret_cast<uint2*>(c_lo + crow + e) = ol;
+        }
+        *reinterpret_cast<uint2*>(o_hi + row + e) = oh;
+        if (o_lo) *reinterpret_cast<uint2*>(o_lo + row + e) = ol;
+    }
+}
+
+// the shifted half of out [B*R, D] from the cache rows a finished prefill_ln launch wrote: one thread per vector V (16 bytes, or 8 when
+// a channel quarter is no multiple of 8 elements) of the first D / 2 channels of a row, consecutive threads on consecutive vectors.
+//   fmap > 0  ShiftVideoTokens: first quarter <- row i - fmap, second quarter <- row i - 1, zero at the frame border; row 0 keeps h
+//   fmap < 0  ShiftAudioTokens: first half <- row i - 1, zeros for row 0
+template <typename V> __device__ __forceinline__ V vec_zero();
+template <> __device__ __forceinline__ uint4 vec_zero<uint4>() { return make_uint4(0u, 0u, 0u, 0u); }
+template <> __device__ __forceinline__ uint2 vec_zero<uint2>() { return make_uint2(0u, 0u); }
+
+template <typename V>
+__global__ __launch_bounds__(256) void prefill_shift_kernel(const bf16_t* __restrict__ c_hi, const bf16_t* __restrict__ c_lo,
+                                                            bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo, int B, int R,
+                                                            int cache_rows, int D, int fmap) {
+    constexpr int EV = sizeof(V) / sizeof(bf16_t);
+    const int per_row = (D >> 1) / EV, qd = D >> 2;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)B * R * per_row) return;
+    const int e = (int)(idx % per_row) * EV;
+    const size_t r = idx / per_row;
+    const int i = (int)(r % R), smp = (int)(r / R);
+    int back;                                        // rows back to the source row; 0 = zeros
+    if (fmap > 0) {
+        if (i == 0) return;                          // <bos> is not shifted
+        const int p = i - 1, wq = p % fmap, yq = (p / fmap) % fmap;
+        back = e < qd ? (yq > 0 ? fmap : 0) : (wq > 0 ? 1 : 0);
+    } else {
+        back = i > 0 ? 1 : 0;
+    }
+    const size_t src = ((size_t)smp * cache_rows + (i - back)) * D + e, dst = r * D + e;
+    if (back) {
+        *reinterpret_cast<V*>(o_hi + dst) = *reinterpret_cast<const V*>(c_hi + src);
+        if (o_lo) *reinterpret_cast<V*>(o_lo + dst) = *reinterpret_cast<const V*>(c_lo + src);
+    } else {
+        *reinterpret_cast<V*>(o_hi + dst) = vec_zero<V>();
+        if (o_lo) *reinterpret_cast<V*>(o_lo + dst) = vec_zero<V>();
+    }
+}
+
+// k | v columns of qkv [B*R, 3*inner] -> rows [0, R) of kv [B, cache_rows, 2*inner]: one 16-byte vector per thread, consecutive
+// threads on consecutive vectors of a row (inner % 8 == 0: both the column offset and the row pitches are multiples of 16 bytes)
+__global__ __launch_bounds__(256) void prefill_kv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ qkvl,
+                                                         bf16_t* __restrict__ kv, bf16_t* __restrict__ kvl, int B, int R,
+                                                         int cache_rows, int inner) {
+    const int per_row = inner >> 2;                  // 2 * inner / 8
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)B * R * per_row) return;
+    const int c = (int)(idx % per_row) * 8;
+    const size_t r = idx / per_row;
+    const size_t src = r * 3 * inner + inner + c, dst = ((r / R) * cache_rows + r % R) * 2 * inner + c;
+    *reinterpret_cast<uint4*>(kv + dst) = *reinterpret_cast<const uint4*>(qkv + src);
+    if (kvl) *reinterpret_cast<uint4*>(kvl + dst) = *reinterpret_cast<const uint4*>(qkvl + src);
+}
+
 size_t rows_ws_floats(int B, int T, int heads, int dim_head, int& nsplit) {
     nsplit = (T + 1 + ROWS_SPLIT - 1) / ROWS_SPLIT;
     return (size_t)B * ((size_t)heads * (T + 1) + (size_t)nsplit * (2 * heads + heads * dim_head));
@@ -684,6 +837,55 @@ extern "C" int amdnuwa_decode_ln(const void* y, int y_is_bf16, const float* resi
     else
         hipLaunchKernelGGL((decode_ln_kernel<false>), dim3(B), dim3(256), 0, stream, y, resid, w, b, next_w, next_b, x_new, cache_hi,
                            cache_lo, out_hi, out_lo, pos, cache_rows, D, fmap, eps);
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+
+extern "C" int amdnuwa_prefill_ln(const void* y, int y_is_bf16, const float* resid, const float* w, const float* b,
+                                  const float* next_w, const float* next_b, float* x_new, uint16_t* cache_hi, uint16_t* cache_lo,
+                                  uint16_t* out_hi, uint16_t* out_lo, int B, int R, int cache_rows, int D, int fmap, float eps,
+                                  hipStream_t stream) {
+    if (!y || B <= 0 || R <= 0 || D <= 0) return AMDNUWA_ERR_ARG;
+    if (resid && (!w || !b || !x_new)) return AMDNUWA_ERR_ARG;
+    if (!resid && y_is_bf16) return AMDNUWA_ERR_ARG;                 // without a post-norm, y IS the fp32 stream row
+    if (next_w && (!next_b || !out_hi)) return AMDNUWA_ERR_ARG;
+    if (!next_w && !resid) return AMDNUWA_ERR_ARG;
+    if (cache_hi && (fmap == 0 || fmap < -1 || cache_rows <= 0 || R > cache_rows || !next_w)) return AMDNUWA_ERR_ARG;
+    if (cache_hi && ((cache_lo != nullptr) != (out_lo != nullptr))) return AMDNUWA_ERR_ARG;
+    if (!cache_hi && cache_lo) return AMDNUWA_ERR_ARG;
+    if (D % 16 || D > 4096) return AMDNUWA_ERR_UNSUPPORTED;
+    if ((size_t)B * R > 0x7fffffffu) return AMDNUWA_ERR_UNSUPPORTED;
+    if (y_is_bf16)
+        hipLaunchKernelGGL((prefill_ln_kernel<true>), dim3(B * R), dim3(256), 0, stream, y, resid, w, b, next_w, next_b, x_new, cache_hi,
+                           cache_lo, out_hi, out_lo, R, cache_rows, D, eps);
+    else
+        hipLaunchKernelGGL((prefill_ln_kernel<false>), dim3(B * R), dim3(256), 0, stream, y, resid, w, b, next_w, next_b, x_new, cache_hi,
+                           cache_lo, out_hi, out_lo, R, cache_rows, D, eps);
+    if (cache_hi) {
+        // second launch, ordered behind the first on the stream: every cache row it reads is complete
+        const bool v16 = D % 32 == 0;                                // a channel quarter is a whole number of 16-byte vectors
+        const size_t nvec = (size_t)B * R * ((D >> 1) / (v16 ? 8 : 4)), nblk = (nvec + 255) / 256;
+        if (nblk > 0x7fffffffu) return AMDNUWA_ERR_UNSUPPORTED;
+        if (v16)
+            hipLaunchKernelGGL((prefill_shift_kernel<uint4>), dim3((unsigned)nblk), dim3(256), 0, stream, cache_hi, cache_lo, out_hi, out_lo,
+                               B, R, cache_rows, D, fmap);
+        else
+            hipLaunchKernelGGL((prefill_shift_kernel<uint2>), dim3((unsigned)nblk), dim3(256), 0, stream, cache_hi, cache_lo, out_hi, out_lo,
+                               B, R, cache_rows, D, fmap);
+    }
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+
+extern "C" int amdnuwa_prefill_kv(const uint16_t* qkv, const uint16_t* qkv_lo, uint16_t* kv_cache, uint16_t* kv_cache_lo, int B, int R,
+                                  int cache_rows, int inner, hipStream_t stream) {
+    if (!qkv || !kv_cache || B <= 0 || R <= 0 || cache_rows <= 0 || inner <= 0 || R > cache_rows) return AMDNUWA_ERR_ARG;
+    if ((qkv_lo != nullptr) != (kv_cache_lo != nullptr)) return AMDNUWA_ERR_ARG;
+    if (inner % 8) return AMDNUWA_ERR_UNSUPPORTED;                   // 16-byte vectors
+    const size_t nblk = ((size_t)B * R * (inner >> 2) + 255) / 256;
+    if (nblk > 0x7fffffffu) return AMDNUWA_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(prefill_kv_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, qkv, qkv_lo, kv_cache, kv_cache_lo, B, R, cache_rows,
+                       inner);
     LAUNCH_CHECK();
     return AMDNUWA_OK;
 }

@@ -10,6 +10,12 @@ and computes ONE new row per call with the same libamdnuwa kernels the training 
 cross-attention core with n = 1) plus the two single-row kernels of csrc/decode.hip.  The row index lives in device memory,
 so the per-token work of a whole guided step can be captured once in a HIP graph and replayed for every token.
 
+Past max_video_frames NUWA.generate slides its frame window (np.py:1873-1881): every kept token moves one frame earlier, its position
+embedding changes and with it every cached row of every layer.  IncrementalDecoder.prefill / GuidedStepper.prefill rebuild the caches
+with ONE full-sequence pass over the rows the new window already determines -- the mirror of step() over R rows, on the rows forms of
+the two norm / cache kernels (amdnuwa_prefill_ln, amdnuwa_prefill_kv) and the full-sequence attention cores of the training path, in
+the operand forms step() uses -- after which the captured row step serves the new frame's tokens again.
+
 NUWAVideoAudio.generate (np.py:2111-2222) decodes two interleaved streams through the DualModalityDecoder (np.py:1299-1487).  Every
 stage is row-causal there too: the audio window attention looks back only, and the chunked video <-> audio attention lets frame t
 of one stream see frame t - 1 of the other (np.py:908-1067), which is complete -- and final -- by the time any row of frame t is
@@ -205,6 +211,78 @@ class IncrementalDecoder:
             for d in blk.store_after:
                 d.store(x, self.pos_dev)
         return x if self.halves == 1 else (state[0] + state[1]) * self.combine
+
+    def _enter_rows(self, x, nxt, R):
+        """_enter for R rows per sample (x fp32 [B*R, D], sample-major): the block's cache rows [0, R) are written"""
+        if nxt is None:
+            return None
+        if nxt.pre is None:
+            return _cast_row(x, self.lo)
+        return K.prefill_ln(x, None, None, nxt.pre, R, cache=nxt.hcache, fmap=nxt.fmap or 0)[1]
+
+    def prefill(self, x_rows):
+        """x_rows fp32 [B, R, D]: the decoder input rows 0 .. R-1 of every sample -> those rows after all layers (before the final norm),
+        [B, R, D]; rows [0, R) of every block's hcache / kvcache are left as R step() calls at pos = 0 .. R-1 would have left them.
+
+        The mirror of step() over R rows: the same operand forms (the hi (+ lo) bf16 pair of K.want_lo(), never the fp16 forms of the
+        training forward), the norms / shift / cache writes by the rows form of the single-row kernels (prefill_ln, prefill_kv) and the
+        attention cores by the full-sequence kernels of the training path.  This is the pass NUWA.generate runs when its frame window
+        slides: every kept token moves one frame earlier, so every hidden state and cached row changes.  The position counter is the
+        caller's (GuidedStepper.prefill sets it to R)."""
+        B, R, D = x_rows.shape
+        if B != self.B or not 1 <= R <= self.rows:
+            raise ValueError(f'IncrementalDecoder.prefill: {B} x {R} rows do not fit caches of {self.B} x {self.rows} rows')
+        blocks = self.blocks
+        if any(b.kind in ('xm', 'xc2') or b.store_before or b.store_after for b in blocks):
+            raise NotImplementedError('IncrementalDecoder.prefill: no full-sequence cache prefill for cross-modality / SparseCross2DNA blocks')
+        fast = ops._fast()
+        x = x_rows.reshape(B * R, D).contiguous()
+        state = [x] * self.halves
+        h = self._enter_rows(x, blocks[0], R)
+        for i, blk in enumerate(blocks):
+            inner = blk.inner
+            raw = blk.post is None
+            if blk.kind == 's3':
+                p = inner._params()
+                W = ops.S3Inner.weights(inner._cache, p)
+                g0 = blk.geom
+                g = K.s3_geom(B, R, (g0.F, g0.H, g0.W), (g0.kf, g0.kh, g0.kw), (g0.df, g0.dh, g0.dw), g0.heads, g0.dim_head)
+                rel = p[5].detach().contiguous() if len(p) > 5 else None
+                qkv = K.gemm_nt(h, W['qkv'], out_bf16=True)
+                K.prefill_kv(qkv, blk.kvcache, R)
+                o = K.sparse3dna_fwd(g, qkv, p[2].detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel)
+                y = K.gemm_nt(o, W['out'], bias=p[4].detach(), out_bf16=fast and not raw)
+            elif blk.kind == 'x':
+                p = inner._params()
+                W = ops.XInner.weights(inner._cache, p)
+                g0 = blk.xg
+                if blk.o_const is not None:      # the all-masked pass: the same row for every position
+                    rep = lambda t: None if t is None else t[:, None].expand(B, R, t.shape[-1]).reshape(B * R, -1).contiguous()
+                    o = K.BF(rep(blk.o_const.hi), rep(blk.o_const.lo))
+                else:
+                    # blk.pk was packed with an n = 1 geometry: the key images depend on (B, T, heads, dim_head) alone, so R queries attend them
+                    g = K.x_geom(B, R, g0.T, g0.heads, g0.dim_head)
+                    q = K.gemm_nt(h, W['q'], out_bf16=True)
+                    o = K.xattn_fwd(g, q, blk.pk, p[2].detach().reshape(g.heads, g.heads).contiguous(), save=False)[0]
+                y = K.gemm_nt(o, W['out'], out_bf16=fast and not raw)
+            else:
+                W = ops.FFInner.weights(inner._cache, inner._params())
+                u = K.gemm_nt(h, W['w1'], out_bf16=True)
+                gg = K.geglu_fwd(u, W['FP'], interleaved=True)
+                y = K.gemm_nt(gg, W['w2'], out_bf16=fast and not raw)
+            nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+            if not raw:
+                fused = nxt is not None and nxt.pre is not None
+                x, h = K.prefill_ln(y, state[blk.dst], blk.post, nxt.pre if fused else None, R, cache=nxt.hcache if fused else None,
+                                    fmap=(nxt.fmap or 0) if fused else 0)
+                if nxt is not None and not fused:
+                    h = _cast_row(x, self.lo)
+            else:
+                x = state[blk.dst] + y
+                h = self._enter_rows(x, nxt, R)
+            state[blk.dst] = x
+        out = x if self.halves == 1 else (state[0] + state[1]) * self.combine
+        return out.reshape(B, R, D)
 
 
 class _Cross2DNARows:
@@ -521,7 +599,7 @@ class GuidedStepper:
     def __init__(self, nuwa, text_embeds, text_mask, max_rows, cond_scale, graph=True):
         dev = text_embeds.device
         B, D = text_embeds.shape[0], text_embeds.shape[-1]
-        self.nuwa, self.cond_scale = nuwa, cond_scale
+        self.nuwa, self.cond_scale, self.max_rows = nuwa, cond_scale, max_rows
         self.pos_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         tr = nuwa.video_transformer
         self.cond = IncrementalDecoder(tr, B, max_rows, text_embeds, text_mask, self.pos_dev)
@@ -545,6 +623,20 @@ class GuidedStepper:
             logits = ul + (logits - ul) * self.cond_scale
         self.pos_dev += 1
         return logits
+
+    def prefill(self, rows):
+        """rows fp32 [B, R, D] = decoder input rows 0 .. R-1 of a (new) window: one full-sequence pass per decoder fills cache rows [0, R)
+        (IncrementalDecoder.prefill; with guidance the text-masked pass is fed the conditioned pass's final-normed output, np.py:1894-1898)
+        and the position becomes R -- the next call is row R.  Caches, x_in and pos_dev are persistent buffers, so a graph captured
+        before the prefill keeps serving the rows after it.  Cache rows >= R keep the previous window's data: row r is written by the
+        step at position r before any later step reads it (every stage looks back only)."""
+        R = rows.shape[1]
+        hidden = self.cond.prefill(rows)
+        if self.uncond is not None:
+            self.uncond.prefill(self.nuwa.video_transformer.norm(hidden).contiguous())
+        self.pos_dev.fill_(R)                          # (outside any capture)
+        self._calls += 1
+        return hidden
 
     def __call__(self, x_row):
         """x_row fp32 [B, D] = decoder input row at the current position -> logits [B, C] for the next token"""

@@ -1226,6 +1226,32 @@ def s3_decode(g, qkv, kv_cache, pos_dev, wth, rel_bias=None):
     return o
 
 
+def prefill_ln(y, resid, post, nxt, R, cache=None, fmap=0, eps=1e-5):
+    """decode_ln for R rows per sample at once (rows sample-major: y / resid [B*R, D]): bit-identical to R decode_ln calls at
+    pos = 0 .. R-1; rows [0, R) of cache BF [B, rows, D] are written.  Returns (x_new fp32 [B*R, D] or None, h BF [B*R, D] or None)"""
+    L = _lib.lib()
+    yp, ybf, (BR, D), dev = _f32_or_bf(y)
+    assert BR % R == 0
+    x_new = torch.empty((BR, D), dtype=torch.float32, device=dev) if resid is not None else None
+    h = empty_bf((BR, D), dev) if nxt is not None else BF(None, None)
+    ch, cl, rows = (cache.hi, cache.lo, cache.hi.shape[1]) if cache is not None else (None, None, 0)
+    assert cache is None or cache.hi.shape[0] == BR // R
+    check(L.amdnuwa_prefill_ln(yp, 1 if ybf else 0, _p(resid), _p(post[0]) if post else None, _p(post[1]) if post else None,
+                               _p(nxt[0]) if nxt else None, _p(nxt[1]) if nxt else None, _p(x_new), _p(ch), _p(cl), _p(h.hi),
+                               _p(h.lo), BR // R, R, rows, D, fmap, eps, _stream()), 'amdnuwa_prefill_ln')
+    return x_new, (h if nxt is not None else None)
+
+
+def prefill_kv(qkv, kv_cache, R):
+    """the k | v columns of qkv BF [B*R, 3*inner] (dense rows) -> rows [0, R) of kv_cache BF [B, rows, 2*inner], as R s3_decode calls leave them"""
+    L = _lib.lib()
+    BR, inner3 = qkv.hi.shape
+    B, rows, inner2 = kv_cache.hi.shape
+    assert BR == B * R and inner3 * 2 == inner2 * 3 and qkv.hi.is_contiguous() and kv_cache.hi.is_contiguous()
+    check(L.amdnuwa_prefill_kv(_p(qkv.hi), _p(qkv.lo), _p(kv_cache.hi), _p(kv_cache.lo), B, R, rows, inner2 // 2, _stream()),
+          'amdnuwa_prefill_kv')
+
+
 def xattn_decode(g, q, pk, wth):
     """single-query text cross-attention (g.n == 1): q BF [B, inner] -> o BF [B, inner]"""
     L = _lib.lib()

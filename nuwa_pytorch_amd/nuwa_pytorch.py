@@ -87,6 +87,19 @@ def lookback_window(ids, tokens_per_frame, max_frames):
     return ids[:, -keep:]
 
 
+def slide_plan(n, tokens_per_frame, max_frames):
+    """(keep, slid) for the decoding step that has n tokens behind it: keep = the length of lookback_window(ids, ...) for n ids -- the
+    step's new decoder row is row `keep` of the window (row 0 = <bos>) and its newest token sits at window position keep - 1 --, slid = the
+    window starts one frame later than at step n - 1, so every kept row has moved and the key/value caches need a prefill.  The window
+    slides when n is past it and opens a new frame (every step past the window when a frame is one token)."""
+    window = tokens_per_frame * max_frames
+    if n <= window:
+        return n, False
+    partial = n % tokens_per_frame
+    keep = (max_frames - (1 if partial else 0)) * tokens_per_frame + partial
+    return keep, partial == 1 or tokens_per_frame == 1
+
+
 def causal_neighbor_mask(video_shape, kernel_size, dilation):
     """(N, K+1) bool, True = tap falls in the causal zero padding; column 0 (<bos>) never masked.
     Same content as the reference's `mask` buffer (np.py:442-457), computed by index arithmetic."""
@@ -1103,6 +1116,8 @@ class NUWA(nn.Module):
 
     generate_use_cache = True        # key/value-cached generate() (decode.py); False = the reference's recompute loop
     generate_use_graph = True        # replay each token's decoder work as one captured HIP graph
+    generate_slide_cache = True      # num_frames > max_video_frames: keep the cached rows and prefill the caches at every slide of the
+                                     # frame window; False = the whole call on the recompute loop (A/B switch)
 
     # -- text side (adjacent, row f1) ------------------------------------------------------------
     def embed_text(self, text, mask=None):
@@ -1168,19 +1183,25 @@ class NUWA(nn.Module):
     @eval_decorator
     def generate(self, *, text, filter_thres=0.9, temperature=1., decode_max_batchsize=10, cond_scale=2., num_frames=None):
         """np.py:1841-1915.  The reference recomputes the whole prefix (twice) per token; here each token costs one new decoder
-        row against per-layer key/value caches (decode.GuidedStepper, row f3) whenever the sequence fits the video shape and every
-        decoder block (Transformer or ReversibleTransformer) is on the single-row kernels -- otherwise the reference's recompute algorithm runs on the same kernels."""
+        row against per-layer key/value caches (decode.GuidedStepper, row f3) whenever every decoder block (Transformer or
+        ReversibleTransformer) is on the single-row kernels -- otherwise the reference's recompute algorithm runs on the same kernels.
+        Past max_video_frames the reference slides a window over the last frames (np.py:1873-1881): every kept token moves one frame
+        earlier, so at a slide the caches are rebuilt by ONE full-sequence pass over the rows the window already determines
+        (GuidedStepper.prefill) and the tokens of the new frame are single-row steps again."""
         batch, device = text.shape[0], text.device
         text_mask = text != 0
         text_embeds = self.embed_text(text, mask=text_mask)
-        tpf = self.video_fmap_size ** 2
-        total = tpf * default(num_frames, self.max_video_frames)
+        tpf, max_frames = self.video_fmap_size ** 2, self.max_video_frames
+        total = tpf * default(num_frames, max_frames)
+        window = tpf * max_frames
         ids = torch.empty((batch, 0), device=device, dtype=torch.long)
-        cached = self.generate_use_cache and text.is_cuda and total <= tpf * self.max_video_frames
+        cached = self.generate_use_cache and text.is_cuda and (total <= window or self.generate_slide_cache)
         if cached:
             from .decode import GuidedStepper
+            # rows: <bos> + the tokens behind the last step; at n = window tokens the window has not slid yet and holds window + 1 rows
+            max_rows = total if total <= window else window + 1
             try:                                 # plain and reversible decoder alike; a block outside the single-row kernels -> recompute
-                stepper = GuidedStepper(self, text_embeds, text_mask, total, cond_scale, graph=self.generate_use_graph)
+                stepper = GuidedStepper(self, text_embeds, text_mask, max_rows, cond_scale, graph=self.generate_use_graph)
             except NotImplementedError:
                 cached = False
         if cached:
@@ -1188,13 +1209,21 @@ class NUWA(nn.Module):
             row = self.video_bos[None].expand(batch, -1)
         for t in range(total):
             if cached:
+                keep, slid = slide_plan(t, tpf, max_frames)
+                if slid:
+                    # the rows embed_video(lookback_window(ids)) has, a row's position-embedding index being its index inside the window:
+                    # rows 0 .. keep - 1 (<bos> + all but the newest token) refill the caches; row keep (`row`, made below at the
+                    # end of the step before with its window index) is an ordinary step
+                    rows = torch.cat((self.video_bos[None, None].expand(batch, 1, -1),
+                                      self.image_embedding(ids[:, t - keep:-1]) + pos_table[:keep - 1]), dim=1)
+                    stepper.prefill(rows)
                 logits = stepper(row)
             else:
-                logits = self._guided_last_logits(lookback_window(ids, tpf, self.max_video_frames), text_embeds, text_mask, cond_scale)
+                logits = self._guided_last_logits(lookback_window(ids, tpf, max_frames), text_embeds, text_mask, cond_scale)
             token = sample_top_fraction(logits, filter_thres, temperature)
             ids = torch.cat((ids, token[:, None]), dim=1)
             if cached:
-                row = self.image_embedding(token) + pos_table[t]
+                row = self.image_embedding(token) + pos_table[slide_plan(t + 1, tpf, max_frames)[0] - 1]
         self.last_generated_ids = ids                      # (b, frames * fmap^2) token ids behind the returned frames
         return self._ids_to_frames(ids, decode_max_batchsize)
 
