@@ -38,7 +38,8 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 * 20: the amdnuwa_cattn_* family, 21: amdnuwa_cattn_geom.n_keys; ABI 21 also accepts token grids of up to 64 columns in the
                                                 *     window kernels -- amdnuwa_s3_geom / amdnuwa_s3_supported below: a wider accepted range, no signature or struct change;
                                                 *     amdnuwa_attn_decode_rows and its _workspace_bytes were added at 21 as well: purely additive; so were amdnuwa_prefill_ln and
-                                                *     amdnuwa_prefill_kv, the cache prefill of a sliding generate() window) */
+                                                *     amdnuwa_prefill_kv, the cache prefill of a sliding generate() window, and amdnuwa_cross2dna_decode with its
+                                                *     _workspace_bytes, the single-query SparseCross2DNA over a window of any size) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -632,6 +633,24 @@ size_t amdnuwa_attn_decode_rows_workspace_bytes(int B, int T, int heads, int dim
 int amdnuwa_attn_decode_rows(int B, int T, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo, int ldq,
                              const uint16_t* kv, const uint16_t* kv_lo, int cache_rows, const int* first_row, const uint8_t* key_mask,
                              const float* null_k, const float* null_v, const float* w_th, const float* th_bias, uint16_t* o,
+                             uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
+/* SparseCross2DNA (np.py:761-901, rows after <bos>) for ONE query row per sample, its window read IN PLACE (added at ABI 21, purely
+ * additive).  The query of decoder row pos[0] (DEVICE memory, >= 1: a captured launch serves every row) sits at feature-map position
+ * i = (pos[0] - 1) mod n_pos.  Slot 0 is the learned null key, always visible; slot 1 + j is context row slot_rows[i][j] of the sample, read
+ * from kv [B][ctx_rows][2 * inner] (k | v: to_kv of the sketch rows, bf16 hi with an optional lo image).  slot_rows [n_pos][J] int32 lives in
+ * device memory; a negative entry is 'same' padding: the slot is hidden, contributes nothing, and NO address is formed from it.  key_mask
+ * [B][ctx_rows] (0 = hidden; indexed by CONTEXT ROW, not by slot) or NULL; a row the mask hides may still be read.  Scores q . k * scale,
+ * fp32 softmax over the J + 1 slots, P'[g][j] = sum_h w_th[g][h] P[h][j] (no bias), o[g] = sum_j P'[g][j] v_j[g].  pos[0] < 1, or any
+ * entry of slot_rows[i] >= ctx_rows, writes nothing (the <bos> row is the caller's).  q [B, ldq] unscaled, o [B, ldo]: bf16 hi (+ lo) rows;
+ * the lo images of q, kv and o are given together or not at all.  heads 1..8, dim_head 32 / 64, any J >= 1, any n_pos >= 1; otherwise
+ * AMDNUWA_ERR_UNSUPPORTED (arguments are checked first: a null or non-positive one is AMDNUWA_ERR_ARG).  The kernels are those of
+ * amdnuwa_attn_decode_rows with the slot -> row mapping exchanged: splits of 128 slots, the split count a function of J alone, partial results
+ * met in index order, no atomics -- two runs are bit-identical.  workspace: >= _workspace_bytes =
+ * 4 * B * (heads * (J + 1) + ceil((J + 1) / 128) * (2 * heads + heads * dim_head)) bytes, AMDNUWA_ERR_WORKSPACE otherwise. */
+size_t amdnuwa_cross2dna_decode_workspace_bytes(int B, int J, int heads, int dim_head);
+int amdnuwa_cross2dna_decode(int B, int J, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo, int ldq,
+                             const uint16_t* kv, const uint16_t* kv_lo, int ctx_rows, const int* slot_rows, int n_pos, const int* pos,
+                             const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o,
                              uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
 
 /* ---- frozen VQGanVAE tokenizer (VQGanVAE.get_video_indices -> encode, reference vqgan_vae.py:431-435, 452-458), exact fp32 ---- */

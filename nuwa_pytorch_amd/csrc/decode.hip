@@ -216,24 +216,36 @@ __device__ __forceinline__ float dot_q_k(const float* qrow, const bf16_t* khi, c
     return acc;
 }
 
+// acc[0 .. 8) += pj * V[off .. off+8): one 16 B load per image
+__device__ __forceinline__ void pv_row(float (&acc)[8], float pj, const bf16_t* vhi, const bf16_t* vlo, size_t off) {
+    const uint4 h = *reinterpret_cast<const uint4*>(vhi + off);
+    float v[8] = {lo_f(h.x), hi_f(h.x), lo_f(h.y), hi_f(h.y), lo_f(h.z), hi_f(h.z), lo_f(h.w), hi_f(h.w)};
+    if (vlo) {
+        const uint4 l = *reinterpret_cast<const uint4*>(vlo + off);
+        v[0] += lo_f(l.x); v[1] += hi_f(l.x); v[2] += lo_f(l.y); v[3] += hi_f(l.y);
+        v[4] += lo_f(l.z); v[5] += hi_f(l.z); v[6] += lo_f(l.w); v[7] += hi_f(l.w);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, v[e], acc[e]);
+}
+
 // out[c0 .. c0+8) += sum over this thread's slots of P'[j] * V_j[c0 .. c0+8): 16 B loads, no branch (masked slots carry
 // P' == 0 exactly and point at finite rows), eight loads in flight
 template <typename RowOf>
 __device__ __forceinline__ void pv_chunk(float (&acc)[8], const float* pmg, const bf16_t* vhi, const bf16_t* vlo, int j0, int jstep,
                                          int J, RowOf row_off) {
 #pragma unroll 8
+    for (int j = j0; j < J; j += jstep) pv_row(acc, pmg[j], vhi, vlo, row_off(j));
+}
+
+// pv_chunk over slots whose rows come from a table (krow[j], < 0 = no row): such a slot is SKIPPED -- its P' is exactly 0 (a mix
+// without bias) -- so that no address is ever formed from it; row r starts at r * pitch + col
+__device__ __forceinline__ void pv_chunk_tab(float (&acc)[8], const float* pmg, const int* krow, const bf16_t* vhi, const bf16_t* vlo,
+                                             int j0, int jstep, int J, size_t pitch, size_t col) {
+#pragma unroll 4
     for (int j = j0; j < J; j += jstep) {
-        const float pj = pmg[j];
-        const size_t off = row_off(j);
-        const uint4 h = *reinterpret_cast<const uint4*>(vhi + off);
-        float v[8] = {lo_f(h.x), hi_f(h.x), lo_f(h.y), hi_f(h.y), lo_f(h.z), hi_f(h.z), lo_f(h.w), hi_f(h.w)};
-        if (vlo) {
-            const uint4 l = *reinterpret_cast<const uint4*>(vlo + off);
-            v[0] += lo_f(l.x); v[1] += hi_f(l.x); v[2] += lo_f(l.y); v[3] += hi_f(l.y);
-            v[4] += lo_f(l.z); v[5] += hi_f(l.z); v[6] += lo_f(l.w); v[7] += hi_f(l.w);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, v[e], acc[e]);
+        const int r = krow[j];
+        if (r >= 0) pv_row(acc, pmg[j], vhi, vlo, (size_t)r * pitch + col);
     }
 }
 
@@ -409,6 +421,12 @@ __global__ __launch_bounds__(1024) void xattn_decode_kernel(XDecArgs a) {
 //   rows_apply_kernel  : merges the statistics of all splits IN INDEX ORDER, P = exp(s - M) / Z, P' = W P + bias, partial o of the split
 //   rows_reduce_kernel : sums the partial rows in index order and rounds the output
 // No atomics, the split count depends on T alone: two runs are bit-identical.  The first row comes from device memory (graph replay).
+//
+// The three kernels are templated on the slot -> cache-row mapping.  TAB = false is the contiguous window above.  TAB = true serves
+// SparseCross2DNA (np.py:761-901) for the query of decoder row pos (device memory, >= 1): slot 1 + t is context row tab[i][t] of the sample,
+// i = (pos - 1) mod n_pos the query's feature-map position; a negative entry is 'same' padding -- hidden, never turned into an address --
+// and the key mask is indexed by context row.  Every workgroup reads the table row of i ONCE, keeps its own split's entries in LDS and
+// checks all of them against cache_rows on the way, so that all workgroups of the three launches agree on whether anything is written.
 constexpr int ROWS_SPLIT = 128;
 constexpr float ROWS_NEG = -3.4028234663852886e38f;
 
@@ -416,32 +434,62 @@ struct RowsArgs {
     const bf16_t *q, *ql;            // [B, ldq] unscaled
     const bf16_t *kv, *kvl;          // [B, cache_rows, 2*inner]: k | v
     const int* first;                // device: cache row of slot 1
-    const uint8_t* mask;             // [B, T] or NULL
+    const uint8_t* mask;             // [B, T] (TAB: [B, cache_rows], by context row) or NULL
     const float *nk, *nv, *wth, *bias;
     bf16_t *o, *ol;                  // [B, ldo]
     float *sc, *st, *part;           // workspace: scores [B][J][NH] | stats [B][nsplit][NH][2] | partial rows [B][nsplit][inner]
     int ldq, ldo, cache_rows, T, heads, dim_head, nsplit;
     float scale;
+    const int* tab;                  // TAB: [n_pos][T] cache row of every slot, < 0 = padding; `first` then holds the decoder row
+    int n_pos;
 };
 
 __device__ __forceinline__ bool rows_window_ok(const RowsArgs& a, int first) {
     return first >= 0 && (long long)first + a.T <= (long long)a.cache_rows;
 }
 
-template <int DHT>
+// first <- the device-side row; false (for every thread of every workgroup of the launch alike): nothing is written.
+// TAB: krow[j] <- the cache row of slot j0 + j for j < Jl (-1 for the null key's slot 0), visible to the whole workgroup on return
+template <bool TAB>
+__device__ __forceinline__ bool rows_begin(const RowsArgs& a, int* krow, int j0, int Jl, int& first) {
+    first = a.first[0];
+    if constexpr (!TAB) {
+        return rows_window_ok(a, first);
+    } else {
+        if (first < 1) return false;
+        const int* tab = a.tab + (size_t)((first - 1) % a.n_pos) * a.T;
+        int bad = 0;
+        for (int t = threadIdx.x; t < a.T; t += blockDim.x) {        // consecutive threads, consecutive entries
+            const int r = tab[t], j = t + 1 - j0;
+            bad |= r >= a.cache_rows;
+            if (j >= 0 && j < Jl) krow[j] = r;
+        }
+        if (j0 == 0 && Jl > 0 && threadIdx.x == 0) krow[0] = -1;
+        return __syncthreads_or(bad) == 0;
+    }
+}
+
+// is slot j0 + j of sample b visible?  slot 0, the null key, always is
+template <bool TAB>
+__device__ __forceinline__ bool rows_slot_ok(const RowsArgs& a, const int* krow, int b, int j0, int j) {
+    const int jg = j0 + j;
+    if constexpr (TAB) return jg == 0 || (krow[j] >= 0 && (!a.mask || a.mask[(size_t)b * a.cache_rows + krow[j]] != 0));
+    else return jg == 0 || !a.mask || a.mask[(size_t)b * a.T + jg - 1] != 0;
+}
+
+template <int DHT, bool TAB>
 __global__ __launch_bounds__(256) void rows_stats_kernel(RowsArgs a) {
     __shared__ float qs[8 * 65];
     __shared__ float s[8 * ROWS_SPLIT];
     __shared__ int ok[ROWS_SPLIT];
+    __shared__ int krow[ROWS_SPLIT];
     const int NH = a.heads, DH = a.dim_head, inner = NH * DH, QS = DH + 1, J = a.T + 1;
-    const int sp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, first = a.first[0];
-    if (!rows_window_ok(a, first)) return;
+    const int sp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int j0 = sp * ROWS_SPLIT, Jl = min(ROWS_SPLIT, J - j0);
+    int first;
+    if (!rows_begin<TAB>(a, krow, j0, Jl, first)) return;
     for (int c = tid; c < inner; c += blockDim.x) qs[(c / DH) * QS + c % DH] = ld_hl(a.q, a.ql, (size_t)b * a.ldq + c) * a.scale;
-    for (int j = tid; j < Jl; j += blockDim.x) {
-        const int jg = j0 + j;
-        ok[j] = jg == 0 || !a.mask || a.mask[(size_t)b * a.T + jg - 1] != 0;
-    }
+    for (int j = tid; j < Jl; j += blockDim.x) ok[j] = rows_slot_ok<TAB>(a, krow, b, j0, j);
     __syncthreads();
     const size_t kvb = (size_t)b * a.cache_rows * 2 * inner;
     for (int idx = tid; idx < NH * Jl; idx += blockDim.x) {       // consecutive threads: the heads of one key row (contiguous)
@@ -452,7 +500,8 @@ __global__ __launch_bounds__(256) void rows_stats_kernel(RowsArgs a) {
                 sc = 0.f;
                 for (int d = 0; d < DH; ++d) sc = fmaf(qs[h * QS + d], a.nk[h * DH + d], sc);
             } else {
-                const size_t base = kvb + (size_t)(first + jg - 1) * 2 * inner + (size_t)h * DH;
+                const size_t row = TAB ? (size_t)krow[j] : (size_t)(first + jg - 1);
+                const size_t base = kvb + row * 2 * inner + (size_t)h * DH;
                 sc = dot_q_k<DHT>(qs + h * QS, a.kv + base, a.kvl ? a.kvl + base : nullptr, DH);
             }
         }
@@ -476,16 +525,19 @@ __global__ __launch_bounds__(256) void rows_stats_kernel(RowsArgs a) {
     }
 }
 
+template <bool TAB>
 __global__ __launch_bounds__(256) void rows_apply_kernel(RowsArgs a) {
     __shared__ float pr[8 * ROWS_SPLIT];
     __shared__ float pm[8 * ROWS_SPLIT];
     __shared__ float red[2048];                                   // [slot group][inner]: 256 / (inner / 8) groups
     __shared__ float mz[16];
     __shared__ int ok[ROWS_SPLIT];
+    __shared__ int krow[ROWS_SPLIT];
     const int NH = a.heads, DH = a.dim_head, inner = NH * DH, J = a.T + 1;
-    const int sp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, first = a.first[0];
-    if (!rows_window_ok(a, first)) return;
+    const int sp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int j0 = sp * ROWS_SPLIT, Jl = min(ROWS_SPLIT, J - j0);
+    int first;
+    if (!rows_begin<TAB>(a, krow, j0, Jl, first)) return;
     if (tid < NH) {                                               // the statistics of all splits meet in index order (eight loads in
         const float* st = a.st + ((size_t)b * a.nsplit * NH + tid) * 2;   // flight at a time: one thread walks a chain of latencies)
         float M = ROWS_NEG;
@@ -511,10 +563,7 @@ __global__ __launch_bounds__(256) void rows_apply_kernel(RowsArgs a) {
         mz[tid] = M;
         mz[8 + tid] = 1.f / Z;                                    // (the null key is always visible: Z >= 1 term)
     }
-    for (int j = tid; j < Jl; j += blockDim.x) {
-        const int jg = j0 + j;
-        ok[j] = jg == 0 || !a.mask || a.mask[(size_t)b * a.T + jg - 1] != 0;
-    }
+    for (int j = tid; j < Jl; j += blockDim.x) ok[j] = rows_slot_ok<TAB>(a, krow, b, j0, j);
     __syncthreads();
     for (int idx = tid; idx < NH * Jl; idx += blockDim.x) {
         const int j = idx / NH, h = idx - j * NH;
@@ -537,8 +586,12 @@ __global__ __launch_bounds__(256) void rows_apply_kernel(RowsArgs a) {
     if (grp < ngrp) {
         const bf16_t* vb = a.kv + (size_t)b * a.cache_rows * 2 * inner;
         const bf16_t* vlb = a.kvl ? a.kvl + (size_t)b * a.cache_rows * 2 * inner : nullptr;
-        const size_t r0 = (size_t)(first + j0 + off - 1);
-        pv_chunk(acc, pm + g * ROWS_SPLIT + off, vb, vlb, grp, ngrp, Jl - off, [&](int j) { return (r0 + j) * 2 * inner + inner + c0; });
+        if constexpr (TAB) {
+            pv_chunk_tab(acc, pm + g * ROWS_SPLIT + off, krow + off, vb, vlb, grp, ngrp, Jl - off, (size_t)2 * inner, (size_t)(inner + c0));
+        } else {
+            const size_t r0 = (size_t)(first + j0 + off - 1);
+            pv_chunk(acc, pm + g * ROWS_SPLIT + off, vb, vlb, grp, ngrp, Jl - off, [&](int j) { return (r0 + j) * 2 * inner + inner + c0; });
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) red[grp * inner + c0 + e] = acc[e];
     }
@@ -551,9 +604,11 @@ __global__ __launch_bounds__(256) void rows_apply_kernel(RowsArgs a) {
     }
 }
 
+template <bool TAB>
 __global__ __launch_bounds__(256) void rows_reduce_kernel(RowsArgs a) {
     const int inner = a.heads * a.dim_head, b = blockIdx.x;
-    if (!rows_window_ok(a, a.first[0])) return;
+    int first;
+    if (!rows_begin<TAB>(a, nullptr, 0, 0, first)) return;
     for (int c = threadIdx.x; c < inner; c += blockDim.x) {
         const float* part = a.part + (size_t)b * a.nsplit * inner + c;
         float t = 0.f;
@@ -722,6 +777,16 @@ size_t rows_ws_floats(int B, int T, int heads, int dim_head, int& nsplit) {
     return (size_t)B * ((size_t)heads * (T + 1) + (size_t)nsplit * (2 * heads + heads * dim_head));
 }
 
+// the three launches of one single-query attention: one workgroup per (split, sample), then one per sample
+template <bool TAB>
+void rows_launch(const RowsArgs& a, int B, hipStream_t stream) {
+    const dim3 grid(a.nsplit, B);
+    if (a.dim_head == 64) hipLaunchKernelGGL((rows_stats_kernel<64, TAB>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((rows_stats_kernel<32, TAB>), grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((rows_apply_kernel<TAB>), grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((rows_reduce_kernel<TAB>), dim3(B), dim3(256), 0, stream, a);
+}
+
 }  // namespace
 
 extern "C" size_t amdnuwa_attn_decode_rows_workspace_bytes(int B, int T, int heads, int dim_head) {
@@ -749,11 +814,35 @@ extern "C" int amdnuwa_attn_decode_rows(int B, int T, int heads, int dim_head, f
     a.sc = static_cast<float*>(workspace);
     a.st = a.sc + (size_t)B * heads * (T + 1);
     a.part = a.st + (size_t)B * a.nsplit * heads * 2;
-    const dim3 grid(a.nsplit, B);
-    if (dim_head == 64) hipLaunchKernelGGL((rows_stats_kernel<64>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((rows_stats_kernel<32>), grid, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(rows_apply_kernel, grid, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(rows_reduce_kernel, dim3(B), dim3(256), 0, stream, a);
+    rows_launch<false>(a, B, stream);
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+
+extern "C" size_t amdnuwa_cross2dna_decode_workspace_bytes(int B, int J, int heads, int dim_head) {
+    return amdnuwa_attn_decode_rows_workspace_bytes(B, J, heads, dim_head);
+}
+
+extern "C" int amdnuwa_cross2dna_decode(int B, int J, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo, int ldq,
+                                        const uint16_t* kv, const uint16_t* kv_lo, int ctx_rows, const int* slot_rows, int n_pos,
+                                        const int* pos, const uint8_t* key_mask, const float* null_k, const float* null_v,
+                                        const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes,
+                                        hipStream_t stream) {
+    if (!q || !kv || !slot_rows || !pos || !null_k || !null_v || !w_th || !o) return AMDNUWA_ERR_ARG;
+    if (B <= 0 || J <= 0 || heads <= 0 || dim_head <= 0 || ctx_rows <= 0 || n_pos <= 0) return AMDNUWA_ERR_ARG;
+    if ((q_lo != nullptr) != (kv_lo != nullptr) || (q_lo != nullptr) != (o_lo != nullptr)) return AMDNUWA_ERR_ARG;
+    if ((long long)ldq < (long long)heads * dim_head || (long long)ldo < (long long)heads * dim_head) return AMDNUWA_ERR_ARG;
+    if (heads > 8 || (dim_head != 32 && dim_head != 64)) return AMDNUWA_ERR_UNSUPPORTED;
+    RowsArgs a{};
+    const size_t nf = rows_ws_floats(B, J, heads, dim_head, a.nsplit);
+    if (!workspace || workspace_bytes < nf * sizeof(float)) return AMDNUWA_ERR_WORKSPACE;
+    a.q = q; a.ql = q_lo; a.kv = kv; a.kvl = kv_lo; a.first = pos; a.mask = key_mask; a.nk = null_k; a.nv = null_v;
+    a.wth = w_th; a.bias = nullptr; a.o = o; a.ol = o_lo; a.ldq = ldq; a.ldo = ldo; a.cache_rows = ctx_rows; a.T = J;
+    a.heads = heads; a.dim_head = dim_head; a.scale = scale; a.tab = slot_rows; a.n_pos = n_pos;
+    a.sc = static_cast<float*>(workspace);
+    a.st = a.sc + (size_t)B * heads * (J + 1);
+    a.part = a.st + (size_t)B * a.nsplit * heads * 2;
+    rows_launch<true>(a, B, stream);
     LAUNCH_CHECK();
     return AMDNUWA_OK;
 }

@@ -22,6 +22,8 @@ of one stream see frame t - 1 of the other (np.py:908-1067), which is complete -
 computed, because the sampler alternates one video frame / one audio frame.  DualIncrementalDecoder therefore keeps one
 IncrementalDecoder per modality (own position counter) and links the two at the cross-modality layers: each stream stores its
 layer-input rows projected with the OTHER direction's to_kv, and attends the other stream's stored rows of the matching frame."""
+import os
+
 import torch
 import torch.nn.functional as F
 
@@ -285,13 +287,31 @@ class IncrementalDecoder:
         return out.reshape(B, R, D)
 
 
+XC2_PACKED_MAX_SLOTS = 287          # window slots (+ the null key = 288) the packed key images of amdnuwa_xattn_decode hold
+XC2_DECODE_PACKED_DEFAULT = False   # the side windows of at most XC2_PACKED_MAX_SLOTS slots take when the switch below is not set
+
+
+def xc2_decode_packed():
+    """A/B switch AMDNUWA_XC2_DECODE_PACKED (1 / 0): SparseCross2DNA rows gather + pack their window and attend it with
+    amdnuwa_xattn_decode, as before amdnuwa_cross2dna_decode existed, for windows the packed images hold; read when a row program is built"""
+    return os.environ.get('AMDNUWA_XC2_DECODE_PACKED', '1' if XC2_DECODE_PACKED_DEFAULT else '0') == '1'
+
+
+def cross2dna_slot_rows(nbr, frames):
+    """nbr (tpf, k^2): the in-frame neighbour positions of every feature-map position, -1 = 'same' padding (SparseCross2DNA._nbr) ->
+    int32 (tpf, frames * k^2): the context row of every window slot, slot order (frame, tap) as np.py:855, -1 kept for padding"""
+    tpf = nbr.shape[0]
+    return torch.cat([torch.where(nbr >= 0, nbr + a * tpf, nbr) for a in range(frames)], dim=1).to(torch.int32).contiguous()
+
+
 class _Cross2DNARows:
     """SparseCross2DNA (np.py:761-901) for one new query row per sample (NUWASketch.generate, np.py:2440-2512).  The block is row-wise:
     query row pos (> 0) sits at feature-map position i = (pos - 1) mod fmap^2 and attends to the learned null key + the kernel^2
-    neighbourhood of i in EVERY sketch frame.  to_kv(context) is computed once; per row the window's key / value rows are gathered
-    (index tables on the device, indexed by the device-side position, so the step stays capturable in a HIP graph), packed with
-    amdnuwa_xattn_pack (padding slots and masked sketch tokens through its key mask) and attended with the single-query
-    cross-attention kernel (fp32 softmax, talking heads).  Row 0 (<bos>) attends to ALL context tokens without talking heads
+    neighbourhood of i in EVERY sketch frame.  to_kv(context) is computed once; per row amdnuwa_cross2dna_decode attends the window IN
+    PLACE: it reads the slot table (context row of every slot of every position, -1 = padding) and the position on the device -- the step
+    stays capturable in a HIP graph -- and takes any number of slots.  With AMDNUWA_XC2_DECODE_PACKED=1 a window of at most 287 slots
+    takes the earlier path instead: gather the window's rows, pack them with amdnuwa_xattn_pack (padding slots and masked sketch tokens
+    through its key mask), attend with amdnuwa_xattn_decode.  Row 0 (<bos>) attends to ALL context tokens without talking heads
     (np.py:826-849): B rows of glue arithmetic, as in the training path (ops.XC2Inner).  With every context token masked (the
     second pass of classifier-free guidance) both outputs are constants, computed once."""
 
@@ -304,24 +324,28 @@ class _Cross2DNARows:
         T = ctx_bf.hi.shape[0] // batch
         if T % tpf:
             raise NotImplementedError('cached decoding: the sketch context is not a whole number of frames')
-        fs = T // tpf
-        nbr = mod._nbr.to(dev)                                               # (tpf, k^2) in-frame neighbours, -1 = padding
-        idx = torch.cat([torch.where(nbr >= 0, nbr + a * tpf, torch.zeros_like(nbr)) for a in range(fs)], dim=1)
-        self.win_idx = idx.contiguous()                                      # (tpf, fs * k^2) context rows of every window slot
-        self.win_ok = (nbr >= 0).repeat(1, fs).to(torch.uint8).contiguous()  # 0 = the slot is 'same' padding
-        J = self.win_idx.shape[1]
-        self.xg = K.x_geom(batch, 1, J, h, dh)
-        if self.xg.JP > 288:
-            raise NotImplementedError('cached decoding: SparseCross2DNA window too large for the single-query kernel')
+        self.slot_rows = cross2dna_slot_rows(mod._nbr.to(dev), T // tpf)     # (tpf, fs * k^2) context rows of every window slot
+        J = self.slot_rows.shape[1]
+        self.packed = xc2_decode_packed() and J <= XC2_PACKED_MAX_SLOTS
         p = mod._params()
         self.nk, self.nv = p[0].detach().reshape(h, dh).contiguous(), p[1].detach().reshape(h, dh).contiguous()
         self.wth = p[2].detach().reshape(h, h).contiguous()
         self.mask_u8 = mask_u8 if mask_u8 is not None else torch.ones((batch, T), dtype=torch.uint8, device=dev)
         self.o_const = self.o_bos = self.kv = None
+        if self.packed:
+            self.win_idx = self.slot_rows.clamp(min=0).long()
+            self.win_ok = (self.slot_rows >= 0).to(torch.uint8)              # 0 = the slot is 'same' padding
+            self.xg = K.x_geom(batch, 1, J, h, dh)
         if all_masked:
-            kv0 = K.zeros_bf((batch * J, 2 * self.inner), dev, lo=lo)
-            pk = K.xattn_pack(self.xg, kv0, self.nk, self.nv, torch.zeros((batch, J), dtype=torch.uint8, device=dev))
-            self.o_const = K.xattn_decode(self.xg, K.zeros_bf((batch, self.inner), dev, lo=lo), pk, self.wth)
+            q0 = K.zeros_bf((batch, self.inner), dev, lo=lo)
+            if self.packed:
+                kv0 = K.zeros_bf((batch * J, 2 * self.inner), dev, lo=lo)
+                pk = K.xattn_pack(self.xg, kv0, self.nk, self.nv, torch.zeros((batch, J), dtype=torch.uint8, device=dev))
+                self.o_const = K.xattn_decode(self.xg, q0, pk, self.wth)
+            else:                                                            # every row hidden: none is read
+                self.o_const = K.cross2dna_decode(q0, K.zeros_bf((batch, T, 2 * self.inner), dev, lo=lo), self.slot_rows,
+                                                  torch.ones(1, dtype=torch.int32, device=dev), h, dh, self.nk, self.nv, self.wth,
+                                                  mask_u8=torch.zeros((batch, T), dtype=torch.uint8, device=dev), scale=mod.scale)
             self.o_bos = ops._to_bf(self.nv.float().reshape(1, self.inner).expand(batch, -1).contiguous())      # softmax over the null key alone
         else:
             W = ops.XInner.weights(mod._cache, p)
@@ -342,6 +366,9 @@ class _Cross2DNARows:
             o0 = P0[..., :1] * self.nv.float()[None] + torch.einsum('bht,bthd->bhd', P0[..., 1:], kvf[:, :, 1])
             o = ops._to_bf(o0.reshape(B, inner).contiguous())
             return o if self.lo else K.BF(o.hi, None)
+        if not self.packed:
+            return K.cross2dna_decode(q, self.kv, self.slot_rows, pos_dev, hd, dh, self.nk, self.nv, self.wth, mask_u8=self.mask_u8,
+                                      scale=mod.scale)
         i = torch.remainder(pos_dev.long() - 1, self.tpf)                    # device-side feature-map position of this row
         idx = self.win_idx.index_select(0, i)[0]
         J = idx.shape[0]

@@ -1288,6 +1288,30 @@ def attn_decode_rows(q, kv, first_dev, T, heads, dim_head, null_k, null_v, wth, 
     return o
 
 
+def cross2dna_decode(q, kv, slot_rows, pos_dev, heads, dim_head, null_k, null_v, wth, mask_u8=None, scale=None):
+    """single-query SparseCross2DNA over a window read in place: q BF [B, inner] (unscaled); kv BF [B, ctx_rows, 2 * inner] (k | v);
+    slot_rows int32 [n_pos, J] on the device: the context row of every window slot of every feature-map position, -1 = padding; pos_dev
+    int32 [1] on the device: the decoder row of the query (>= 1); null_k / null_v fp32 [heads, dim_head]; wth fp32 [heads, heads]; mask_u8
+    [B, ctx_rows] or None.  Returns o BF [B, inner]"""
+    L = _lib.lib()
+    _chk_dev(q.hi, kv.hi, slot_rows, pos_dev, null_k, null_v, wth, mask_u8)
+    B, inner = q.hi.shape[0], heads * dim_head
+    assert kv.hi.dim() == 3 and kv.hi.is_contiguous() and kv.hi.shape[0] == B and kv.hi.shape[2] == 2 * inner
+    assert (q.lo is None) == (kv.lo is None) and (kv.lo is None or kv.lo.is_contiguous())
+    ctx_rows = kv.hi.shape[1]
+    assert slot_rows.dtype == torch.int32 and slot_rows.dim() == 2 and slot_rows.is_contiguous() and pos_dev.dtype == torch.int32
+    assert mask_u8 is None or (mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (B, ctx_rows) and mask_u8.is_contiguous())
+    n_pos, J = slot_rows.shape
+    o = empty_bf((B, inner), q.hi.device, lo=q.lo is not None)
+    nb = L.amdnuwa_cross2dna_decode_workspace_bytes(B, J, heads, dim_head)
+    ws = workspace(nb, q.hi.device)
+    check(L.amdnuwa_cross2dna_decode(B, J, heads, dim_head, dim_head ** -0.5 if scale is None else scale, _p(q.hi), _p(q.lo),
+                                     q.hi.stride(0), _p(kv.hi), _p(kv.lo), ctx_rows, _p(slot_rows), n_pos, _p(pos_dev), _p(mask_u8),
+                                     _p(null_k), _p(null_v), _p(wth), _p(o.hi), _p(o.lo), inner, _p(ws), nb, _stream()),
+          'amdnuwa_cross2dna_decode')
+    return o
+
+
 def x_geom(B, n, T, heads, dim_head):
     g = XGeom()
     g.B, g.n, g.T = B, n, T
