@@ -39,7 +39,8 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 *     window kernels -- amdnuwa_s3_geom / amdnuwa_s3_supported below: a wider accepted range, no signature or struct change;
                                                 *     amdnuwa_attn_decode_rows and its _workspace_bytes were added at 21 as well: purely additive; so were amdnuwa_prefill_ln and
                                                 *     amdnuwa_prefill_kv, the cache prefill of a sliding generate() window, and amdnuwa_cross2dna_decode with its
-                                                *     _workspace_bytes, the single-query SparseCross2DNA over a window of any size) */
+                                                *     _workspace_bytes, the single-query SparseCross2DNA over a window of any size, and amdnuwa_sample_next_row, the
+                                                *     sampling tail of a generate() token) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -652,6 +653,22 @@ int amdnuwa_cross2dna_decode(int B, int J, int heads, int dim_head, float scale,
                              const uint16_t* kv, const uint16_t* kv_lo, int ctx_rows, const int* slot_rows, int n_pos, const int* pos,
                              const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o,
                              uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
+/* The end of one generate() token on the device (np.py:55-65, 1713-1720, 1883-1908; added at ABI 21, purely additive): sample a class from
+ * the guided logits and assemble the decoder input row that follows.  logits [B][ld] fp32 (C classes, ld >= C); keep >= 1, keep <= C;
+ * temperature > 0; u [B][keep] fp32 uniforms, NULL exactly when keep == 1; emb [C][D] and pos [P][D] fp32; pos_idx [cap] int32 and step [1]
+ * int32 in DEVICE memory; ids [B][cap] int64; x_next [B][D] fp32.  With t = step[0]:
+ *   1. the keep largest logits of each row in descending order, equal values by lower class index first (-0 counts as +0, NaN as the largest);
+ *   2. score_j = v_j / temperature + g(u[b][j]) for the rank-j logit v_j, g(u) = -logf(max(-logf(max(u, 1e-20)), 1e-20));
+ *   3. the FIRST maximum of the scores (keep == 1: the largest logit itself, nothing is drawn);
+ *   4. ids[b][t] = its class, x_next[b] = emb[class] + pos[pos_idx[t]] (one fp32 add per element).
+ * t outside [0, cap) or pos_idx[t] outside [0, P) writes NOTHING, in every workgroup alike.  step is read, never advanced: the caller advances
+ * it on the stream (inside its captured graph), so that one captured launch serves every token.  One workgroup per sample, no atomics, every
+ * reduction of a fixed shape: two runs are bit-identical.  No workspace.  Arguments are checked first (a null pointer, a non-positive size,
+ * keep outside [1, C], ld < C, u given with keep == 1 or missing otherwise, a temperature that is not a positive finite number:
+ * AMDNUWA_ERR_ARG); then the envelope: C <= 16384, D % 4 == 0, emb / pos / x_next 16-byte aligned, otherwise AMDNUWA_ERR_UNSUPPORTED. */
+int amdnuwa_sample_next_row(int B, int C, int keep, float temperature, const float* logits, int ld, const float* u, const float* emb,
+                            int D, const float* pos, int P, const int* pos_idx, int cap, const int* step, long long* ids, float* x_next,
+                            amdnuwa_stream stream);
 
 /* ---- frozen VQGanVAE tokenizer (VQGanVAE.get_video_indices -> encode, reference vqgan_vae.py:431-435, 452-458), exact fp32 ---- */
 typedef struct {

@@ -618,12 +618,31 @@ class DualGuidedStepper:
         return self.glogits[which].clone()
 
 
+def position_schedule(tokens_per_frame, max_frames, total):
+    """int32 [total] (host): entry t = the position-embedding row of the decoder input that FOLLOWS step t -- the window index of the token
+    step t samples, slide_plan(t + 1)[0] - 1 (inside the window simply t)"""
+    from .nuwa_pytorch import slide_plan
+    return torch.tensor([slide_plan(t + 1, tokens_per_frame, max_frames)[0] - 1 for t in range(total)], dtype=torch.int32)
+
+
+def kept_logits(filter_thres, num_classes):
+    """how many of the largest logits sample_top_fraction keeps"""
+    return max(int((1 - filter_thres) * num_classes), 1)
+
+
 class GuidedStepper:
     """The per-token work of NUWA.generate (and NUWASketch.generate, np.py:2440-2512: same decoder, sketch context): conditioned pass -> logits; if cond_scale != 1 the reference feeds the final-normed
     conditioned OUTPUT row into a second, text-masked pass (np.py:1894-1898) and mixes the two logits.  One call = one new row.
-    graph=True captures the step in a HIP graph after a warm-up call (static input / output buffers, device-side position)."""
+    graph=True captures the step in a HIP graph after a warm-up call (static input / output buffers, device-side position).
 
-    def __init__(self, nuwa, text_embeds, text_mask, max_rows, cond_scale, graph=True):
+    sampler = dict(total, tokens_per_frame, max_frames, filter_thres, temperature) adds the SAMPLING TAIL of the token to the step
+    (amdnuwa_sample_next_row, the last launch of _body and so of the captured graph): it samples the token from the guided logits as
+    nuwa_pytorch.sample_top_fraction does, writes it to column t of `ids` [B, total] and leaves the next decoder input row -- token
+    embedding + position row pos_idx[t] -- in x_in; t is the device-side counter step_dev, advanced inside the graph like pos_dev.  The
+    caller then drives the whole call with advance(): per token one draw of the uniforms `u` (none when one logit is kept) and one replay.
+    A shape the kernel does not take leaves device_sampler False and the caller on the torch tail."""
+
+    def __init__(self, nuwa, text_embeds, text_mask, max_rows, cond_scale, graph=True, sampler=None):
         dev = text_embeds.device
         B, D = text_embeds.shape[0], text_embeds.shape[-1]
         self.nuwa, self.cond_scale, self.max_rows = nuwa, cond_scale, max_rows
@@ -638,6 +657,30 @@ class GuidedStepper:
         self.graph = None
         self._want_graph = graph
         self._calls = 0
+        self.device_sampler = False
+        if sampler is not None:
+            self._init_sampler(B, dev, **sampler)
+
+    def _init_sampler(self, B, dev, total, tokens_per_frame, max_frames, filter_thres, temperature):
+        nuwa = self.nuwa
+        if not 0 < temperature < float('inf'):         # the kernel refuses it as an argument; the torch tail does what it always did
+            return
+        self.emb = nuwa.image_embedding.embed.weight.detach()
+        self.pos_table = nuwa.video_pos_emb().detach().contiguous()
+        C = nuwa.to_logits.weight.shape[0]
+        self.keep, self.temperature = kept_logits(filter_thres, C), float(temperature)
+        self.ids = torch.zeros((B, total), dtype=torch.int64, device=dev)
+        self.u = torch.zeros((B, self.keep), dtype=torch.float32, device=dev) if self.keep > 1 else None
+        self.pos_idx = position_schedule(tokens_per_frame, max_frames, total).to(dev)
+        self.step_dev = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        # one launch at step -1 (out of range: nothing is written) asks the kernel whether it takes this shape
+        probe = torch.zeros((B, C), dtype=torch.float32, device=dev)
+        self.device_sampler = self.emb.shape[0] >= C and self.emb.is_contiguous() and self._sample(probe, allow_unsupported=True)
+        self.step_dev.zero_()
+
+    def _sample(self, logits, allow_unsupported=False):
+        return K.sample_next_row(logits, self.keep, self.temperature, self.u, self.emb, self.pos_table, self.pos_idx, self.step_dev,
+                                 self.ids, self.x_in, allow_unsupported=allow_unsupported)
 
     def _body(self, bos=False):
         nuwa = self.nuwa
@@ -649,6 +692,9 @@ class GuidedStepper:
             ul = nuwa._final(uh[:, None])[:, 0]
             logits = ul + (logits - ul) * self.cond_scale
         self.pos_dev += 1
+        if self.device_sampler:                        # the token and the next input row: x_in is read above, rewritten here
+            self._sample(logits)
+            self.step_dev += 1
         return logits
 
     def prefill(self, rows):
@@ -668,6 +714,20 @@ class GuidedStepper:
     def __call__(self, x_row):
         """x_row fp32 [B, D] = decoder input row at the current position -> logits [B, C] for the next token"""
         self.x_in.copy_(x_row)
+        return self._run()
+
+    def advance(self, x_row=None):
+        """device_sampler: one whole token -- the row step on x_in (x_row: the <bos> row of the first call; afterwards the row the step
+        before left there), the sample into ids[:, t] and the next input row.  The uniforms are drawn here, outside the graph, from the
+        default generator exactly as sample_top_fraction's torch.rand_like(vals) draws them (same shape, same dtype; the row step between
+        the two draws nothing), so a seeded call samples what the torch tail samples"""
+        if x_row is not None:
+            self.x_in.copy_(x_row)
+        if self.u is not None:
+            self.u.uniform_()
+        self._run()
+
+    def _run(self):
         first = self._calls == 0
         self._calls += 1
         if first and self.cond.bos_row_differs:        # NUWASketch: the <bos> row of a SparseCross2DNA block is its own program --
@@ -680,8 +740,12 @@ class GuidedStepper:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
+                x_keep = self.x_in.clone() if self.device_sampler else None
                 self._body()
                 self.pos_dev -= 1
+                if self.device_sampler:                # the warm-up's tail has replaced the input row and counted a token: both back
+                    self.x_in.copy_(x_keep)            # (the id it wrote is rewritten by the real step, from the same uniforms)
+                    self.step_dev -= 1
             torch.cuda.current_stream().wait_stream(s)
             try:
                 self.graph = torch.cuda.CUDAGraph()

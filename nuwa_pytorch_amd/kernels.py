@@ -1312,6 +1312,31 @@ def cross2dna_decode(q, kv, slot_rows, pos_dev, heads, dim_head, null_k, null_v,
     return o
 
 
+def sample_next_row(logits, keep, temperature, u, emb, pos, pos_idx, step_dev, ids, x_next, allow_unsupported=False):
+    """the sampling tail of one generate() token, in place: logits fp32 [B, C] (rows may be pitched); u fp32 [B, keep] uniforms, None exactly
+    when keep == 1; emb fp32 [>= C, D]; pos fp32 [P, D]; pos_idx int32 [cap] and step_dev int32 [1] on the device; ids int64 [B, cap] and
+    x_next fp32 [B, D] are WRITTEN: ids[:, t] = the sampled class, x_next = emb[class] + pos[pos_idx[t]], t = step_dev[0] (nothing when t or
+    pos_idx[t] is out of range; step_dev is not advanced).  Returns True; with allow_unsupported a shape outside the kernel's envelope
+    returns False instead of raising (decode.GuidedStepper then keeps the torch tail)"""
+    L = _lib.lib()
+    _chk_dev(logits, u, emb, pos, pos_idx, step_dev, ids, x_next)
+    B, Cn = logits.shape
+    D = emb.shape[1]
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and emb.dtype == torch.float32 and pos.dtype == torch.float32
+    assert emb.is_contiguous() and pos.is_contiguous() and emb.shape[0] >= Cn and pos.shape[1] == D
+    assert pos_idx.dtype == torch.int32 and pos_idx.dim() == 1 and pos_idx.is_contiguous() and step_dev.dtype == torch.int32
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and tuple(ids.shape) == (B, pos_idx.shape[0])
+    assert x_next.dtype == torch.float32 and x_next.is_contiguous() and tuple(x_next.shape) == (B, D)
+    assert u is None or (u.dtype == torch.float32 and u.is_contiguous() and tuple(u.shape) == (B, keep))
+    rc = L.amdnuwa_sample_next_row(B, Cn, keep, temperature, _p(logits), logits.stride(0) if B > 1 else max(logits.stride(0), Cn), _p(u),
+                                   _p(emb), D, _p(pos), pos.shape[0], _p(pos_idx), pos_idx.shape[0], _p(step_dev), _p(ids), _p(x_next),
+                                   _stream())
+    if allow_unsupported and rc == -2:
+        return False
+    check(rc, 'amdnuwa_sample_next_row')
+    return True
+
+
 def x_geom(B, n, T, heads, dim_head):
     g = XGeom()
     g.B, g.n, g.T = B, n, T

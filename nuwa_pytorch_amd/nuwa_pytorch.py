@@ -1118,6 +1118,8 @@ class NUWA(nn.Module):
     generate_use_graph = True        # replay each token's decoder work as one captured HIP graph
     generate_slide_cache = True      # num_frames > max_video_frames: keep the cached rows and prefill the caches at every slide of the
                                      # frame window; False = the whole call on the recompute loop (A/B switch)
+    generate_device_sampler = True   # cached path: the sample, the id write and the next input row by amdnuwa_sample_next_row at the end
+                                     # of the (captured) row step; False = sample_top_fraction + cat + embedding as eager torch launches
 
     # -- text side (adjacent, row f1) ------------------------------------------------------------
     def embed_text(self, text, mask=None):
@@ -1200,13 +1202,26 @@ class NUWA(nn.Module):
             from .decode import GuidedStepper
             # rows: <bos> + the tokens behind the last step; at n = window tokens the window has not slid yet and holds window + 1 rows
             max_rows = total if total <= window else window + 1
+            sampler = dict(total=total, tokens_per_frame=tpf, max_frames=max_frames, filter_thres=filter_thres,
+                           temperature=temperature) if self.generate_device_sampler else None
             try:                                 # plain and reversible decoder alike; a block outside the single-row kernels -> recompute
-                stepper = GuidedStepper(self, text_embeds, text_mask, max_rows, cond_scale, graph=self.generate_use_graph)
+                stepper = GuidedStepper(self, text_embeds, text_mask, max_rows, cond_scale, graph=self.generate_use_graph, sampler=sampler)
             except NotImplementedError:
                 cached = False
         if cached:
             pos_table = self.video_pos_emb()
             row = self.video_bos[None].expand(batch, -1)
+        if cached and stepper.device_sampler:
+            # the whole token on the device: the step's last launch samples into stepper.ids and leaves the next input row in place
+            for t in range(total):
+                keep, slid = slide_plan(t, tpf, max_frames)
+                if slid:                         # (as below; the kept tokens come from the id buffer)
+                    rows = torch.cat((self.video_bos[None, None].expand(batch, 1, -1),
+                                      self.image_embedding(stepper.ids[:, t - keep:t - 1]) + pos_table[:keep - 1]), dim=1)
+                    stepper.prefill(rows)
+                stepper.advance(row if t == 0 else None)
+            self.last_generated_ids = ids = stepper.ids
+            return self._ids_to_frames(ids, decode_max_batchsize)
         for t in range(total):
             if cached:
                 keep, slid = slide_plan(t, tpf, max_frames)
@@ -1299,6 +1314,7 @@ class NUWASketch(nn.Module):
 
     generate_use_cache = True               # key/value-cached generate() (decode.py); False = the reference's recompute loop
     generate_use_graph = True               # replay each token's decoder work (rows >= 1) as one captured HIP graph
+    generate_device_sampler = True          # cached path: sample + id write + next input row on the device, as NUWA.generate_device_sampler
     embed_video = NUWA.embed_video          # <bos> + positional + token embedding, one libamdnuwa node
     _final = NUWA._final                    # final StableLayerNorm + logits (+ cross entropy), fused
     _guided_last_logits = NUWA._guided_last_logits
@@ -1339,13 +1355,20 @@ class NUWASketch(nn.Module):
         cached = self.generate_use_cache and sketch.is_cuda and total <= tpf * self.max_video_frames
         if cached:
             from .decode import GuidedStepper
+            sampler = dict(total=total, tokens_per_frame=tpf, max_frames=self.max_video_frames, filter_thres=filter_thres,
+                           temperature=temperature) if self.generate_device_sampler else None
             try:
-                stepper = GuidedStepper(self, sketch_embeds, context_mask, total, cond_scale, graph=self.generate_use_graph)
+                stepper = GuidedStepper(self, sketch_embeds, context_mask, total, cond_scale, graph=self.generate_use_graph, sampler=sampler)
             except NotImplementedError:
                 cached = False
         if cached:
             pos_table = self.video_pos_emb()
             row = self.video_bos[None].expand(batch, -1)
+        if cached and stepper.device_sampler:            # the whole token on the device (the <bos> row: an eager first call, as below)
+            for t in range(total):
+                stepper.advance(row if t == 0 else None)
+            self.last_generated_ids = ids = stepper.ids
+            return self._ids_to_frames(ids, decode_max_batchsize)
         for t in range(total):
             if cached:
                 logits = stepper(row)

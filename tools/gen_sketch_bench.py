@@ -2,7 +2,8 @@
 """NUWASketch.generate on one MI355X (dim 512, 12 decoder layers, 5 x 16 x 16 video tokens, 2 sketch frames, SparseCross2DNA kernel 3):
 per-token cost of the row-at-a-time decoder (decode.GuidedStepper; rows >= 1 replayed as a HIP graph, or launched eagerly) against
 the reference's algorithm -- recompute the whole prefix, twice with guidance -- on the same training kernels.
-  python tools/gen_sketch_bench.py [--batch 4] [--tokens 96]"""
+  python tools/gen_sketch_bench.py [--batch 4] [--tokens 96]
+--sampler-ab ROUNDS: instead, whole guided tokens with generate_device_sampler off and on, alternated ROUNDS times (gen_bench.sampler_ab)."""
 import argparse
 import os
 import sys
@@ -11,6 +12,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import nuwa_pytorch_amd as A  # noqa: E402
 from nuwa_pytorch_amd.decode import GuidedStepper  # noqa: E402
 
@@ -20,6 +22,8 @@ def main():
     ap.add_argument('--batch', type=int, default=4)
     ap.add_argument('--tokens', type=int, default=96)
     ap.add_argument('--cond-scale', type=float, default=2.)
+    ap.add_argument('--sampler-ab', type=int, default=0, metavar='ROUNDS',
+                    help='only the A/B of the sampling tail: ROUNDS alternations of generate_device_sampler off / on in this process')
     args = ap.parse_args()
     dev = 'cuda'
     torch.manual_seed(0)
@@ -32,6 +36,12 @@ def main():
     g = torch.Generator().manual_seed(1)
     sketch = torch.rand(b, 2, 3, 256, 256, generator=g).to(dev)
     ids = torch.randint(0, 8192, (b, N), generator=g).to(dev)
+    if args.sampler_ab:
+        from gen_bench import sampler_ab
+        with torch.no_grad():
+            ctx, cmask = m.embed_sketch(sketch)
+            sampler_ab(m, ctx, cmask, args, 256, 5, f'NUWASketch, b={b}')
+        return
     with torch.no_grad():
         ctx, cmask = m.embed_sketch(sketch)
         rows = m.embed_video(ids[:, :args.tokens])
