@@ -12,9 +12,10 @@ so the per-token work of a whole guided step can be captured once in a HIP graph
 
 Past max_video_frames NUWA.generate slides its frame window (np.py:1873-1881): every kept token moves one frame earlier, its position
 embedding changes and with it every cached row of every layer.  IncrementalDecoder.prefill / GuidedStepper.prefill rebuild the caches
-with ONE full-sequence pass over the rows the new window already determines -- the mirror of step() over R rows, on the rows forms of
-the two norm / cache kernels (amdnuwa_prefill_ln, amdnuwa_prefill_kv) and the full-sequence attention cores of the training path, in
-the operand forms step() uses -- after which the captured row step serves the new frame's tokens again.
+with ONE full-sequence pass over the rows the new window already determines -- the same block walk as step() (IncrementalDecoder._walk)
+in its R-rows mode: the rows forms of the two norm / cache kernels (amdnuwa_prefill_ln, amdnuwa_prefill_kv) and the full-sequence
+attention cores of the training path, in the operand forms of the single row -- after which the captured row step serves the new
+frame's tokens again.
 
 NUWAVideoAudio.generate (np.py:2111-2222) decodes two interleaved streams through the DualModalityDecoder (np.py:1299-1487).  Every
 stage is row-causal there too: the audio window attention looks back only, and the chunked video <-> audio attention lets frame t
@@ -23,6 +24,7 @@ computed, because the sampler alternates one video frame / one audio frame.  Dua
 IncrementalDecoder per modality (own position counter) and links the two at the cross-modality layers: each stream stores its
 layer-input rows projected with the OTHER direction's to_kv, and attends the other stream's stored rows of the matching frame."""
 import os
+from functools import partial
 
 import torch
 import torch.nn.functional as F
@@ -35,7 +37,7 @@ class _Block:
     """one sub-block of a row program: out_slot <- out_slot + post(inner(pre(in_slot)));  pre / post = None for the un-normed modules
     of the reversible dual decoder's cross-modality layer"""
     __slots__ = ('kind', 'pre', 'post', 'inner', 'fmap', 'hcache', 'kvcache', 'geom', 'pk', 'xg', 'o_const', 'xm', 'src', 'dst',
-                 'store_before', 'store_after', 'c2')
+                 'store_before', 'store_after', 'c2', 'wth', 'rel')
 
 
 def _cast_row(x, lo):
@@ -44,27 +46,71 @@ def _cast_row(x, lo):
     return out
 
 
+def _row_program(dec, context, xm=None):
+    """The row program of a decoder: ({stream: [block spec, ...]}, halves, combine); a single-stream decoder is stream 'v'.  A spec is the
+    dict IncrementalDecoder's `block_list` takes: `mod`, `context`, `xm`, `dst`, `store_before` / `store_after`.
+    Transformer: (attention, cross-attention, feed-forward) per layer, one residual.  ReversibleTransformer (np.py:1184-1295): (f, g) pairs,
+    y1 = x1 + f(x2), y2 = x2 + g(y1), output = the SUM of the halves.  DualModalityDecoder (np.py:1299-1487) and
+    ReversibleDualModalityDecoder (np.py:1489-1655 + reversible_video_audio.py; output = the mean of the halves): two streams, linked at
+    the cross-modality layers through xm(module, context stream) -> _XmDirection."""
+    from .nuwa_pytorch import ReversibleTransformer, ShiftVideoTokens, Transformer
+    from .video_audio import DualModalityDecoder, ReversibleDualModalityDecoder
+    v, a = [], []
+    if isinstance(dec, Transformer):
+        v += [dict(mod=sn, context=ctx_arg) for attn, cross, ff in dec.layers
+              for sn, ctx_arg in ((attn, None), (cross, context), (ff, None)) if sn is not None]
+        return {'v': v}, 1, 0.5                     # (one residual: nothing to combine)
+    if isinstance(dec, ReversibleTransformer):
+        for f, g in dec.layers:
+            is_cross = not isinstance(f.fn, ShiftVideoTokens)
+            v += [dict(mod=f, context=context if is_cross else None, dst=0), dict(mod=g, dst=1)]
+        return {'v': v}, 2, 1.0
+    if isinstance(dec, DualModalityDecoder):
+        for blocks, kind in zip(dec.layers, dec.layer_types):
+            if kind == 'intra_modality':
+                for lst, (attn, cross, ff) in zip((v, a), blocks):
+                    lst += [dict(mod=attn), dict(mod=cross, context=context), dict(mod=ff)]
+            else:                               # both directions read the layer INPUT of the other stream (np.py:1467-1470)
+                (v_x, v_ff), (a_x, a_ff) = blocks
+                v_from_a, a_from_v = xm(v_x.fn, 'a'), xm(a_x.fn, 'v')
+                v += [dict(mod=v_x, xm=v_from_a, store_before=(a_from_v,)), dict(mod=v_ff)]
+                a += [dict(mod=a_x, xm=a_from_v, store_before=(v_from_a,)), dict(mod=a_ff)]
+        return {'v': v, 'a': a}, 1, 0.5
+    if isinstance(dec, ReversibleDualModalityDecoder):
+        for (f, g, j, k), kind in zip(dec.layers, dec.layer_types):
+            if kind == 'intra_modality_self_attn':
+                v += [dict(mod=f, dst=0), dict(mod=g, dst=1)]
+                a += [dict(mod=j, dst=0), dict(mod=k, dst=1)]
+            elif kind == 'intra_modality_cross_attn':
+                v += [dict(mod=f, context=context, dst=0), dict(mod=g, dst=1)]
+                a += [dict(mod=j, context=context, dst=0), dict(mod=k, dst=1)]
+            else:
+                # un-normed modules; video: y1 = x1 + f(x2, ctx = audio m2), y2 = x2 + k(y1); audio: n1 = m1 + j(m2, ctx = the
+                # UPDATED video half y2), n2 = m2 + g(n1) -- `k` / `g` crossed over as in reversible_video_audio.py:241-244
+                v_from_a, a_from_v = xm(f, 'a'), xm(j, 'v')
+                v += [dict(mod=f, xm=v_from_a, dst=0), dict(mod=k, dst=1, store_after=(a_from_v,))]
+                a += [dict(mod=j, xm=a_from_v, dst=0, store_before=(v_from_a,)), dict(mod=g, dst=1)]
+        return {'v': v, 'a': a}, 2, 0.5
+    raise NotImplementedError(type(dec).__name__)
+
+
 class IncrementalDecoder:
-    """One decoder pass (conditioned or not) over a growing sequence.  transformer: nuwa_pytorch.Transformer (non-reversible)
+    """One decoder pass (conditioned or not) over a growing sequence.  transformer: nuwa_pytorch.Transformer or ReversibleTransformer
     whose blocks are all on the fused HIP path; context [B, T, D] fp32 and context_mask [B, T] bool as in Transformer.forward.
 
-    Instead of `transformer`, `block_list` gives the row program explicitly: dicts with `mod` (a SandwichNorm block, or a bare
-    FeedForward / CrossModalityCrossAttention), optional `context` (text rows for a cross-attention), `xm` (_XmDirection this block
-    attends through), `dst` (the residual half it adds into: reversible stacks keep two, np.py's reversible.py; the block reads the
-    OTHER half), `store_before` / `store_after` (_XmDirection objects that take this row's input / output as context); `combine`
-    scales the sum of the two halves at the end (1 for the ReversibleTransformer, which is detected and laid out here; 0.5 for the
-    reversible dual decoder)."""
+    Instead of `transformer`, `block_list` gives the row program explicitly (_row_program lays out all four decoders): dicts with `mod`
+    (a SandwichNorm block, or a bare FeedForward / CrossModalityCrossAttention), optional `context` (text rows for a cross-attention), `xm`
+    (_XmDirection this block attends through), `dst` (the residual half it adds into: reversible stacks keep two, np.py's reversible.py;
+    the block reads the OTHER half), `store_before` / `store_after` (_XmDirection objects that take this row's input / output as context);
+    `combine` scales the sum of the two halves at the end (1 for the ReversibleTransformer, 0.5 for the reversible dual decoder)."""
 
     def __init__(self, transformer, batch, max_rows, context, context_mask, pos_dev, block_list=None, halves=1, combine=0.5):
         from .nuwa_pytorch import Attention, FeedForward, Sparse3DNA, SandwichNorm, SparseCross2DNA
         from .video_audio import SparseCausal2DNA
         dev = context.device
-        if block_list is None and hasattr(transformer, 'net'):         # ReversibleTransformer (np.py:1184-1295): (f, g) pairs, y1 = x1 +
-            from .nuwa_pytorch import ShiftVideoTokens                  # f(x2), y2 = x2 + g(y1), output = the SUM of the halves
-            block_list, halves, combine = [], 2, 1.0
-            for f, g in transformer.layers:
-                is_cross = not isinstance(f.fn, ShiftVideoTokens)
-                block_list += [dict(mod=f, context=context if is_cross else None, dst=0), dict(mod=g, dst=1)]
+        if block_list is None:
+            lists, halves, combine = _row_program(transformer, context)
+            block_list = lists['v']
         self.B, self.rows, self.pos_dev, self.halves, self.combine = batch, max_rows, pos_dev, halves, combine
         lo = self.lo = K.want_lo()
         D = context.shape[-1]
@@ -74,13 +120,10 @@ class IncrementalDecoder:
         # output is the same row for every position -- (sum_h W_th[g, h]) * null_v[g] -- and is computed once
         all_masked = context_mask is not None and not bool(context_mask.any())
         self.blocks = []
-        if block_list is None:
-            block_list = [dict(mod=sn, context=ctx_arg) for attn, cross, ff in transformer.layers
-                          for sn, ctx_arg in ((attn, None), (cross, context), (ff, None)) if sn is not None]
         for spec in block_list:
             mod, ctx_arg = spec['mod'], spec.get('context')
             blk = _Block()
-            blk.kvcache = blk.geom = blk.pk = blk.xg = blk.o_const = blk.hcache = blk.fmap = blk.c2 = None
+            blk.kvcache = blk.geom = blk.pk = blk.xg = blk.o_const = blk.hcache = blk.fmap = blk.c2 = blk.wth = blk.rel = None
             blk.xm = spec.get('xm')
             blk.dst = spec.get('dst', 0)
             blk.src = (1 - blk.dst) if halves == 2 else 0
@@ -106,18 +149,19 @@ class IncrementalDecoder:
             blk.hcache = K.zeros_bf((batch, max_rows, D), dev, lo=lo) if fmap is not None else None
             if blk.xm is not None:
                 blk.kind = 'xm'
-            elif isinstance(inner, SparseCausal2DNA):               # the audio window attention IS a 3DNA over a (time, 1, 1) grid
-                blk.kind = 's3'
-                blk.geom = K.s3_geom(batch, max_rows, (max(max_rows - 1, 1), 1, 1), (inner.kernel_size[0], 1, 1),
-                                     (inner.dilation[0], 1, 1), inner.heads, inner.dim_head)
-                blk.kvcache = K.zeros_bf((batch, max_rows, 2 * inner.heads * inner.dim_head), dev, lo=lo)
-            elif isinstance(inner, Sparse3DNA):
-                if not inner.causal:
+            elif isinstance(inner, (SparseCausal2DNA, Sparse3DNA)):
+                if isinstance(inner, SparseCausal2DNA):             # the audio window attention IS a 3DNA over a (time, 1, 1) grid
+                    grid = ((max(max_rows - 1, 1), 1, 1), (inner.kernel_size[0], 1, 1), (inner.dilation[0], 1, 1))
+                elif not inner.causal:
                     raise NotImplementedError('IncrementalDecoder needs causal Sparse3DNA')
+                else:
+                    grid = (inner.video_shape, inner.kernel_size, inner.dilation)
                 blk.kind = 's3'
-                blk.geom = K.s3_geom(batch, max_rows, inner.video_shape, inner.kernel_size, inner.dilation, inner.heads,
-                                     inner.dim_head)
+                blk.geom = K.s3_geom(batch, max_rows, *grid, inner.heads, inner.dim_head)
                 blk.kvcache = K.zeros_bf((batch, max_rows, 2 * inner.heads * inner.dim_head), dev, lo=lo)
+                p = inner._params()
+                blk.wth = p[2].detach().reshape(inner.heads, inner.heads).contiguous()
+                blk.rel = p[5].detach().contiguous() if len(p) > 5 else None
             elif isinstance(inner, Attention):
                 if inner.causal:
                     # plain causal self-attention has no cached single-row path: generate() keeps the recompute loop for such stacks
@@ -130,12 +174,13 @@ class IncrementalDecoder:
                 p = inner._params()
                 W = ops.XInner.weights(inner._cache, p)
                 blk.xg = K.x_geom(batch, 1, context.shape[1], inner.heads, inner.dim_head)
+                blk.wth = p[2].detach().reshape(inner.heads, inner.heads).contiguous()
                 kv = K.gemm_nt(ctx_bf, W['kv'], out_bf16=True)                 # text keys / values: once per sequence
                 blk.pk = K.xattn_pack(blk.xg, kv, p[0].detach().reshape(inner.heads, inner.dim_head).contiguous(),
                                       p[1].detach().reshape(inner.heads, inner.dim_head).contiguous(), mask_u8)
                 if all_masked:
                     q0 = K.zeros_bf((batch, inner.heads * inner.dim_head), dev, lo=lo)
-                    blk.o_const = K.xattn_decode(blk.xg, q0, blk.pk, p[2].detach().reshape(inner.heads, inner.heads).contiguous())
+                    blk.o_const = K.xattn_decode(blk.xg, q0, blk.pk, blk.wth)
             elif isinstance(inner, SparseCross2DNA):
                 blk.kind = 'xc2'
                 blk.c2 = _Cross2DNARows(inner, batch, ctx_bf, mask_u8, all_masked, lo)
@@ -146,81 +191,92 @@ class IncrementalDecoder:
             self.blocks.append(blk)
         self.bos_row_differs = any(b.kind == 'xc2' for b in self.blocks)       # row 0 takes another code path: not one graph for all rows
 
-    def _enter(self, x, nxt):
-        """the operand row of block `nxt` from its fp32 input row: pre-norm (+ token shift through the block's cache), or a plain
-        cast for an un-normed block"""
+    def _norm(self, y, resid, post, nxt, R):
+        """-> (x, h).  x = resid + post-norm(y) (post None: none, x = y) and, in the same launch, h = the operand rows of block `nxt`: its
+        pre-norm of x + its token shift through its cache (cache write + gather); h = None when `nxt` is None or un-normed.
+        R None: the row at pos_dev (decode_ln); R: rows 0 .. R-1 of every sample, cache rows [0, R) written (prefill_ln)"""
+        pre, cache, fmap = (nxt.pre, nxt.hcache, nxt.fmap or 0) if nxt is not None and nxt.pre is not None else (None, None, 0)
+        if R is None:
+            return K.decode_ln(y, resid, post, pre, cache=cache, pos_dev=self.pos_dev, fmap=fmap)
+        return K.prefill_ln(y, resid, post, pre, R, cache=cache, fmap=fmap)
+
+    def _enter(self, x, nxt, R):
+        """the operand rows of block `nxt` from its fp32 input rows: pre-norm (+ token shift), or a plain cast for an un-normed block"""
         if nxt is None:
             return None
-        if nxt.pre is None:
-            return _cast_row(x, self.lo)
-        return K.decode_ln(x, None, None, nxt.pre, cache=nxt.hcache, pos_dev=self.pos_dev, fmap=nxt.fmap or 0)[1]
+        return _cast_row(x, self.lo) if nxt.pre is None else self._norm(x, None, None, nxt, R)[1]
 
-    def step(self, x, bos=False):
-        """x fp32 [B, D]: decoder input row `pos` of every sample -> that row after all layers (before the final norm).
-        bos: this is row 0 (only a SparseCross2DNA block cares: its <bos> query attends to the whole context; the position itself
-        lives in device memory and is not read on the host)"""
-        fast = ops._fast()
-        blocks = self.blocks
+    def _walk(self, x, R=None, bos=False):
+        """The one loop over the blocks.  R None: x fp32 [B, D], the row at pos_dev of every sample, single-row kernels against the caches
+        (step).  R: x [B * R, D], sample-major rows 0 .. R-1 (prefill).  The modes differ in _norm and in the attention core of 's3' and
+        'x'; only the single row has 'xm' / 'xc2' blocks and store hooks (prefill refuses them before it gets here)."""
+        B, fast, blocks = self.B, ops._fast(), self.blocks
         state = [x] * self.halves
-        h = self._enter(x, blocks[0])
+        h = self._enter(x, blocks[0], R)
         for i, blk in enumerate(blocks):
             inner = blk.inner
             for d in blk.store_before:
                 d.store(state[blk.src], self.pos_dev)
             raw = blk.post is None                  # (an un-normed block adds its fp32 output itself)
+            out16 = fast and not raw
             if blk.kind == 's3':
                 p = inner._params()
                 W = ops.S3Inner.weights(inner._cache, p)
                 g = blk.geom
-                rel = p[5].detach().contiguous() if len(p) > 5 else None
                 qkv = K.gemm_nt(h, W['qkv'], out_bf16=True)
-                o = K.s3_decode(g, qkv, blk.kvcache, self.pos_dev, p[2].detach().reshape(g.heads, g.heads).contiguous(), rel)
-                y = K.gemm_nt(o, W['out'], bias=p[4].detach(), out_bf16=fast and not raw)
+                if R is None:
+                    o = K.s3_decode(g, qkv, blk.kvcache, self.pos_dev, blk.wth, blk.rel)
+                else:
+                    K.prefill_kv(qkv, blk.kvcache, R)
+                    g = K.s3_geom(B, R, (g.F, g.H, g.W), (g.kf, g.kh, g.kw), (g.df, g.dh, g.dw), g.heads, g.dim_head)
+                    o = K.sparse3dna_fwd(g, qkv, blk.wth, rel_bias=blk.rel)
+                y = K.gemm_nt(o, W['out'], bias=p[4].detach(), out_bf16=out16)
             elif blk.kind == 'xm':
                 y = blk.xm.attend(h)
             elif blk.kind == 'x':
-                p = inner._params()
-                W = ops.XInner.weights(inner._cache, p)
+                W = ops.XInner.weights(inner._cache, inner._params())
                 g = blk.xg
-                wth = p[2].detach().reshape(g.heads, g.heads).contiguous()
-                if blk.o_const is not None:
+                if blk.o_const is not None:         # the all-masked pass: the same row for every position
                     o = blk.o_const
+                    if R is not None:
+                        rep = lambda t: None if t is None else t[:, None].expand(B, R, t.shape[-1]).reshape(B * R, -1).contiguous()
+                        o = K.BF(rep(o.hi), rep(o.lo))
                 else:
                     q = K.gemm_nt(h, W['q'], out_bf16=True)
-                    o = K.xattn_decode(g, q, blk.pk, wth)
-                y = K.gemm_nt(o, W['out'], out_bf16=fast and not raw)
+                    if R is None:
+                        o = K.xattn_decode(g, q, blk.pk, blk.wth)
+                    else:
+                        # blk.pk was packed with an n = 1 geometry: the key images depend on (B, T, heads, dim_head) alone, so R queries attend them
+                        o = K.xattn_fwd(K.x_geom(B, R, g.T, g.heads, g.dim_head), q, blk.pk, blk.wth, save=False)[0]
+                y = K.gemm_nt(o, W['out'], out_bf16=out16)
             elif blk.kind == 'xc2':
                 W = ops.XInner.weights(inner._cache, inner._params())
                 o = blk.c2.attend(h, W, self.pos_dev, bos)
-                y = K.gemm_nt(o, W['out'], out_bf16=fast and not raw)
+                y = K.gemm_nt(o, W['out'], out_bf16=out16)
             else:
                 W = ops.FFInner.weights(inner._cache, inner._params())
                 u = K.gemm_nt(h, W['w1'], out_bf16=True)
                 gg = K.geglu_fwd(u, W['FP'], interleaved=True)
-                y = K.gemm_nt(gg, W['w2'], out_bf16=fast and not raw)
+                y = K.gemm_nt(gg, W['w2'], out_bf16=out16)
             nxt = blocks[i + 1] if i + 1 < len(blocks) else None
             if not raw:
                 # post-norm + residual, the next block's pre-norm and its token shift (cache write + gather): one launch
-                fused = nxt is not None and nxt.pre is not None
-                x, h = K.decode_ln(y, state[blk.dst], blk.post, nxt.pre if fused else None, cache=nxt.hcache if fused else None,
-                                   pos_dev=self.pos_dev, fmap=(nxt.fmap or 0) if fused else 0)
-                if nxt is not None and not fused:
+                x, h = self._norm(y, state[blk.dst], blk.post, nxt, R)
+                if nxt is not None and nxt.pre is None:
                     h = _cast_row(x, self.lo)
             else:
                 x = state[blk.dst] + y
-                h = self._enter(x, nxt)
+                h = self._enter(x, nxt, R)
             state[blk.dst] = x
             for d in blk.store_after:
                 d.store(x, self.pos_dev)
         return x if self.halves == 1 else (state[0] + state[1]) * self.combine
 
-    def _enter_rows(self, x, nxt, R):
-        """_enter for R rows per sample (x fp32 [B*R, D], sample-major): the block's cache rows [0, R) are written"""
-        if nxt is None:
-            return None
-        if nxt.pre is None:
-            return _cast_row(x, self.lo)
-        return K.prefill_ln(x, None, None, nxt.pre, R, cache=nxt.hcache, fmap=nxt.fmap or 0)[1]
+    def step(self, x, bos=False):
+        """x fp32 [B, D]: decoder input row `pos` of every sample -> that row after all layers (before the final norm).
+        bos: this is row 0 (only a SparseCross2DNA block cares: its <bos> query attends to the whole context; the position itself
+        lives in device memory and is not read on the host)"""
+        return self._walk(x, None, bos)
 
     def prefill(self, x_rows):
         """x_rows fp32 [B, R, D]: the decoder input rows 0 .. R-1 of every sample -> those rows after all layers (before the final norm),
@@ -234,57 +290,9 @@ class IncrementalDecoder:
         B, R, D = x_rows.shape
         if B != self.B or not 1 <= R <= self.rows:
             raise ValueError(f'IncrementalDecoder.prefill: {B} x {R} rows do not fit caches of {self.B} x {self.rows} rows')
-        blocks = self.blocks
-        if any(b.kind in ('xm', 'xc2') or b.store_before or b.store_after for b in blocks):
+        if any(b.kind in ('xm', 'xc2') or b.store_before or b.store_after for b in self.blocks):
             raise NotImplementedError('IncrementalDecoder.prefill: no full-sequence cache prefill for cross-modality / SparseCross2DNA blocks')
-        fast = ops._fast()
-        x = x_rows.reshape(B * R, D).contiguous()
-        state = [x] * self.halves
-        h = self._enter_rows(x, blocks[0], R)
-        for i, blk in enumerate(blocks):
-            inner = blk.inner
-            raw = blk.post is None
-            if blk.kind == 's3':
-                p = inner._params()
-                W = ops.S3Inner.weights(inner._cache, p)
-                g0 = blk.geom
-                g = K.s3_geom(B, R, (g0.F, g0.H, g0.W), (g0.kf, g0.kh, g0.kw), (g0.df, g0.dh, g0.dw), g0.heads, g0.dim_head)
-                rel = p[5].detach().contiguous() if len(p) > 5 else None
-                qkv = K.gemm_nt(h, W['qkv'], out_bf16=True)
-                K.prefill_kv(qkv, blk.kvcache, R)
-                o = K.sparse3dna_fwd(g, qkv, p[2].detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel)
-                y = K.gemm_nt(o, W['out'], bias=p[4].detach(), out_bf16=fast and not raw)
-            elif blk.kind == 'x':
-                p = inner._params()
-                W = ops.XInner.weights(inner._cache, p)
-                g0 = blk.xg
-                if blk.o_const is not None:      # the all-masked pass: the same row for every position
-                    rep = lambda t: None if t is None else t[:, None].expand(B, R, t.shape[-1]).reshape(B * R, -1).contiguous()
-                    o = K.BF(rep(blk.o_const.hi), rep(blk.o_const.lo))
-                else:
-                    # blk.pk was packed with an n = 1 geometry: the key images depend on (B, T, heads, dim_head) alone, so R queries attend them
-                    g = K.x_geom(B, R, g0.T, g0.heads, g0.dim_head)
-                    q = K.gemm_nt(h, W['q'], out_bf16=True)
-                    o = K.xattn_fwd(g, q, blk.pk, p[2].detach().reshape(g.heads, g.heads).contiguous(), save=False)[0]
-                y = K.gemm_nt(o, W['out'], out_bf16=fast and not raw)
-            else:
-                W = ops.FFInner.weights(inner._cache, inner._params())
-                u = K.gemm_nt(h, W['w1'], out_bf16=True)
-                gg = K.geglu_fwd(u, W['FP'], interleaved=True)
-                y = K.gemm_nt(gg, W['w2'], out_bf16=fast and not raw)
-            nxt = blocks[i + 1] if i + 1 < len(blocks) else None
-            if not raw:
-                fused = nxt is not None and nxt.pre is not None
-                x, h = K.prefill_ln(y, state[blk.dst], blk.post, nxt.pre if fused else None, R, cache=nxt.hcache if fused else None,
-                                    fmap=(nxt.fmap or 0) if fused else 0)
-                if nxt is not None and not fused:
-                    h = _cast_row(x, self.lo)
-            else:
-                x = state[blk.dst] + y
-                h = self._enter_rows(x, nxt, R)
-            state[blk.dst] = x
-        out = x if self.halves == 1 else (state[0] + state[1]) * self.combine
-        return out.reshape(B, R, D)
+        return self._walk(x_rows.reshape(B * R, D).contiguous(), R).reshape(B, R, D)
 
 
 XC2_PACKED_MAX_SLOTS = 287          # window slots (+ the null key = 288) the packed key images of amdnuwa_xattn_decode hold
@@ -398,7 +406,10 @@ class _XmDirection:
             raise NotImplementedError('cached decoding: this CrossModalityCrossAttention configuration is not on the libamdnuwa path')
         self.mod, self.B, self.lo = mod, batch, lo
         self.c, self.cc = mod.chunk_size, mod.context_chunk_size
-        self.inner = mod.heads * mod.dim_head
+        h, dh = mod.heads, mod.dim_head
+        self.inner = h * dh
+        self.nk, self.nv = mod.null_k.detach().reshape(h, dh).contiguous(), mod.null_v.detach().reshape(h, dh).contiguous()
+        self.wth, self.th_bias = mod.talking_heads.weight.detach().reshape(h, h).contiguous(), mod.talking_heads.bias.detach().contiguous()
         # context rows under mod.to_kv: cc - 1 zero rows (to_kv has no bias), then context row r at cc - 1 + r, so that context
         # frame f is rows [f * cc, (f + 1) * cc)
         self.kv = K.zeros_bf((batch, self.cc - 1 + ctx_rows, 2 * self.inner), dev, lo=lo)
@@ -441,7 +452,7 @@ class _XmDirection:
         kv = K.BF(self.kv.hi[:, sl].reshape(self.B * cc, 2 * self.inner).contiguous(),
                   self.kv.lo[:, sl].reshape(self.B * cc, 2 * self.inner).contiguous() if self.kv.lo is not None else None)
         h, dh = m.heads, m.dim_head
-        K.xattn_pack(self.g, kv, m.null_k.detach().reshape(h, dh).contiguous(), m.null_v.detach().reshape(h, dh).contiguous(), None, out=self.pk)
+        K.xattn_pack(self.g, kv, self.nk, self.nv, None, out=self.pk)
         v = kv.hi[:, self.inner:].float()
         if kv.lo is not None:
             v = v + kv.lo[:, self.inner:].float()
@@ -463,12 +474,10 @@ class _XmDirection:
             self._pack(f)
         W = self._weights()
         q = K.gemm_nt(h, W['q'], out_bf16=True)
-        wth = m.talking_heads.weight.detach().reshape(m.heads, m.heads).contiguous()
         if self.long:
-            o = K.attn_decode_rows(q, self.kv, self.first, self.cc, m.heads, m.dim_head, m.null_k.detach().reshape(m.heads, -1).contiguous(),
-                                   m.null_v.detach().reshape(m.heads, -1).contiguous(), wth, th_bias=m.talking_heads.bias.detach().contiguous())
+            o = K.attn_decode_rows(q, self.kv, self.first, self.cc, m.heads, m.dim_head, self.nk, self.nv, self.wth, th_bias=self.th_bias)
             return K.gemm_nt(o, W['out'], out_bf16=False)
-        o = K.xattn_decode(self.g, q, self.pk, wth)
+        o = K.xattn_decode(self.g, q, self.pk, self.wth)
         return K.gemm_nt(o, W['out'], out_bf16=False) + self.corr
 
 
@@ -478,40 +487,12 @@ class DualIncrementalDecoder:
     takes the decoder input row of the next position of that stream and returns the row after all layers (before the final norm)."""
 
     def __init__(self, dec, batch, rows_v, rows_a, context, context_mask):
-        from .video_audio import DualModalityDecoder, ReversibleDualModalityDecoder
         dev, lo = context.device, K.want_lo()
         self.pos = {'v': torch.zeros(1, dtype=torch.int32, device=dev), 'a': torch.zeros(1, dtype=torch.int32, device=dev)}
-        lists = {'v': [], 'a': []}
-        if isinstance(dec, DualModalityDecoder):
-            halves = 1
-            for blocks, kind in zip(dec.layers, dec.layer_types):
-                if kind == 'intra_modality':
-                    for key, (attn, cross, ff) in zip('va', blocks):
-                        lists[key] += [dict(mod=attn), dict(mod=cross, context=context), dict(mod=ff)]
-                else:                               # both directions read the layer INPUT of the other stream (np.py:1467-1470)
-                    (v_x, v_ff), (a_x, a_ff) = blocks
-                    v_from_a, a_from_v = _XmDirection(v_x.fn, batch, rows_a, dev, lo), _XmDirection(a_x.fn, batch, rows_v, dev, lo)
-                    lists['v'] += [dict(mod=v_x, xm=v_from_a, store_before=(a_from_v,)), dict(mod=v_ff)]
-                    lists['a'] += [dict(mod=a_x, xm=a_from_v, store_before=(v_from_a,)), dict(mod=a_ff)]
-        elif isinstance(dec, ReversibleDualModalityDecoder):
-            halves = 2                              # y1 = x1 + f(x2), y2 = x2 + g(y1) per block; the output is the mean of the halves
-            for (f, g, j, k), kind in zip(dec.layers, dec.layer_types):
-                if kind == 'intra_modality_self_attn':
-                    lists['v'] += [dict(mod=f, dst=0), dict(mod=g, dst=1)]
-                    lists['a'] += [dict(mod=j, dst=0), dict(mod=k, dst=1)]
-                elif kind == 'intra_modality_cross_attn':
-                    lists['v'] += [dict(mod=f, context=context, dst=0), dict(mod=g, dst=1)]
-                    lists['a'] += [dict(mod=j, context=context, dst=0), dict(mod=k, dst=1)]
-                else:
-                    # un-normed modules; video: y1 = x1 + f(x2, ctx = audio m2), y2 = x2 + k(y1); audio: n1 = m1 + j(m2, ctx = the
-                    # UPDATED video half y2), n2 = m2 + g(n1) -- `k` / `g` crossed over as in reversible_video_audio.py:241-244
-                    v_from_a, a_from_v = _XmDirection(f, batch, rows_a, dev, lo), _XmDirection(j, batch, rows_v, dev, lo)
-                    lists['v'] += [dict(mod=f, xm=v_from_a, dst=0), dict(mod=k, dst=1, store_after=(a_from_v,))]
-                    lists['a'] += [dict(mod=j, xm=a_from_v, dst=0, store_before=(v_from_a,)), dict(mod=g, dst=1)]
-        else:
-            raise NotImplementedError(type(dec).__name__)
-        self.streams = {key: IncrementalDecoder(None, batch, rows, context, context_mask, self.pos[key], block_list=lists[key], halves=halves)
-                        for key, rows in (('v', rows_v), ('a', rows_a))}
+        rows = {'v': rows_v, 'a': rows_a}
+        lists, halves, combine = _row_program(dec, context, lambda mod, ctx_stream: _XmDirection(mod, batch, rows[ctx_stream], dev, lo))
+        self.streams = {key: IncrementalDecoder(None, batch, rows[key], context, context_mask, self.pos[key], block_list=lists[key],
+                                                halves=halves, combine=combine) for key in 'va'}
 
     def directions(self, which):
         """(_XmDirection objects this stream QUERIES through, those it STORES context rows for)"""
@@ -539,6 +520,45 @@ class DualIncrementalDecoder:
             d.n_ctx += 1
 
 
+class _CapturedStep:
+    """step(body, checkpoint): `body` -- the device work of one row step, reading and writing persistent buffers only -- captured once in a
+    HIP graph and replayed for every later call.  The first call warms up on a side stream (workspaces, weight caches, lazy module
+    state), puts back what the warm-up moved and captures; the rows the warm-up wrote are rewritten by the real step at the same
+    position.  checkpoint() is called before the warm-up and returns the function that rewinds it (device counters; buffers the body
+    overwrites).  eager (graph switched off by the owner, or set here by a failed capture, which warns once): the body's kernels are
+    launched one by one.  graph: the captured graph or None; the call returns the body's output (replayed: the static buffer the graph
+    writes).  The callables are passed per call, not kept, so that the owner is not part of a reference cycle and its caches are freed
+    with its last reference."""
+
+    def __init__(self, what, eager=False):
+        self.what, self.graph, self.out, self.eager = what, None, None, eager
+
+    def __call__(self, body, checkpoint):
+        if self.eager:
+            return body()
+        if self.graph is None:
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                rewind = checkpoint()
+                body()
+                rewind()
+            torch.cuda.current_stream().wait_stream(s)
+            try:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):               # capture records, it does not execute: the replay below is the step itself
+                    self.out = body()
+                self.graph = g
+            except RuntimeError as e:                   # same kernels, launched one by one
+                import warnings
+                warnings.warn(f'nuwa_pytorch_amd: HIP graph capture of the {self.what} failed ({e}); launching eagerly')
+                self.eager = True
+                torch.cuda.synchronize()
+                return body()
+        self.graph.replay()
+        return self.out
+
+
 class DualGuidedStepper:
     """The per-token work of NUWAVideoAudio.generate: advance(which, x_row) feeds the next input row of one stream and returns the
     logits for that stream's next token; with cond_scale != 1 the final-normed conditioned output row is the input of a second,
@@ -554,9 +574,8 @@ class DualGuidedStepper:
         # One captured HIP graph per stream for its ORDINARY rows (every row but a stream's start token and the first row of a frame,
         # where a cross-modality direction re-packs the other stream's frame on the host): static input / output buffers, positions
         # and context-row writes indexed on the device.
-        self._want_graph = graph
         self.x_in = {k: torch.zeros(B, D, dtype=torch.float32, device=text_embeds.device) for k in 'va'}
-        self.graphs, self.glogits = {}, {}
+        self.captured = {k: _CapturedStep('dual decode step', eager=not graph) for k in 'va'}
 
     def _logits(self, which, hidden):
         m, dec = self.m, self.m.video_audio_transformer
@@ -582,40 +601,27 @@ class DualGuidedStepper:
         if self.uncond is not None:
             self.uncond.tick(which)
 
+    def _checkpoint(self, which):
+        """before a warm-up run of _body(which) -> the function that rewinds it: the stream's position in every pass"""
+        def rewind():
+            for d in (self.cond, self.uncond):
+                if d is not None:
+                    d.pos[which] -= 1
+        return rewind
+
     def advance(self, which, x_row):
         self.x_in[which].copy_(x_row)
-        eager = not self._want_graph or self.cond.needs_eager_row(which) or (self.uncond is not None and self.uncond.needs_eager_row(which))
+        eager = any(c.eager for c in self.captured.values()) or self.cond.needs_eager_row(which) or \
+            (self.uncond is not None and self.uncond.needs_eager_row(which))
         if eager:
             logits = self._body(which)
-            self._tick(which)
-            return logits
-        if which not in self.graphs:
-            # warm-up on a side stream (workspaces, weight caches), positions rewound, then capture; the rows the warm-up wrote are
-            # rewritten by the real step at the same positions
-            decs = [self.cond] + ([self.uncond] if self.uncond is not None else [])
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._body(which)
-                for d in decs:
-                    d.pos[which] -= 1
-            torch.cuda.current_stream().wait_stream(s)
-            try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self.glogits[which] = self._body(which)
-                self.graphs[which] = g
-            except RuntimeError as e:
-                import warnings
-                warnings.warn(f'nuwa_pytorch_amd: HIP graph capture of the dual decode step failed ({e}); launching eagerly')
-                self._want_graph = False
-                torch.cuda.synchronize()
-                logits = self._body(which)
-                self._tick(which)
-                return logits
-        self.graphs[which].replay()
+        else:
+            step = self.captured[which]
+            logits = step(partial(self._body, which), partial(self._checkpoint, which))
+            if step.graph is not None:                  # the graph's static output: the caller keeps a stream's logits across replays
+                logits = logits.clone()
         self._tick(which)
-        return self.glogits[which].clone()
+        return logits
 
 
 def position_schedule(tokens_per_frame, max_frames, total):
@@ -653,9 +659,7 @@ class GuidedStepper:
         if cond_scale != 1:
             self.uncond = IncrementalDecoder(tr, B, max_rows, text_embeds, torch.zeros_like(text_mask).bool(), self.pos_dev)
         self.x_in = torch.zeros(B, D, dtype=torch.float32, device=dev)
-        self.logits = None
-        self.graph = None
-        self._want_graph = graph
+        self._captured = _CapturedStep('decode step', eager=not graph)
         self._calls = 0
         self.device_sampler = False
         if sampler is not None:
@@ -727,35 +731,26 @@ class GuidedStepper:
             self.u.uniform_()
         self._run()
 
+    @property
+    def graph(self):
+        """the captured graph of the row step, or None (graph=False, not captured yet, or the capture failed)"""
+        return self._captured.graph
+
+    def _checkpoint(self):
+        """before a warm-up run of _body -> the function that rewinds it: the position; with the device sampler the warm-up's tail has also
+        replaced the input row and counted a token: both back (the id it wrote is rewritten by the real step, from the same uniforms)"""
+        x_keep = self.x_in.clone() if self.device_sampler else None
+
+        def rewind():
+            self.pos_dev -= 1
+            if self.device_sampler:
+                self.x_in.copy_(x_keep)
+                self.step_dev -= 1
+        return rewind
+
     def _run(self):
         first = self._calls == 0
         self._calls += 1
         if first and self.cond.bos_row_differs:        # NUWASketch: the <bos> row of a SparseCross2DNA block is its own program --
             return self._body(True)                    # launched eagerly; the graph is captured at row 1 and serves every later row
-        if not self._want_graph:
-            return self._body()
-        if self.graph is None:
-            # warm-up on a side stream (weight caches, workspaces, lazy module state), then rewind the position and capture;
-            # the rows the warm-up wrote are rewritten by the real step at that position
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                x_keep = self.x_in.clone() if self.device_sampler else None
-                self._body()
-                self.pos_dev -= 1
-                if self.device_sampler:                # the warm-up's tail has replaced the input row and counted a token: both back
-                    self.x_in.copy_(x_keep)            # (the id it wrote is rewritten by the real step, from the same uniforms)
-                    self.step_dev -= 1
-            torch.cuda.current_stream().wait_stream(s)
-            try:
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):     # capture records, it does not execute: the replay below is step `pos`
-                    self.logits = self._body()
-            except RuntimeError as e:                  # same kernels, launched one by one
-                import warnings
-                warnings.warn(f'nuwa_pytorch_amd: HIP graph capture of the decode step failed ({e}); launching eagerly')
-                self.graph, self._want_graph = None, False
-                torch.cuda.synchronize()
-                return self._body()
-        self.graph.replay()
-        return self.logits
+        return self._captured(self._body, self._checkpoint)

@@ -1190,55 +1190,58 @@ class NUWA(nn.Module):
         Past max_video_frames the reference slides a window over the last frames (np.py:1873-1881): every kept token moves one frame
         earlier, so at a slide the caches are rebuilt by ONE full-sequence pass over the rows the window already determines
         (GuidedStepper.prefill) and the tokens of the new frame are single-row steps again."""
-        batch, device = text.shape[0], text.device
         text_mask = text != 0
         text_embeds = self.embed_text(text, mask=text_mask)
+        total = self.video_fmap_size ** 2 * default(num_frames, self.max_video_frames)
+        return self._sample_video(text_embeds, text_mask, total, filter_thres, temperature, cond_scale, decode_max_batchsize)
+
+    def _sample_video(self, context, context_mask, total, filter_thres, temperature, cond_scale, decode_max_batchsize):
+        """The token loop of generate(): `total` tokens sampled one by one under the condition context [b, T, dim] / context_mask [b, T]
+        -> frames; the ids stay in last_generated_ids.  Cached (decode.GuidedStepper: one new decoder row per token) when generate_use_cache
+        is on, the device is a GPU, every block has a single-row path and the call either stays inside the window or may slide it on a
+        cache prefill (generate_slide_cache); otherwise the reference's recompute loop.  The cached loop ends a token either inside the
+        step (stepper.device_sampler: the step's last launch samples into stepper.ids and leaves the next input row in place) or with
+        the torch tail: sample_top_fraction, cat, embedding + position row."""
+        batch = context.shape[0]
         tpf, max_frames = self.video_fmap_size ** 2, self.max_video_frames
-        total = tpf * default(num_frames, max_frames)
         window = tpf * max_frames
-        ids = torch.empty((batch, 0), device=device, dtype=torch.long)
-        cached = self.generate_use_cache and text.is_cuda and (total <= window or self.generate_slide_cache)
-        if cached:
+        ids = torch.empty((batch, 0), device=context.device, dtype=torch.long)
+        stepper = None
+        if self.generate_use_cache and context.is_cuda and (total <= window or self.generate_slide_cache):
             from .decode import GuidedStepper
             # rows: <bos> + the tokens behind the last step; at n = window tokens the window has not slid yet and holds window + 1 rows
             max_rows = total if total <= window else window + 1
             sampler = dict(total=total, tokens_per_frame=tpf, max_frames=max_frames, filter_thres=filter_thres,
                            temperature=temperature) if self.generate_device_sampler else None
             try:                                 # plain and reversible decoder alike; a block outside the single-row kernels -> recompute
-                stepper = GuidedStepper(self, text_embeds, text_mask, max_rows, cond_scale, graph=self.generate_use_graph, sampler=sampler)
+                stepper = GuidedStepper(self, context, context_mask, max_rows, cond_scale, graph=self.generate_use_graph, sampler=sampler)
             except NotImplementedError:
-                cached = False
-        if cached:
+                pass
+        if stepper is None:
+            for t in range(total):
+                logits = self._guided_last_logits(lookback_window(ids, tpf, max_frames), context, context_mask, cond_scale)
+                ids = torch.cat((ids, sample_top_fraction(logits, filter_thres, temperature)[:, None]), dim=1)
+        else:
+            on_device = stepper.device_sampler
             pos_table = self.video_pos_emb()
             row = self.video_bos[None].expand(batch, -1)
-        if cached and stepper.device_sampler:
-            # the whole token on the device: the step's last launch samples into stepper.ids and leaves the next input row in place
             for t in range(total):
-                keep, slid = slide_plan(t, tpf, max_frames)
-                if slid:                         # (as below; the kept tokens come from the id buffer)
-                    rows = torch.cat((self.video_bos[None, None].expand(batch, 1, -1),
-                                      self.image_embedding(stepper.ids[:, t - keep:t - 1]) + pos_table[:keep - 1]), dim=1)
-                    stepper.prefill(rows)
-                stepper.advance(row if t == 0 else None)
-            self.last_generated_ids = ids = stepper.ids
-            return self._ids_to_frames(ids, decode_max_batchsize)
-        for t in range(total):
-            if cached:
                 keep, slid = slide_plan(t, tpf, max_frames)
                 if slid:
                     # the rows embed_video(lookback_window(ids)) has, a row's position-embedding index being its index inside the window:
-                    # rows 0 .. keep - 1 (<bos> + all but the newest token) refill the caches; row keep (`row`, made below at the
-                    # end of the step before with its window index) is an ordinary step
-                    rows = torch.cat((self.video_bos[None, None].expand(batch, 1, -1),
-                                      self.image_embedding(ids[:, t - keep:-1]) + pos_table[:keep - 1]), dim=1)
-                    stepper.prefill(rows)
-                logits = stepper(row)
-            else:
-                logits = self._guided_last_logits(lookback_window(ids, tpf, max_frames), text_embeds, text_mask, cond_scale)
-            token = sample_top_fraction(logits, filter_thres, temperature)
-            ids = torch.cat((ids, token[:, None]), dim=1)
-            if cached:
-                row = self.image_embedding(token) + pos_table[slide_plan(t + 1, tpf, max_frames)[0] - 1]
+                    # rows 0 .. keep - 1 (<bos> + all but the newest token) refill the caches; row keep (made at the end of the step
+                    # before with its window index) is an ordinary step
+                    kept = (stepper.ids if on_device else ids)[:, t - keep:t - 1]
+                    stepper.prefill(torch.cat((self.video_bos[None, None].expand(batch, 1, -1),
+                                               self.image_embedding(kept) + pos_table[:keep - 1]), dim=1))
+                if on_device:
+                    stepper.advance(row if t == 0 else None)
+                else:
+                    token = sample_top_fraction(stepper(row), filter_thres, temperature)
+                    ids = torch.cat((ids, token[:, None]), dim=1)
+                    row = self.image_embedding(token) + pos_table[slide_plan(t + 1, tpf, max_frames)[0] - 1]
+            if on_device:
+                ids = stepper.ids
         self.last_generated_ids = ids                      # (b, frames * fmap^2) token ids behind the returned frames
         return self._ids_to_frames(ids, decode_max_batchsize)
 
@@ -1314,11 +1317,13 @@ class NUWASketch(nn.Module):
 
     generate_use_cache = True               # key/value-cached generate() (decode.py); False = the reference's recompute loop
     generate_use_graph = True               # replay each token's decoder work (rows >= 1) as one captured HIP graph
+    generate_slide_cache = False            # past max_video_frames the recompute loop: SparseCross2DNA rows have no cache prefill
     generate_device_sampler = True          # cached path: sample + id write + next input row on the device, as NUWA.generate_device_sampler
     embed_video = NUWA.embed_video          # <bos> + positional + token embedding, one libamdnuwa node
     _final = NUWA._final                    # final StableLayerNorm + logits (+ cross entropy), fused
     _guided_last_logits = NUWA._guided_last_logits
     _ids_to_frames = NUWA._ids_to_frames
+    _sample_video = NUWA._sample_video      # the token loop of generate(): cached rows (device sampler / torch tail) or recompute
 
     def decode_hidden(self, frame_embeddings, sketch_embeds, context_mask):
         return self.video_transformer.forward_layers(frame_embeddings, context=sketch_embeds, context_mask=context_mask)
@@ -1347,39 +1352,9 @@ class NUWASketch(nn.Module):
         sequence fits the video shape and every block has a single-row path; otherwise the recompute algorithm runs on the same kernels."""
         if sketch.ndim == 4:
             sketch = sketch[:, None]
-        batch, device = sketch.shape[0], sketch.device
         sketch_embeds, context_mask = self.embed_sketch(sketch, mask=sketch_mask)
-        tpf = self.video_fmap_size ** 2
-        total = tpf * default(num_frames, self.max_video_frames)
-        ids = torch.empty((batch, 0), device=device, dtype=torch.long)
-        cached = self.generate_use_cache and sketch.is_cuda and total <= tpf * self.max_video_frames
-        if cached:
-            from .decode import GuidedStepper
-            sampler = dict(total=total, tokens_per_frame=tpf, max_frames=self.max_video_frames, filter_thres=filter_thres,
-                           temperature=temperature) if self.generate_device_sampler else None
-            try:
-                stepper = GuidedStepper(self, sketch_embeds, context_mask, total, cond_scale, graph=self.generate_use_graph, sampler=sampler)
-            except NotImplementedError:
-                cached = False
-        if cached:
-            pos_table = self.video_pos_emb()
-            row = self.video_bos[None].expand(batch, -1)
-        if cached and stepper.device_sampler:            # the whole token on the device (the <bos> row: an eager first call, as below)
-            for t in range(total):
-                stepper.advance(row if t == 0 else None)
-            self.last_generated_ids = ids = stepper.ids
-            return self._ids_to_frames(ids, decode_max_batchsize)
-        for t in range(total):
-            if cached:
-                logits = stepper(row)
-            else:
-                logits = self._guided_last_logits(lookback_window(ids, tpf, self.max_video_frames), sketch_embeds, context_mask, cond_scale)
-            token = sample_top_fraction(logits, filter_thres, temperature)
-            ids = torch.cat((ids, token[:, None]), dim=1)
-            if cached:
-                row = self.image_embedding(token) + pos_table[t]
-        self.last_generated_ids = ids
-        return self._ids_to_frames(ids, decode_max_batchsize)
+        total = self.video_fmap_size ** 2 * default(num_frames, self.max_video_frames)
+        return self._sample_video(sketch_embeds, context_mask, total, filter_thres, temperature, cond_scale, decode_max_batchsize)
 
     def forward(self, *, sketch, sketch_mask=None, video=None, return_loss=False, cond_dropout_prob=0.2):
         if sketch.ndim == 4:                              # one sketch frame

@@ -109,3 +109,85 @@ def test_prefill_refuses_blocks_without_a_full_sequence_form():
             d.prefill(torch.zeros(2, 3, 32))
     with pytest.raises(ValueError):
         d.prefill(torch.zeros(2, 9, 32))                      # more rows than the caches hold
+
+
+class _StubStepper:
+    """what the token loop drives of decode.GuidedStepper, recording every call into model.log; `t` = steps taken so far"""
+
+    def __init__(self, model, context, context_mask, max_rows, cond_scale, graph=True, sampler=None):
+        self.log, self.t = model.log, 0
+        self.log['built'].append(max_rows)
+        self.device_sampler = sampler is not None
+        self.batch = context.shape[0]
+        if sampler is not None:
+            self.ids = torch.zeros((self.batch, sampler['total']), dtype=torch.long)
+
+    def prefill(self, rows):
+        self.log['prefill'].append((self.t, rows.clone()))
+
+    def __call__(self, row):
+        self.log['rows'].append(row.clone())
+        self.t += 1
+        return torch.zeros(self.batch, 8)
+
+    def advance(self, x_row=None):
+        assert (x_row is not None) == (self.t == 0)               # the <bos> row once; afterwards the step leaves the next row in place
+        self.t += 1
+
+
+def _loop_model(fmap, max_frames, slide_cache, device_sampler):
+    """the attributes NUWA._sample_video reads, on a stand-in: <bos> = -1, token embedding 0, position row i = i + 1 in every channel"""
+    import types
+    m = types.SimpleNamespace(video_fmap_size=fmap, max_video_frames=max_frames, generate_use_cache=True, generate_use_graph=True,
+                              generate_slide_cache=slide_cache, generate_device_sampler=device_sampler,
+                              log=dict(built=[], prefill=[], rows=[], recompute=[]))
+    window = fmap * fmap * max_frames
+    m.video_bos = torch.full((4,), -1.)
+    m.image_embedding = lambda ids: torch.zeros(*ids.shape, 4)
+    m.video_pos_emb = lambda: (torch.arange(window, dtype=torch.float32) + 1)[:, None].expand(window, 4)
+    m._ids_to_frames = lambda ids, chunks: ids
+
+    def recompute(ids, context, context_mask, cond_scale):
+        m.log['recompute'].append(ids.shape[1])
+        return torch.zeros(ids.shape[0], 8)
+    m._guided_last_logits = recompute
+    return m
+
+
+@pytest.mark.parametrize('fmap', [1, 2])
+@pytest.mark.parametrize('max_frames', [1, 2, 3])
+def test_token_loop_prefills_at_slides_and_follows_the_position_schedule(monkeypatch, fmap, max_frames):
+    """NUWA._sample_video (the loop NUWA.generate and NUWASketch.generate share) on a stub stepper, total = 1 .. three frames past the
+    window, both cached tails: prefill exactly at the steps slide_plan marks, with `keep` rows (<bos>, then the window's position rows from 0);
+    the torch tail feeds step t + 1 the position row position_schedule(...)[t]; the caches hold total or window + 1 rows; with the slide
+    switch off (NUWASketch's setting) a call past the window never builds a stepper and recomputes the look-back window at every step"""
+    import types
+    from nuwa_pytorch_amd import decode
+    from nuwa_pytorch_amd.nuwa_pytorch import NUWA, slide_plan
+    monkeypatch.setattr(decode, 'GuidedStepper', _StubStepper)
+    tpf = fmap * fmap
+    window = tpf * max_frames
+    ctx = types.SimpleNamespace(shape=(2, 3, 4), is_cuda=True, device='cpu')
+    for total in range(1, window + 3 * tpf + 1):
+        slides = [t for t in range(total) if slide_plan(t, tpf, max_frames)[1]]
+        schedule = decode.position_schedule(tpf, max_frames, total)
+        for device_sampler in (False, True):
+            m = _loop_model(fmap, max_frames, True, device_sampler)
+            ids = NUWA._sample_video(m, ctx, None, total, 0.9, 1., 2., 10)
+            assert ids is m.last_generated_ids and tuple(ids.shape) == (2, total)
+            assert m.log['built'] == [total if total <= window else window + 1] and not m.log['recompute']
+            assert [t for t, _ in m.log['prefill']] == slides, (total, device_sampler)
+            for t, rows in m.log['prefill']:
+                keep = slide_plan(t, tpf, max_frames)[0]
+                assert tuple(rows.shape) == (2, keep, 4)
+                assert torch.equal(rows[0, :, 0], torch.cat((torch.tensor([-1.]), torch.arange(keep - 1) + 1.)))
+            if not device_sampler:
+                fed = torch.stack(m.log['rows'])[:, 0, 0]
+                assert fed[0] == -1 and torch.equal(fed[1:], schedule[:total - 1] + 1.)
+        m = _loop_model(fmap, max_frames, False, True)
+        NUWA._sample_video(m, ctx, None, total, 0.9, 1., 2., 10)
+        assert tuple(m.last_generated_ids.shape) == (2, total)
+        if total > window:
+            assert not m.log['built'] and m.log['recompute'] == [slide_plan(t, tpf, max_frames)[0] for t in range(total)]
+        else:
+            assert m.log['built'] == [total] and not m.log['recompute']
