@@ -223,16 +223,14 @@ class SandwichNorm(nn.Module):
             meta['handoff_in'] = hin
             if nxt is not None and not (nxt_fmap is not None and D % 32):
                 nxt_fn = nxt.fn.fn if isinstance(nxt.fn, (ShiftVideoTokens,)) else nxt.fn
-                nxt_kind = None                  # what the next block's first GEMM is (it may want an fp16 copy of its input: ops.SandwichBlockFn)
-                if isinstance(nxt_fn, FeedForward):
-                    nxt_kind = ('ff', nxt_fn.net[3].weight.shape[1], (nxt_fn.net[0].weight, nxt_fn.net[3].weight), nxt_fn._dropout_active())
-                elif isinstance(nxt_fn, Sparse3DNA) and nxt_fn.causal:
-                    nxt_kind = ('s3', nxt_fn.to_q.weight.shape[0], nxt_fn._meta(B, n, x.device)['geom'], (nxt_fn.to_q.weight, nxt_fn.to_kv.weight),
-                                nxt_fn.to_out.weight, nxt_fn.rel_pos_bias is not None)
-                elif isinstance(nxt_fn, Attention) and nxt_ctx is not None and nxt_fn._hip_ok(nxt_ctx.shape[1]):
-                    nxt_kind = ('x', nxt_fn.to_q.weight.shape[0], K.x_geom(B, n, nxt_ctx.shape[1], nxt_fn.heads, nxt_fn.dim_head), {},
-                                (nxt_fn.to_q.weight, nxt_fn.to_out.weight))
-                meta['next_pre'] = (nxt.prenorm.weight, nxt.prenorm.bias, (n, nxt_fmap) if nxt_fmap is not None else None, nxt_kind)
+                # the next block as ops.block_plan takes it: its plan says which form of its LayerNorm output this block's post-norm kernel writes.
+                # (its meta without the key mask: no plan reads one.)  The chain plans for the decoder's three blocks; any other gets bf16 hi[/lo]
+                nxt_block = None
+                if isinstance(nxt_fn, FeedForward) or (isinstance(nxt_fn, Sparse3DNA) and nxt_fn.causal) or \
+                        (isinstance(nxt_fn, Attention) and nxt_ctx is not None and nxt_fn._hip_ok(nxt_ctx.shape[1])):
+                    nxt_meta = nxt_fn._meta(B, n, x.device, context=nxt_ctx)
+                    nxt_block = (nxt_meta['kind'], nxt_fn._plan_params(), nxt_meta, False)
+                meta['next_pre'] = (nxt.prenorm.weight, nxt.prenorm.bias, (n, nxt_fmap) if nxt_fmap is not None else None, nxt_block)
                 meta['handoff_out'] = hout
         return ops.SandwichBlockFn.apply(x, resid, context if isinstance(inner, (Attention, SparseCross2DNA)) else None, meta,
                                          self.prenorm.weight, self.prenorm.bias, self.postnorm.weight,
@@ -337,6 +335,8 @@ class FeedForward(nn.Module):
     def _params(self):
         return (self.net[0].weight, self.net[3].weight)
 
+    _plan_params = _params
+
     def _dropout_active(self):
         return self.training and self.net[2].p > 0
 
@@ -387,6 +387,8 @@ class Attention(nn.Module):
 
     def _params(self):
         return (self.null_k, self.null_v, self.talking_heads.weight, self.to_q.weight, self.to_kv.weight, self.to_out.weight)
+
+    _plan_params = _params
 
     def _hip_ok(self, n_keys):
         """geometry the cross-attention kernels cover (they also serve non-causal SELF-attention: keys / values = the query rows)"""
@@ -523,8 +525,13 @@ class Sparse3DNA(nn.Module):
             self.register_buffer('_nbr', nbr, persistent=False)
         self._cache = ops.WeightCache()
 
-    def _params(self):
+    def _plan_params(self):
+        """what ops.block_plan reads of _params(): the weights, and THAT there is a relative-position bias -- nothing computed, nothing launched"""
         p = (self.to_q.weight, self.to_kv.weight, self.talking_heads.weight, self.to_out.weight, self.to_out.bias)
+        return p + (None,) if self.rel_pos_bias is not None else p
+
+    def _params(self):
+        p = self._plan_params()[:5]
         if self.rel_pos_bias is not None:
             taps = self.rel_pos_bias().reshape(self.kernel_numel, self.heads)             # [taps, heads], raster (a, b, c) order
             p = p + (torch.cat((taps.new_zeros(1, self.heads), taps), 0).float(),)       # key slot 0 = <bos>: no bias
@@ -745,16 +752,9 @@ class Transformer(nn.Module):
             calls.append((ff, {}, {}, ff._inner() if cuda else None))
         if cuda and K.mixed():
             # fp16 range verdicts of every weight the 'bf16x3-fwd' forward may run in fp16, in ONE device -> host transfer per step
-            ws = []
-            for _, _, _, inner in calls:
-                fn = inner[0] if inner is not None else None
-                if isinstance(fn, FeedForward):
-                    ws += [fn.net[0].weight, fn.net[3].weight]
-                elif isinstance(fn, Sparse3DNA):
-                    ws += [fn.to_q.weight, fn.to_kv.weight, fn.to_out.weight]
-                elif isinstance(fn, Attention):
-                    ws += [fn.to_q.weight, fn.to_out.weight]
-            ops.f16_ranges_prefetch(ws)
+            kinds = ((FeedForward, ops.FFInner), (Sparse3DNA, ops.S3Inner), (Attention, ops.XInner))
+            ops.f16_ranges_prefetch([w for _, _, _, inner in calls if inner is not None for cls, stage in kinds if isinstance(inner[0], cls)
+                                     for w in stage.guarded(inner[0]._plan_params())])
         handoff = None
         for i, (block, fused_kw, plain_kw, inner) in enumerate(calls):
             if inner is None:

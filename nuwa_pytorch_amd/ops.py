@@ -12,6 +12,7 @@ are fp32; GEMM / attention operands are bf16 (plus a bf16 residual in 'bf16x3' p
 The same inner stages also back the standalone modules (Sparse3DNA, Attention, FeedForward,
 LayerNorm wrappers) through `InnerFn`, so `Sparse3DNA(...)(x)` alone works as in the reference.
 """
+from collections import namedtuple
 import functools
 import os
 import warnings
@@ -143,6 +144,32 @@ def _f16_to_pair(h):
 # inner stages.  fwd(h: BF [R, D], ...) -> (y fp32 [R, D], saved) ; bwd(saved, dy: BF) -> (dh fp32, grads)
 # =================================================================================================
 
+# What a block runs is decided ONCE per forward call, by the plan() of its kind (block_plan below), from the precision mode, the A/B switches,
+# the kernels' support queries and the fp16 range verdicts of its weights -- and never cached: modes and switches may change between calls.
+# SandwichBlockFn / InnerFn put the record into meta['plan']; the kind's fwd dispatches on it and its bwd on the copy saved with the node.
+#   h16      form of the LayerNorm output the block reads: False = bf16 hi[/lo], True = bf16 + fp16 copy pair, 'only' = the fp16 copy alone
+#   bwd16    the backward runs on fp16 gradients (kernels.G16) against the single fp16 copies the forward leaves
+#   guarded  the weights the fp16 range guard judges (Inner.guarded: Transformer.forward_layers prefetches their verdicts)
+#   a16      the first product runs fp16 operands: the 3DNA q / k / v projection, both FeedForward products, the two-MFMA ('f16x2') cross-
+#            attention q product (False: gemm_nt on bf16 hi[/lo])
+#   core16   q / k / v leave their projection with an fp16 copy and the attention core runs fp16 MFMAs
+#   o16      the core's output is a bf16 + fp16 copy pair for the two-MFMA to_out ('only': the fp16 copy alone)
+#   core, pack, lean, bwd   cross attention: the forward core (X_CORES), the images packed ('x6b16' / 'x6b': the xattn6 backward's own, from the
+#            fp16 / bf16 copy of k / v; 'x1': xattn_pack with lean=), the backward (X_BWDS)
+_PLAN = dict(h16=False, bwd16=False, guarded=(), a16=False, core16=False, o16=False, core=None, pack=None, lean=False, bwd=None)
+Plan = namedtuple('Plan', list(_PLAN), defaults=list(_PLAN.values()))
+X_CORES = ('x6_f16_only', 'x6_f16', 'x6_bf16', 'x2_f16', 'x2_bf16', 'x1_stats', 'x1_p')      # kernel generation _ operand form / what it keeps
+X_BWDS = ('x6_16', 'x6', 'x2', 'x2_rc', 'x1')               # xattn6 on fp16 gradients, xattn6, xattn2, xattn2 recomputing the key side, xattn1
+
+
+def block_plan(kind, R, D, p, meta, has_resid=False, ln=True):
+    """the Plan of one block of R rows x D columns.  has_resid: a block of a reversible stack (separate residual input) keeps the bf16 backward
+    -- not chained, every one of them would take its own gradient scale: one amax pass per block, -2.7 % on cfg 4.  ln=False: no LayerNorm in
+    front (InnerFn: the standalone modules), the input is a plain bf16 hi[/lo] cast.  Kinds without a plan() have no choice to make."""
+    plan = getattr(INNERS[kind], 'plan', None)
+    return plan(R, D, p, meta, has_resid, ln) if plan is not None else Plan()
+
+
 class S3Inner:
     """to_q/to_kv -> Sparse3DNA core -> to_out (np.py:481-613).  params: to_q.w, to_kv.w, talking_heads.w,
     to_out.w, to_out.b"""
@@ -172,20 +199,24 @@ class S3Inner:
         return cache.get('s3', (wq, wkv, wo), build)
 
     @staticmethod
-    def bwd16_ok(R, D, inner, g, ws=None, wo=None, rel=False):
-        """the fp16-gradient backward applies (class 's'): the fp16 projection + core + two-MFMA to_out of the forward apply, the band kernels take
-        the geometry without a relative-position bias, and the five backward products fit their fp16 kernels"""
-        return K.bwd_f16('s') and not rel and S3Inner.f16_proj_ok(R, D, inner, g, ws) and K.proj_f16x2('o') and \
-            K.gemm_nt_f16x2_ok(R, D, inner, out_bf16=False) and (wo is None or f16_weights_ok(wo)) and K.s3_bwd16_supported(g) and \
-            K.gemm_nt_f16ops_ok(R, 3 * inner, D, out_bf16=False, out_f16=True) and K.gemm_nt_f16ops_ok(R, inner, D, out_bf16=False, out_f16=True) and \
-            K.gemm_nt_f16ops_ok(R, D, 3 * inner, out_bf16=False, out_f16=True) and K.gemm_tn16_ok(R, D, inner) and K.gemm_tn16_ok(R, 3 * inner, D)
+    def guarded(p):
+        return (p[0], p[1], p[3])
 
     @staticmethod
-    def f16_proj_ok(R, D, inner, g, ws=None):
-        """'bf16x3-fwd': q / k / v projection on single fp16 MFMAs (bf16 + fp16 copies out) feeding the fp16 core; ws = (to_q.weight,
-        to_kv.weight) adds the fp16 range guard of the weights"""
-        return K.qkv_f16() and K.s3_f16_supported(g) and K.gemm_nt_f16ops_ok(R, 3 * inner, D, out_bf16=True) and \
-            (ws is None or f16_weights_ok(*ws))
+    def plan(R, D, p, meta, has_resid=False, ln=True):
+        """a16: 'bf16x3-fwd' runs the q / k / v projection on single fp16 MFMAs (bf16 + fp16 copies out) feeding the fp16 core.  bwd16 (class
+        's'): that, the two-MFMA to_out, no relative-position bias, and the band kernels and the five backward products take the shapes"""
+        wq, wkv, wo = S3Inner.guarded(p)
+        g, inner = meta['geom'], wq.shape[0]
+        a16 = bool(meta.get('shift') is None and K.qkv_f16() and K.s3_f16_supported(g) and K.gemm_nt_f16ops_ok(R, 3 * inner, D, out_bf16=True) and
+                   f16_weights_ok(wq, wkv))
+        core16 = a16 or bool(K.cores_f16() and K.want_lo() and K.s3_f16_supported(g))
+        o16 = bool(core16 and K.proj_f16x2('o') and K.gemm_nt_f16x2_ok(R, wo.shape[0], inner, out_bf16=False) and f16_weights_ok(wo))
+        b16 = bool(ln and a16 and o16 and not has_resid and K.bwd_f16('s') and len(p) == 5 and
+                   K.s3_bwd16_supported(g) and K.gemm_nt_f16ops_ok(R, 3 * inner, D, out_bf16=False, out_f16=True) and
+                   K.gemm_nt_f16ops_ok(R, inner, D, out_bf16=False, out_f16=True) and K.gemm_nt_f16ops_ok(R, D, 3 * inner, out_bf16=False, out_f16=True) and
+                   K.gemm_tn16_ok(R, D, inner) and K.gemm_tn16_ok(R, 3 * inner, D))
+        return Plan('only' if b16 else ln and a16, b16, (wq, wkv, wo), a16, core16, 'only' if b16 else o16)
 
     @staticmethod
     def fwd(h, p, meta):
@@ -193,26 +224,23 @@ class S3Inner:
         wth, bo = p[2], p[4]
         g = meta['geom']
         rel = p[5].detach().contiguous() if len(p) > 5 else None          # [J, heads] relative-position bias (optional)
-        # 'bf16x3-fwd': q / k / v leave the 3-MFMA projection as a bf16 copy (backward) + an fp16 copy, and the core runs single fp16 MFMAs
-        R, D, _ = K.bf_rows_cols(h)
-        if meta.get('bwd16') and 'qkvT_16' in W and rel is None:
+        pl = meta['plan']
+        if pl.bwd16:
             # fp16-gradient backward: ONE (fp16) copy of h, of q / k / v and of the core's output
             qkv = K.BF(None, None, K.gemm_nt_f16ops(h.f16, W['qkv_16'], out_f16=True))
             o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), o_f16='only')
             y = K.gemm_nt_f16x2(o.f16, W['out_16'], bias=bo.detach())
             return y, (K.BF(None, None, h.f16), qkv, o)
         assert h.hi is not None, 'a bf16 backward needs the bf16 copy of the LayerNorm output'
-        if meta.get('shift') is None and 'qkv_16' in W and S3Inner.f16_proj_ok(R, D, g.heads * g.dim_head, g):
+        if pl.a16:
             h16 = h.f16 if h.f16 is not None else K.hilo_to_f16(h)
             qkv = K.gemm_nt_f16ops(h16, W['qkv_16'], out_bf16=True, copy_f16=True)
-        else:
+        else:       # core16: q / k / v leave the 3-MFMA projection as a bf16 copy (backward) + an fp16 copy, and the core runs single fp16 MFMAs
             h = _f16_to_pair(h)
-            f16 = K.cores_f16() and h.lo is not None and K.s3_f16_supported(g)
-            qkv = K.gemm_nt(h, W['qkv'], out_bf16=True, shift=meta.get('shift'), out_f16=f16)
-        # two-MFMA to_out: the fp16 core hands its output over as a bf16 copy (backward) + an fp16 copy (this product's A operand)
-        o16 = K.proj_f16x2('o') and qkv.f16 is not None and 'out_16' in W and K.gemm_nt_f16x2_ok(R, p[3].shape[0], p[3].shape[1], out_bf16=False)
-        o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel, o_f16=o16)
-        y = K.gemm_nt_f16x2(o.f16, W['out_16'], bias=bo.detach()) if o16 else K.gemm_nt(o, W['out'], bias=bo.detach(), out_bf16=_fast())
+            qkv = K.gemm_nt(h, W['qkv'], out_bf16=True, shift=meta.get('shift'), out_f16=pl.core16)
+        # two-MFMA to_out (o16): the fp16 core hands its output over as a bf16 copy (backward) + an fp16 copy (this product's A operand)
+        o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel, o_f16=pl.o16)
+        y = K.gemm_nt_f16x2(o.f16, W['out_16'], bias=bo.detach()) if pl.o16 else K.gemm_nt(o, W['out'], bias=bo.detach(), out_bf16=_fast())
         return y, _sv(h, qkv, o)
 
     @staticmethod
@@ -223,7 +251,7 @@ class S3Inner:
         rel = p[5].detach().contiguous() if len(p) > 5 else None
         g = meta['geom']
         inner = g.heads * g.dim_head
-        if isinstance(dy, K.G16):
+        if meta['plan'].bwd16:
             # fp16-gradient backward: dy = fp16(S dy); every product on the fp16 MFMA against the fp16 copies the forward left
             s2 = dy.s2
             d_o = K.gemm_nt_f16ops(dy.t, W['outT_16'], out_f16=True)
@@ -286,89 +314,82 @@ class XInner:
         return cache.get('x', (wq, wkv, wo), build)
 
     @staticmethod
-    def bwd16_ok(R, D, inner, g, meta, ws=None):
-        """the fp16-gradient backward applies (class 'x'): the two-MFMA q projection, the fp16 xattn6 cores and the two-MFMA to_out of the forward
-        apply, and the backward products fit their fp16 kernels (ws = to_q.weight, to_out.weight)"""
-        return K.bwd_f16('x') and XInner.f16x2_ok(R, D, inner, g, meta, ws) and K.proj_f16x2('o') and K.xattn6_on() and K.xattn6_supported(g) and \
-            K.gemm_nt_f16x2_ok(R, D, inner, out_bf16=False) and K.xattn_bwd16_ok(g) and not K.xattn2_bwd_rc_ok(g) and \
-            K.gemm_nt_f16ops_ok(R, inner, D, out_bf16=False, out_f16=True) and K.gemm_nt_f16ops_ok(R, D, inner, out_bf16=False, out_f16=True) and \
-            K.gemm_tn16_ok(R, D, inner) and K.gemm_tn16_ok(R, inner, D)
+    def guarded(p):
+        return (p[3], p[5])
 
     @staticmethod
-    def f16x2_ok(R, D, inner, g, meta, ws=None):
-        """'bf16x3-fwd' with the two-MFMA switch on: the q projection takes the LayerNorm output as ONE fp16 value (so the LayerNorm store
-        should write a bf16 + fp16 copy pair) -- when the fp16 core follows, the product fits the ring and (ws = to_q.weight, to_out.weight)
-        the weights sit inside the fp16 range"""
-        return K.proj_f16x2('q') and K.cores_f16() and not meta.get('self_kv') and meta.get('rotary') is None and K.xattn2_supported(g) and \
-            K.gemm_nt_f16x2_ok(R, inner, D, out_bf16=True) and (ws is None or f16_weights_ok(*ws))
+    def plan(R, D, p, meta, has_resid=False, ln=True):
+        """a16: 'bf16x3-fwd' with the two-MFMA switch on -- the q projection takes the LayerNorm output as ONE fp16 value when the fp16 core
+        follows, the product fits the ring and the weights sit inside the fp16 range.  The core: the third design (xattn6: images in LDS order,
+        null key as a rank-one term) wherever the second ran, on fp16 operands (core16) in 'bf16x3-fwd' or bf16 ones in 'bf16'; the first
+        design for the other geometries and for hi + lo operands.  bwd16 (class 'x'): the two-MFMA q and to_out products around the fp16 xattn6
+        core, fp32 null key / value, and the fp16 backward kernels take the shapes"""
+        nk, (wq, wo) = p[0], XInner.guarded(p)
+        g, inner, lo, rot = meta['xgeom'], wq.shape[0], K.want_lo(), meta.get('rotary')          # (lo: h, q and the context carry lo parts)
+        x2s, rc = K.xattn2_supported(g), K.xattn2_bwd_rc_ok(g)
+        core16 = bool(K.cores_f16() and lo and rot is None and x2s)
+        a16 = bool(core16 and K.proj_f16x2('q') and not meta.get('self_kv') and K.gemm_nt_f16x2_ok(R, inner, D, out_bf16=True) and f16_weights_ok(wq, wo))
+        o16 = bool(core16 and K.proj_f16x2('o') and K.gemm_nt_f16x2_ok(R, wo.shape[0], inner, out_bf16=False) and f16_weights_ok(wq, wo))
+        x6 = bool(K.xattn6_on() and K.xattn6_supported(g) and (core16 or (x2s and not lo)) and nk.dtype == torch.float32)
+        if ln and a16 and o16 and x6 and not has_resid and K.bwd_f16('x') and K.xattn_bwd16_ok(g) and not rc and \
+                K.gemm_nt_f16ops_ok(R, inner, D, out_bf16=False, out_f16=True) and K.gemm_nt_f16ops_ok(R, D, inner, out_bf16=False, out_f16=True) and \
+                K.gemm_tn16_ok(R, D, inner) and K.gemm_tn16_ok(R, inner, D):
+            return Plan('only', True, (wq, wo), True, True, 'only', 'x6_f16_only', 'x6b16', False, 'x6_16')
+        if core16:
+            core = 'x6_f16' if x6 else 'x2_f16'
+        elif x2s and not lo:                  # fast mode: statistics only, the backward recomputes the probabilities
+            core = 'x6_bf16' if x6 else 'x2_bf16'
+        else:                                 # 3-MFMA forward: 'bf16x3-fwd' keeps the statistics for xattn2_bwd on the hi parts, else P / P' for xattn_bwd
+            core = 'x1_stats' if K.mixed() and x2s else 'x1_p'
+        x6b = bool(x6 and K.xattn6_bwd_ok(g) and not rc)        # the bf16 backward on its own images (bf16 [key][d] tiles in LDS order)
+        lean = False if x6b else 'bwd' if x6 and not rc else core16 and not rc
+        bwd = 'x1' if core == 'x1_p' else 'x2_rc' if rc else 'x6' if x6b else 'x2'
+        return Plan(ln and a16, False, (wq, wo), a16, core16, o16, core, 'x6b' if x6b else 'x1', lean, bwd)
 
     @staticmethod
     def fwd(h, p, meta):
         W = XInner.weights(meta['cache'], p)
         nk, nv, wth = p[0], p[1], p[2]
-        g = meta['xgeom']
+        g, pl = meta['xgeom'], meta['plan']
         ctx = h if meta.get('self_kv') else meta['ctx_bf']          # self-attention (text encoder): keys / values from the same rows
-        rot = meta.get('rotary')
-        R, D, _ = K.bf_rows_cols(h)
-        inner = g.heads * g.dim_head
-        if meta.get('bwd16'):
+        rot, m8 = meta.get('rotary'), meta['mask_u8']
+        nk2, nv2 = nk.detach().reshape(g.heads, g.dim_head).contiguous(), nv.detach().reshape(g.heads, g.dim_head).contiguous()
+        wth2 = wth.detach().reshape(g.heads, g.heads).contiguous()
+        if pl.bwd16:
             # fp16-gradient backward: ONE (fp16) copy of h, of q and of the core's output; the backward's images come from the fp16 copy of k / v
-            # (_block_bwd16 decided it: the context's hi + lo copy, fp32 null key / value, the fp16 weight copies of this mode)
-            assert 'qT_16' in W and ctx.lo is not None and nk.dtype == torch.float32
             q16 = K.gemm_nt_f16x2(h.f16, W['q_16'], out_f16=True)
             kv = K.gemm_nt(ctx, W['kv'], out_bf16=True, out_f16=True)
-            nk2, nv2 = nk.detach().reshape(g.heads, g.dim_head).contiguous(), nv.detach().reshape(g.heads, g.dim_head).contiguous()
-            wth2 = wth.detach().reshape(g.heads, g.heads).contiguous()
-            pk = K.xattn6_pack_bwd(g, kv.f16, nk2, nv2, meta['mask_u8'])
-            o, stats = K.xattn6_fwd(g, q16, K.xattn6_pack(g, kv.f16, meta['mask_u8']), nk2, nv2, wth2, o_f16='only')
+            pk = K.xattn6_pack_bwd(g, kv.f16, nk2, nv2, m8)
+            o, stats = K.xattn6_fwd(g, q16, K.xattn6_pack(g, kv.f16, m8), nk2, nv2, wth2, o_f16='only')
             y = K.gemm_nt_f16x2(o.f16, W['out_16'])
             return y, (K.BF(None, None, h.f16), K.hi_only(ctx), K.BF(None, None, q16), pk, stats, None, o)
         assert h.hi is not None, 'a bf16 backward needs the bf16 copy of the LayerNorm output'
-        x2 = 'q_16' in W and ctx.lo is not None and XInner.f16x2_ok(R, D, inner, g, meta)
-        if not x2:
-            h = _f16_to_pair(h)
-        f16 = K.cores_f16() and (x2 or h.lo is not None) and ctx.lo is not None and rot is None and K.xattn2_supported(g)
-        if x2:      # two MFMAs: fp16 LayerNorm output x the weight as an fp16 hi + lo pair; q leaves as a bf16 copy + an fp16 copy
+        if pl.a16:      # two MFMAs: fp16 LayerNorm output x the weight as an fp16 hi + lo pair; q leaves as a bf16 copy + an fp16 copy
             q = K.gemm_nt_f16x2(h.f16 if h.f16 is not None else K.hilo_to_f16(h), W['q_16'], out_bf16=True, copy_f16=True)
         else:
-            q = K.gemm_nt(h, W['q'], out_bf16=True, out_f16=f16)
-        kv = K.gemm_nt(ctx, W['kv'], out_bf16=True, out_f16=f16)          # (context rows: B * T of them, a 3-MFMA product either way)
+            h = _f16_to_pair(h)
+            q = K.gemm_nt(h, W['q'], out_bf16=True, out_f16=pl.core16)
+        kv = K.gemm_nt(ctx, W['kv'], out_bf16=True, out_f16=pl.core16)    # (context rows: B * T of them, a 3-MFMA product either way)
         if rot is not None:
             q = _rotary_bf(q, rot, g.B, g.n, g.heads)
             kv = _rotary_bf(kv, rot, g.B, g.T, 2 * g.heads)
-        nk2, nv2 = nk.detach().reshape(g.heads, g.dim_head).contiguous(), nv.detach().reshape(g.heads, g.dim_head).contiguous()
-        # third-design forward core (xattn6: images in LDS order, null key as a rank-one term) wherever the second design ran; the bf16
-        # recomputing backward keeps its two [key][d] images
-        x6 = K.xattn6_on() and K.xattn6_supported(g) and (f16 or K.xattn2_supported(g, q)) and nk2.dtype == torch.float32
-        x6b = x6 and K.xattn6_bwd_ok(g) and not K.xattn2_bwd_rc_ok(g)
-        if x6b:       # the backward's own images (bf16 [key][d] tiles in LDS order)
-            pk = K.xattn6_pack_bwd(g, kv.hi, nk2, nv2, meta['mask_u8'])
-        else:
-            pk = K.xattn_pack(g, kv, nk2, nv2, meta['mask_u8'], lean=('bwd' if x6 and not K.xattn2_bwd_rc_ok(g) else (f16 and not K.xattn2_bwd_rc_ok(g))))
-        wth2 = wth.detach().reshape(g.heads, g.heads).contiguous()
-        o16 = False
-        if f16:                               # 'bf16x3-fwd': the forward core on single fp16 MFMAs, hi + lo output, statistics for the bf16 backward
-            o16 = K.proj_f16x2('o') and 'out_16' in W and K.gemm_nt_f16x2_ok(R, p[5].shape[0], p[5].shape[1], out_bf16=False)
-            if x6:
-                o, stats = K.xattn6_fwd(g, q.f16, K.xattn6_pack(g, kv.f16, meta['mask_u8']), nk2, nv2, wth2, o_f16=o16)
-            else:
-                o, stats = K.xattn2_fwd_f16(g, q, pk, wth2, o_f16=o16)
-                pk.drop_lo()
-            P, Pm = stats, None
-        elif K.xattn2_supported(g, q):        # fast mode: statistics only, the backward recomputes the probabilities
-            if x6:
-                o, stats = K.xattn6_fwd(g, q.hi, K.xattn6_pack(g, kv.hi, meta['mask_u8']), nk2, nv2, wth2, lo=False)
-            else:
-                o, stats = K.xattn2_fwd(g, q, pk, wth2)
-            P, Pm = stats, None
-        elif K.mixed() and K.xattn2_supported(g):
-            # 3-MFMA forward that leaves only the softmax statistics; the bf16 backward (xattn2_bwd) recomputes from the hi parts
-            o, stats = K.xattn_fwd(g, q, pk, wth2, want_stats=True)
-            P, Pm = stats, None
-            pk.drop_lo()
+        pk = K.xattn6_pack_bwd(g, kv.hi, nk2, nv2, m8) if pl.pack == 'x6b' else K.xattn_pack(g, kv, nk2, nv2, m8, lean=pl.lean)
+        Pm = None
+        if pl.core == 'x6_f16':         # the forward core on single fp16 MFMAs, hi + lo (or o16) output, statistics for the bf16 backward
+            o, P = K.xattn6_fwd(g, q.f16, K.xattn6_pack(g, kv.f16, m8), nk2, nv2, wth2, o_f16=pl.o16)
+        elif pl.core == 'x2_f16':
+            o, P = K.xattn2_fwd_f16(g, q, pk, wth2, o_f16=pl.o16)
+        elif pl.core == 'x6_bf16':
+            o, P = K.xattn6_fwd(g, q.hi, K.xattn6_pack(g, kv.hi, m8), nk2, nv2, wth2, lo=False)
+        elif pl.core == 'x2_bf16':
+            o, P = K.xattn2_fwd(g, q, pk, wth2)
+        elif pl.core == 'x1_stats':
+            o, P = K.xattn_fwd(g, q, pk, wth2, want_stats=True)
         else:
             o, P, Pm = K.xattn_fwd(g, q, pk, wth2, save=meta.get('save', True))
-        y = K.gemm_nt_f16x2(o.f16, W['out_16']) if o16 else K.gemm_nt(o, W['out'], out_bf16=_fast())
+        if pl.core in ('x2_f16', 'x1_stats'):
+            pk.drop_lo()
+        y = K.gemm_nt_f16x2(o.f16, W['out_16']) if pl.o16 else K.gemm_nt(o, W['out'], out_bf16=_fast())
         return y, _sv(h, ctx, q, pk, P, Pm, o)
 
     @staticmethod
@@ -378,7 +399,8 @@ class XInner:
         nk, nv, wth, wq, wkv, wo = p
         g = meta['xgeom']
         wth2 = wth.detach().reshape(g.heads, g.heads).contiguous()
-        if isinstance(dy, K.G16):
+        bwd = meta['plan'].bwd                  # the route the forward chose (and packed the images for)
+        if bwd == 'x6_16':
             # fp16-gradient backward: dy = fp16(S dy); every large product on the fp16 MFMA against the fp16 copies the forward left
             s2 = dy.s2
             d_o = K.gemm_nt_f16ops(dy.t, W['outT_16'], out_f16=True)
@@ -396,20 +418,15 @@ class XInner:
         d_o = K.gemm_nt(dy, W['outT'], out_bf16=True)
         dwo = torch.empty_like(wo)
         K.gemm_tn(dy, o, dwo)
-        permuted = False
-        if Pm is None and K.xattn2_bwd_rc_ok(g):
+        if bwd == 'x2_rc':
             dq, dKp, dVp, dwth = K.xattn2_bwd_rc(g, q, d_o, pk, wth2, P)         # no dS / Pm arrays: the key side recomputes them
         else:
-            if Pm is None:
-                if isinstance(pk, K.PackedKV6B):
-                    dq, dS, Pm, dwth = K.xattn6_bwd(g, q, d_o, pk, wth2, P)
-                else:
-                    dq, dS, Pm, dwth = K.xattn2_bwd(g, q, d_o, pk, wth2, P)      # dS / Pm columns in the kernel's chunk-permuted key order
-                permuted = True
-            else:
+            if bwd == 'x1':
                 dq, dS, dwth = K.xattn_bwd(g, d_o, pk, wth2, P)
+            else:                               # dS / Pm columns in the kernel's chunk-permuted key order
+                dq, dS, Pm, dwth = (K.xattn6_bwd if bwd == 'x6' else K.xattn2_bwd)(g, q, d_o, pk, wth2, P)
             dKp, dVp = K.xattn_kv_grads(g, dS, Pm, q, d_o)
-        dkv, dnk, dnv = K.xattn_unpack(g, dKp, dVp, lo=dy.lo is not None, permuted=permuted, null_last=isinstance(pk, K.PackedKV6B))
+        dkv, dnk, dnv = K.xattn_unpack(g, dKp, dVp, lo=dy.lo is not None, permuted=bwd in ('x6', 'x2'), null_last=bwd == 'x6')
         rot = meta.get('rotary')
         if rot is not None:
             dq = _rotary_bf(dq, rot, g.B, g.n, g.heads, inverse=True)
@@ -546,30 +563,34 @@ class FFInner:
         return cache.get('ff', (w1, w2), build)
 
     @staticmethod
-    def f16_ok(R, D, FP, ws=None):
-        """the fp16-operand forward applies when 'bf16x3-fwd' wants it, both products run on the 256x256 ring and (ws = the two
-        weights) the weights sit inside the fp16 range"""
-        return K.ff_f16() and K.gemm_nt_f16ops_ok(R, 2 * FP, D, out_bf16=True, gate=True) and K.gemm_nt_f16ops_ok(R, D, FP, out_bf16=False) and \
-            (ws is None or f16_weights_ok(*ws))
+    def guarded(p):
+        return (p[0], p[1])
 
     @staticmethod
-    def bwd16_ok(R, D, FP, FFI, ws=None):
-        """the fp16-gradient backward applies: switched on, the fp16 forward applies, and the four backward products fit their fp16 kernels"""
-        return K.bwd_f16('f') and FFInner.f16_ok(R, D, FP, ws) and \
-            K.gemm_nt_f16ops_ok(R, FP, D, out_bf16=True, geglu_bwd=True) and K.gemm_nt_f16ops_ok(R, D, 2 * FP, out_bf16=False, out_f16=True) and \
-            K.gemm_tn16_ok(R, D, FFI, lda=D, ldb=FP) and K.gemm_tn16_ok(R, 2 * FP, D)
+    def plan(R, D, p, meta, has_resid=False, ln=True):
+        """a16: 'bf16x3-fwd' wants the fp16-operand forward, both products run on the 256x256 ring and the weights sit inside the fp16 range.
+        bwd16 (class 'f'): that, no live dropout (the fp16 GEGLU-backward epilogue has no mask input) and the four backward products fit"""
+        w1, w2 = p
+        FFI = w2.shape[1]
+        FP = _ru(FFI, 32)
+        a16 = bool(meta.get('shift') is None and K.ff_f16() and K.gemm_nt_f16ops_ok(R, 2 * FP, D, out_bf16=True, gate=True) and
+                   K.gemm_nt_f16ops_ok(R, D, FP, out_bf16=False) and f16_weights_ok(w1, w2))
+        b16 = bool(ln and a16 and not has_resid and not meta.get('drop_p') and K.bwd_f16('f') and
+                   K.gemm_nt_f16ops_ok(R, FP, D, out_bf16=True, geglu_bwd=True) and K.gemm_nt_f16ops_ok(R, D, 2 * FP, out_bf16=False, out_f16=True) and
+                   K.gemm_tn16_ok(R, D, FFI, lda=D, ldb=FP) and K.gemm_tn16_ok(R, 2 * FP, D))
+        return Plan('only' if b16 else ln and a16, b16, (w1, w2), a16)
 
     @staticmethod
     def fwd(h, p, meta):
         W = FFInner.weights(meta['cache'], p)
         R, D, _ = K.bf_rows_cols(h)
         drop_p = float(meta.get('drop_p') or 0.0)
-        assert not (drop_p and meta.get('bwd16')), 'FeedForward dropout runs on the bf16 backward (the fp16 GEGLU-backward epilogue has no mask input)'
-        if meta.get('shift') is None and 'w1_16' in W and FFInner.f16_ok(R, D, W['FP']):
+        pl = meta['plan']
+        if pl.a16:
             # 'bf16x3-fwd': both FeedForward products on single fp16 MFMAs (h arrives with an fp16 copy from the LayerNorm store);
             # u and the gate output also leave as bf16 copies for the bf16 backward
             h16 = h.f16 if h.f16 is not None else K.hilo_to_f16(h)
-            if meta.get('bwd16') and 'w1T_16' in W:
+            if pl.bwd16:
                 # fp16-gradient backward: ONE copy of h and of the gate output (fp16); u stays bf16 (read element-wise by the gate's backward)
                 u, gg16, _ = K.gemm_nt_f16ops(h16, W['w1_16'], out_bf16=True, gate=True, gate_bf16=False)
                 y = K.gemm_nt_f16ops(gg16, W['w2_16'])
@@ -611,7 +632,7 @@ class FFInner:
         W = FFInner.weights(meta['cache'], p)
         w1, w2 = p
         FP, FFI = W['FP'], W['FFI']
-        if isinstance(dy, K.G16):
+        if meta['plan'].bwd16:
             # fp16-gradient backward: dy = fp16(S dy); every product on the fp16 MFMA against the fp16 copies the forward left
             s2 = dy.s2
             du = K.gemm_nt_geglu_bwd16(dy.t, W['w2T_16'], u.hi, FP)
@@ -623,7 +644,6 @@ class FFInner:
             d = K.geglu_deinterleave(dw1p, FP, dim=0)
             return dh, None, [torch.cat((d[:FFI], d[FP:FP + FFI]), 0), dw2]
         if keep is not None:
-            assert not isinstance(dy, K.G16)
             dgg = K.gemm_nt(dy, W['w2T'], out_bf16=True)
             if K.ff_drop_torch():
                 dgd = K.empty_bf(tuple(dgg.hi.shape), dgg.hi.device)
@@ -817,22 +837,6 @@ def _grad_scale(g2):
     return torch.stack((S, 1.0 / S)).contiguous()
 
 
-def _block_bwd16(kind, R, D, p, meta):
-    """does this block run the fp16-gradient backward (and so keep only the fp16 copy of its LayerNorm input)?"""
-    if not K.bwd_f16() or meta.get('shift_unfused'):
-        return False
-    if kind == 'ff':
-        return not meta.get('drop_p') and FFInner.bwd16_ok(R, D, _ru(p[1].shape[1], 32), p[1].shape[1], (p[0], p[1]))
-    if kind == 's3':
-        return S3Inner.bwd16_ok(R, D, p[0].shape[0], meta['geom'], (p[0], p[1]), p[3], len(p) > 5)
-    if kind == 'xattn':
-        # (the fp16 branch of XInner.fwd projects the context's hi + lo copy and reads fp32 null key / value)
-        c = meta.get('ctx_bf')
-        return c is not None and c.lo is not None and p[0].dtype == torch.float32 and \
-            XInner.bwd16_ok(R, D, p[3].shape[0], meta['xgeom'], meta, (p[3], p[5]))
-    return False
-
-
 def _takes_ctx(meta):
     """does the inner stage project keys / values from a context tensor (and so want its BF copy in meta['ctx_bf'])?"""
     return (meta['kind'] in ('xattn', 'xc2') and not meta.get('self_kv')) or (meta['kind'] == 'cattn' and bool(meta.get('has_ctx')))
@@ -892,39 +896,28 @@ class SandwichBlockFn(Function):
             meta['ctx_bf'] = _ctx_to_bf(context)
         # the token shift is folded into the pre-LN's STORE: h = shift(LN(x)) is what the forward GEMM and the weight-gradient
         # GEMM consume (plain loaders); only the pre-LN backward still reads its incoming gradient through the inverse shift
-        sh = meta.get('shift')
+        ctx.shift = sh = meta.get('shift')
+        if sh is not None:
+            meta['shift'] = None
         # block chaining (Transformer.forward_layers): the previous block's post-norm kernel may already have produced this
         # block's h = shift(LN(x)) while the new stream row was in its registers, and this block does the same for the next
         hin, nxt, hout = meta.pop('handoff_in', None), meta.pop('next_pre', None), meta.pop('handoff_out', None)
         ctx.prev_ctx = None
-        # h as a bf16 + fp16 copy pair when this block's first GEMM runs fp16 operands ('bf16x3-fwd': FeedForward, the 3DNA projection)
-        want16 = (meta['kind'] == 'ff' and FFInner.f16_ok(B * n, D, _ru(p[1].shape[1], 32), (p[0], p[1]))) or \
-                 (meta['kind'] == 's3' and S3Inner.f16_proj_ok(B * n, D, p[0].shape[0], meta['geom'], (p[0], p[1]))) or \
-                 (meta['kind'] == 'xattn' and XInner.f16x2_ok(B * n, D, p[3].shape[0], meta['xgeom'], meta, (p[3], p[5])))
-        # (blocks of a reversible stack -- a separate residual input -- keep the bf16 backward: they are not chained, so every one of them would
-        #  take its own gradient scale: one amax pass per block, -2.7 % on cfg 4)
-        bw16 = bool(want16) and resid is None and _block_bwd16(meta['kind'], B * n, D, p, meta)
+        plan = block_plan(meta['kind'], B * n, D, p, meta, resid is not None)
         if hin is not None and hin.get('ptr') == x.data_ptr() and hin.get('ver') == x._version and hin.get('shift') == sh \
-                and resid is None and K.bf_rows_cols(hin['h'])[:2] == (B * n, D) and (hin['h'].hi is not None or bw16):
+                and resid is None and K.bf_rows_cols(hin['h'])[:2] == (B * n, D) and (hin['h'].hi is not None or plan.bwd16):
             h, m1, r1 = hin['h'], hin['m1'], hin['r1']
             ctx.prev_ctx = hin.get('ctx')          # the backward chains the two LayerNorm backwards of this boundary too
+            if plan.bwd16 and h.f16 is None:       # a hand-off without the fp16 copy (a predecessor that did not plan for this block): bf16 backward
+                plan = block_plan(meta['kind'], B * n, D, p, meta, True)           # (has_resid gates bwd16 and nothing else: every plan() keeps that)
         else:
-            h, m1, r1, _ = K.ln_fwd(x2, pre_w.detach(), pre_b.detach(), shift=sh, f16='only' if bw16 else want16)
-        ctx.shift = sh
-        if sh is not None:
-            meta['shift'] = None
-        meta['bwd16'] = ctx.bw16 = bw16 and h.f16 is not None
+            h, m1, r1, _ = K.ln_fwd(x2, pre_w.detach(), pre_b.detach(), shift=sh, f16=plan.h16)
+        meta['plan'], ctx.bw16 = plan, plan.bwd16
         y, saved = inner.fwd(h, p, meta)
         if nxt is not None and hout is not None:
-            # the next block's first GEMM runs fp16 operands: FeedForward (nxt[3] = ('ff', inner width)) or the 3DNA projection (('s3', inner, geom))
-            nk = nxt[3] if len(nxt) > 3 else None
-            nxt16 = nk is not None and ((nk[0] == 'ff' and FFInner.f16_ok(B * n, D, _ru(nk[1], 32), nk[2])) or
-                                        (nk[0] == 's3' and S3Inner.f16_proj_ok(B * n, D, nk[1], nk[2], nk[3])) or
-                                        (nk[0] == 'x' and XInner.f16x2_ok(B * n, D, nk[1], nk[2], nk[3], nk[4])))
-            if nxt16 and ((nk[0] == 'ff' and not (len(nk) > 3 and nk[3]) and FFInner.bwd16_ok(B * n, D, _ru(nk[1], 32), nk[1], nk[2])) or     # (nk[3]: live dropout -> bf16 backward)
-                          (nk[0] == 's3' and len(nk) > 5 and S3Inner.bwd16_ok(B * n, D, nk[1], nk[2], nk[3], nk[4], nk[5])) or
-                          (nk[0] == 'x' and XInner.bwd16_ok(B * n, D, nk[1], nk[2], nk[3], nk[4]))):
-                nxt16 = 'only'                    # the next block keeps ONE (fp16) copy of its LayerNorm input: fp16-gradient backward
+            # the form the next block reads its LayerNorm output in: ITS plan, from the (kind, params, meta, has_resid) fused_residual handed over
+            # (None: a block the chain does not plan for -- it gets the bf16 hi[/lo] form)
+            nxt16 = block_plan(nxt[3][0], B * n, D, *nxt[3][1:]).h16 if nxt[3] is not None else False
             xo, m2, r2, hn, mn, rn = K.ln_post_pre_fwd(y, r2_, post_w.detach(), post_b.detach(), nxt[0].detach(),
                                                        nxt[1].detach(), next_shift=nxt[2], next_f16=nxt16)
             hout.update(h=hn, m1=mn, r1=rn, ptr=xo.data_ptr(), ver=xo._version, shift=nxt[2], ctx=ctx if CHAIN_BWD else None)
@@ -954,7 +947,7 @@ class SandwichBlockFn(Function):
         s2 = ho.get('s2') if ho is not None else None          # the gradient scale of this backward pass (fp16-gradient blocks)
         # (only where this block or the one its chained LayerNorm backward feeds runs on fp16 gradients: a reversible stack -- no such block --
         #  paid one amax pass over the stream per block for a scale nobody read: cfg 4 -4 %)
-        if s2 is None and K.bwd_f16() and (bw16 or getattr(ctx.prev_ctx, 'bw16', False)):
+        if s2 is None and (bw16 or getattr(ctx.prev_ctx, 'bw16', False)):
             s2 = _grad_scale(g2)
         if ho is not None and ho['ptr'] == g2.data_ptr() and ho['ver'] == g2._version and isinstance(ho['dy'], K.G16) == bw16:   # the next block's backward already ran this post-norm backward
             dy, dpost_w, dpost_b, dsum = ho['dy'], ho['dw'], ho['db'], ho['dsum']
@@ -1008,6 +1001,7 @@ class InnerFn(Function):
             meta['ctx_bf'] = _ctx_to_bf(context)
         h = K.empty_bf((B * n, D), x.device)
         K.cast_pad(x2, h)
+        meta['plan'] = block_plan(meta['kind'], B * n, D, p, meta, ln=False)
         y, saved = inner.fwd(h, p, meta)
         ctx.meta, ctx.inner_saved, ctx.p = meta, saved, p
         ctx.has_ctx = context is not None
