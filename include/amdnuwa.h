@@ -40,7 +40,8 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 *     amdnuwa_attn_decode_rows and its _workspace_bytes were added at 21 as well: purely additive; so were amdnuwa_prefill_ln and
                                                 *     amdnuwa_prefill_kv, the cache prefill of a sliding generate() window, and amdnuwa_cross2dna_decode with its
                                                 *     _workspace_bytes, the single-query SparseCross2DNA over a window of any size, and amdnuwa_sample_next_row, the
-                                                *     sampling tail of a generate() token) */
+                                                *     sampling tail of a generate() token, and amdnuwa_vq_nearest_l2 with its _workspace_bytes, the Euclidean
+                                                *     code lookup of the tokenizer) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -691,6 +692,24 @@ int amdnuwa_vq_argmax(const float* x, const float* codebook, long long* indices,
 size_t amdnuwa_vq_argmax_workspace_bytes(long long R, int n_codes);
 int amdnuwa_vq_argmax_ws(const float* x, const float* codebook, long long* indices, float* best_sim, long long R, int n_codes,
                          int code_dim, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
+/* Euclidean code lookup (added at ABI 21, purely additive; vq_use_cosine_sim = False of vqgan_vae.py:368-378):
+ * indices[r] = argmin_c ||x[r] - codebook[c]||^2, lowest index on exact ties -- the pick of (-torch.cdist(x, codebook)).argmax(-1) in
+ * exact arithmetic.  x [R][code_dim], codebook [n_codes][code_dim] fp32; best_dist [R] optional (NULL: not written) = the SQUARED
+ * distance to the picked code.  Computed as the arg-max of the centred score
+ *     s(r, c) = (x[r] - mu) . (codebook[c] - mu) - 1/2 ||codebook[c] - mu||^2,   mu = column mean of the codebook,
+ * products on the exact-fp32 MFMA, best_dist = max(||x[r] - mu||^2 - 2 s, 0).  Why centred: distances do not change under a common
+ * shift, fp32 arithmetic does.  The usual expansion ||x||^2 - 2 x.c + ||c||^2 around the origin (torch.cdist's) carries 1/2 ||c||^2,
+ * and on a codebook that sits in a tight cloud away from the origin (codes 100 + 0.05 randn, 256 dims: 1/2 ||c||^2 = 1.3e6, ulp 0.125,
+ * distances apart by ~1) it mispicks 296 of 300 rows that float64 separates beyond doubt; around mu the same arithmetic picks all right.
+ * Deterministic: mu and the code norms come from fixed-order sums (no atomics), equal codes get bit-equal scores wherever they sit, two
+ * calls agree bit for bit.  Nothing outside [R] of the outputs is written.
+ * Envelope: code_dim even; 256 runs the register-resident-rows kernel over slices of the code axis, every other width a kernel with two
+ * 64-row tiles in LDS (code_dim <= 316, as amdnuwa_vq_argmax; more: AMDNUWA_ERR_UNSUPPORTED); tuning key 15 = 1 selects that kernel for 256 too.  Errors come
+ * before the device is touched: NULL x / codebook / indices, n_codes <= 0, code_dim <= 0 or odd -> AMDNUWA_ERR_ARG; R <= 0 -> OK, nothing
+ * done; workspace NULL or smaller than _workspace_bytes (0 for non-positive arguments) -> AMDNUWA_ERR_WORKSPACE. */
+size_t amdnuwa_vq_nearest_l2_workspace_bytes(long long R, int n_codes, int code_dim);
+int amdnuwa_vq_nearest_l2(const float* x, const float* codebook, long long* indices, float* best_dist, long long R, int n_codes,
+                          int code_dim, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
 
 /* VQGanAttention block of the encoder (vqgan_vae.py:244-286), exact fp32: in-place l2 normalisation of rows (q and k over the
  * spatial axis), the per-(image, head) attention core with the continuous-position bias [heads][P][P] precomputed from the

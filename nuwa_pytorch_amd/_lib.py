@@ -163,6 +163,8 @@ SIGNATURES = {
     'amdnuwa_vq_argmax': (I, [P, P, P, P, LL, I, I, P]),
     'amdnuwa_vq_argmax_workspace_bytes': (SZ, [LL, I]),
     'amdnuwa_vq_argmax_ws': (I, [P, P, P, P, LL, I, I, P, SZ, P]),
+    'amdnuwa_vq_nearest_l2_workspace_bytes': (SZ, [LL, I, I]),
+    'amdnuwa_vq_nearest_l2': (I, [P, P, P, P, LL, I, I, P, SZ, P]),
     'amdnuwa_glu_chan': (I, [P, P, I, I, I, P]),
     'amdnuwa_upsample_bilinear2x': (I, [P, P, I, I, I, I, P]),
     'amdnuwa_grad_norm': (I, [P, I, F, P, P, P]),

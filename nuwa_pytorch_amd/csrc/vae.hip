@@ -10,6 +10,7 @@
 //   groupnorm   : nn.GroupNorm(16, C) (+ LeakyReLU) of ResBlock (vq.py:233-237)
 //   vq_argmax   : idx = argmax_c <l2norm(x), l2norm(codebook[c])>  with the LOWEST index on exact ties
 //                 (restated eval path of vector_quantize_pytorch -- PARITY UNPINNED)
+//   vq_nearest_l2: idx = argmin_c ||x - codebook[c]||^2 (vq_use_cosine_sim = False), computed around the codebook's column mean
 #include "common.h"
 #include "../../include/amdnuwa.h"
 
@@ -355,8 +356,10 @@ __global__ __launch_bounds__(256, 2) void vq_argmax2_kernel(const float* __restr
         if ((lane & 31) == 0 && row < R) { part_v[(size_t)blockIdx.y * R + row] = v; part_i[(size_t)blockIdx.y * R + row] = ix; }
     }
 }
+// xnorm == nullptr: best_out = the winning value (cosine lookup); else best_out = max(xnorm[r] - 2 v, 0) (Euclidean lookup below)
 __global__ __launch_bounds__(256) void vq_combine_kernel(const float* __restrict__ part_v, const int* __restrict__ part_i, int S,
-                                                         long long R, long long* __restrict__ idx, float* __restrict__ best_sim) {
+                                                         long long R, long long* __restrict__ idx, float* __restrict__ best_sim,
+                                                         const float* __restrict__ xnorm) {
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
     if (r >= R) return;
     float v = part_v[r];
@@ -366,7 +369,7 @@ __global__ __launch_bounds__(256) void vq_combine_kernel(const float* __restrict
         if (ov > v) { v = ov; ix = part_i[(size_t)s * R + r]; }
     }
     idx[r] = ix;
-    if (best_sim) best_sim[r] = v;
+    if (best_sim) best_sim[r] = xnorm ? fmaxf(xnorm[r] - 2.f * v, 0.f) : v;
 }
 static int vq_slices(long long R, int Cn) {
     const long long rb = (R + 127) / 128;
@@ -375,6 +378,221 @@ static int vq_slices(long long R, int Cn) {
     if (s > smax) s = smax;
     if (s > 64) s = 64;
     return s < 1 ? 1 : s;
+}
+
+// ---- Euclidean VQ lookup: idx[r] = argmin_c ||x_r - c||^2, LOWEST index on exact ties, as argmax_c of the CENTRED score
+//   s(r, c) = (x_r - mu) . (c - mu) - 1/2 ||c - mu||^2,   mu = column mean of the codebook   (||x_r - c||^2 = ||x_r - mu||^2 - 2 s).
+// Distances do not change under a common shift, the fp32 arithmetic does: the expanded form around the origin adds 1/2 ||c||^2, whose
+// ulp on a tight codebook cloud away from the origin (100 + 0.05 randn, 256 dims: 1.3e6, ulp 0.125) exceeds the differences between
+// the distances, and picks wrong codes on nearly every row; around mu every term is of the size of the distances themselves.
+// Prep pass (fixed-order sums, no atomics: two runs agree bit for bit):
+//   colsum: part[p][d] = sum over the p-th run of codes of cb[c][d], codes in increasing order (one thread per column d)
+//   mean  : mu[d] = (part[0][d] + part[1][d] + ...) / Cn
+//   half  : half[c] = 1/2 sum_d (cb[c][d] - mu[d])^2, one wave per code, the same arithmetic for every code: duplicates get equal bits,
+//           and (c - mu) is rounded exactly as the lookup kernels round it while they stage the code tiles
+static int vq_l2_parts(int Cn) {
+    const int p = (Cn + 63) / 64;
+    return p > 256 ? 256 : p;
+}
+__global__ __launch_bounds__(256) void vq_l2_colsum_kernel(const float* __restrict__ cb, float* __restrict__ part, int Cn, int Dc) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= Dc) return;
+    const int per = (Cn + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int c0 = blockIdx.y * per, c1 = min(Cn, c0 + per);
+    float s = 0.f;
+#pragma unroll 8
+    for (int c = c0; c < c1; ++c) s += cb[(size_t)c * Dc + d];
+    part[(size_t)blockIdx.y * Dc + d] = s;
+}
+__global__ __launch_bounds__(256) void vq_l2_mean_kernel(const float* __restrict__ part, float* __restrict__ mu, int P, int Cn, int Dc) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= Dc) return;
+    float s = 0.f;
+#pragma unroll 8
+    for (int p = 0; p < P; ++p) s += part[(size_t)p * Dc + d];
+    mu[d] = s / (float)Cn;
+}
+__global__ __launch_bounds__(256) void vq_l2_half_kernel(const float* __restrict__ cb, const float* __restrict__ mu,
+                                                         float* __restrict__ half, int Cn, int Dc) {
+    const int lane = threadIdx.x & 63;
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= Cn) return;
+    float ss = 0.f;
+    for (int d = lane; d < Dc; d += 64) { const float v = cb[(size_t)c * Dc + d] - mu[d]; ss += v * v; }
+    ss = wave_sum(ss);
+    if (lane == 0) half[c] = 0.5f * ss;
+}
+
+// general form (any even code_dim whose two 64-row tiles fit LDS), structured as vq_argmax_kernel: no normalisation, mu is subtracted
+// while rows and code tiles are staged (rows >= R and codes >= Cn are staged as zeros and never win or get written), half[c] is
+// subtracted from the finished dot product.
+__global__ __launch_bounds__(256) void vq_nearest_l2_kernel(const float* __restrict__ x, const float* __restrict__ cb,
+                                                            const float* __restrict__ mu, const float* __restrict__ half,
+                                                            long long* __restrict__ idx, float* __restrict__ best_dist,
+                                                            long long R, int Cn, int Dc) {
+    extern __shared__ float sm[];
+    float* Xs = sm;                          // [64][Dc + 1] centred rows
+    float* Cs = Xs + 64 * (Dc + 1);          // [64][Dc + 1] centred code tile
+    float* bv = Cs + 64 * (Dc + 1);          // [2][64] best value per column half, then [64] ||x - mu||^2 at bv + 128
+    int* bi = reinterpret_cast<int*>(bv + 256);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long r0 = (long long)blockIdx.x * 64;
+    for (int rr = wave; rr < 64; rr += 4) {
+        const long long r = r0 + rr;
+        float ss = 0.f;
+        for (int d = lane; d < Dc; d += 64) { const float v = r < R ? x[r * Dc + d] - mu[d] : 0.f; Xs[rr * (Dc + 1) + d] = v; ss += v * v; }
+        ss = wave_sum(ss);
+        if (lane == 0) bv[128 + rr] = ss;
+    }
+    const int rb = (wave >> 1) * 32, cbk = (wave & 1) * 32;
+    float best[16];
+    int besti[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { best[r] = -3.0e38f; besti[r] = 0; }
+    for (int c0 = 0; c0 < Cn; c0 += 64) {
+        __syncthreads();
+        for (int cc = wave; cc < 64; cc += 4) {
+            const int cidx = c0 + cc;
+            for (int d = lane; d < Dc; d += 64) Cs[cc * (Dc + 1) + d] = cidx < Cn ? cb[(size_t)cidx * Dc + d] - mu[d] : 0.f;
+        }
+        const int code = c0 + cbk + (lane & 31);
+        const float hv = code < Cn ? half[code] : 0.f;
+        __syncthreads();
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int k = 0; k < Dc; k += 2) {
+            const float af = Xs[(rb + (lane & 31)) * (Dc + 1) + k + (lane >> 5)];
+            const float bf = Cs[(cbk + (lane & 31)) * (Dc + 1) + k + (lane >> 5)];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af, bf, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float s = acc[r] - hv;
+            if (code < Cn && s > best[r]) { best[r] = s; besti[r] = code; }
+        }
+    }
+    // reduce over the 32 lanes sharing a row (different codes): max value, lowest index on ties
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float v = best[r];
+        int ix = besti[r];
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) {
+            const float ov = __shfl_xor(v, o, 64);
+            const int oi = __shfl_xor(ix, o, 64);
+            if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
+        }
+        if ((lane & 31) == 0) {
+            const int row = rb + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            bv[(wave & 1) * 64 + row] = v;
+            bi[(wave & 1) * 64 + row] = ix;
+        }
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const long long r = r0 + tid;
+        if (r < R) {
+            const float v0 = bv[tid], v1 = bv[64 + tid];
+            const int i0 = bi[tid], i1 = bi[64 + tid];
+            const bool take1 = v1 > v0 || (v1 == v0 && i1 < i0);
+            idx[r] = take1 ? i1 : i0;
+            if (best_dist) best_dist[r] = fmaxf(bv[128 + tid] - 2.f * (take1 ? v1 : v0), 0.f);
+        }
+    }
+}
+
+// code_dim 256 form, structured as vq_argmax2_kernel: the 128 rows of a workgroup sit in registers as CENTRED A operands, the codes
+// stream through the double-buffered k-major LDS tile and are centred on the way in (mu [DC] sits in LDS behind the two tiles), the
+// code axis is cut in slices [cbeg, cend) that all start inside the codebook.  The columns of the last tile behind cend hold code cbeg
+// again (centred like any other: real data, no branch in the staging) and half[cend - 1], and are excluded from the comparison; rows
+// >= R read row R - 1 and are never written.
+template <int DC>
+__global__ __launch_bounds__(256, 2) void vq_nearest_l2_2_kernel(const float* __restrict__ x, const float* __restrict__ cb,
+                                                                 const float* __restrict__ mu, const float* __restrict__ half,
+                                                                 float* __restrict__ xnorm, float* __restrict__ part_v,
+                                                                 int* __restrict__ part_i, long long R, int Cn, int per_slice) {
+    extern __shared__ float sm[];                     // [2][DC][VQ_LD] code tiles, [DC] mu
+    float* mus = sm + (size_t)2 * DC * VQ_LD;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
+    const long long r0 = (long long)blockIdx.x * 128 + wave * 32;
+    const int cbeg = blockIdx.y * per_slice, cend = min(Cn, cbeg + per_slice);
+    for (int d = tid; d < DC; d += 256) mus[d] = mu[d];
+    __syncthreads();
+    // A operands: a[kk] = x[row (lane & 31)][2 kk + hi] - mu[2 kk + hi]
+    float a[DC / 2];
+    {
+        const long long row = r0 + (lane & 31);
+        const float* xr = x + (row < R ? row : R - 1) * DC + hi;
+        float ss = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < DC / 2; ++kk) { a[kk] = xr[2 * kk] - mus[2 * kk + hi]; ss += a[kk] * a[kk]; }
+        ss += __shfl_xor(ss, 32, 64);
+        if (blockIdx.y == 0 && hi == 0 && row < R) xnorm[row] = ss;
+    }
+    // staging map: thread -> code (tid >> 3) of the tile, 8 pieces of 4 consecutive k at k = (tid & 7) * 4 + 32 j
+    const int scode = tid >> 3, spart = (tid & 7) * 4;
+    float4 pre[DC / 32];
+    auto fetch = [&](int c0) {
+        const int c = c0 + scode;
+        const float* src = cb + (size_t)(c < cend ? c : cbeg) * DC + spart;
+#pragma unroll
+        for (int j = 0; j < DC / 32; ++j) pre[j] = *reinterpret_cast<const float4*>(src + 32 * j);
+    };
+    auto stash = [&](int buf) {
+        float* base = sm + (size_t)buf * DC * VQ_LD + scode;
+#pragma unroll
+        for (int j = 0; j < DC / 32; ++j) {
+            const int k = spart + 32 * j;
+            const float4 m = *reinterpret_cast<const float4*>(mus + k);
+            base[(k + 0) * VQ_LD] = pre[j].x - m.x; base[(k + 1) * VQ_LD] = pre[j].y - m.y;
+            base[(k + 2) * VQ_LD] = pre[j].z - m.z; base[(k + 3) * VQ_LD] = pre[j].w - m.w;
+        }
+    };
+    float best[16];
+    int besti[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { best[r] = -3.0e38f; besti[r] = cbeg; }
+    fetch(cbeg);
+    stash(0);
+    __syncthreads();
+    int buf = 0;
+    for (int c0 = cbeg; c0 < cend; c0 += VQ_TC, buf ^= 1) {
+        const bool more = c0 + VQ_TC < cend;
+        if (more) fetch(c0 + VQ_TC);                  // in flight under the MFMAs below
+        const int code = c0 + (lane & 31);
+        const float hv = half[min(code, cend - 1)];
+        const bool inside = code < cend;
+        const float* bt = sm + (size_t)buf * DC * VQ_LD + hi * VQ_LD + (lane & 31);
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < DC / 2; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], bt[2 * kk * VQ_LD], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float s = acc[r] - hv;
+            const bool take = inside & (s > best[r]);             // selects, no branch: the compare sits between two MFMA chains
+            best[r] = take ? s : best[r];
+            besti[r] = take ? code : besti[r];
+        }
+        if (more) stash(buf ^ 1);
+        __syncthreads();
+    }
+    // lanes sharing a row hold different codes: max value, lowest index on ties
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float v = best[r];
+        int ix = besti[r];
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) {
+            const float ov = __shfl_xor(v, o, 64);
+            const int oi = __shfl_xor(ix, o, 64);
+            if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
+        }
+        const long long row = r0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        if ((lane & 31) == 0 && row < R) { part_v[(size_t)blockIdx.y * R + row] = v; part_i[(size_t)blockIdx.y * R + row] = ix; }
+    }
 }
 
 // ---- VQGanAttention core (vq.py:244-286), exact fp32 ----------------------------------------------------------------
@@ -962,8 +1180,11 @@ extern "C" int amdnuwa_vq_argmax_ws(const float* x, const float* codebook, long 
     if (!x || !codebook || !indices || n_codes <= 0) return AMDNUWA_ERR_ARG;
     if (R <= 0) return AMDNUWA_OK;
     if (!workspace || workspace_bytes < amdnuwa_vq_argmax_workspace_bytes(R, n_codes)) return AMDNUWA_ERR_WORKSPACE;
-    const int S = vq_slices(R, n_codes);
+    int S = vq_slices(R, n_codes);
     const int per_slice = ((n_codes + S - 1) / S + VQ_TC - 1) / VQ_TC * VQ_TC;
+    // rounding per_slice up to whole tiles can leave slices that start behind the codebook (2600 rows x 8192 codes: 49 slices of 192);
+    // they could never win the combine, but their first fetch formed addresses past the codebook: not launched any more
+    S = (n_codes + per_slice - 1) / per_slice;
     float* inv = (float*)workspace;
     float* part_v = inv + n_codes;
     int* part_i = (int*)(part_v + (size_t)S * R);
@@ -974,7 +1195,61 @@ extern "C" int amdnuwa_vq_argmax_ws(const float* x, const float* codebook, long 
     hipLaunchKernelGGL((vq_argmax2_kernel<256>), dim3((unsigned)((R + 127) / 128), S), dim3(256), lds, stream, x, codebook, inv, part_v,
                        part_i, R, n_codes, per_slice);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(vq_combine_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, part_v, part_i, S, R, indices, best_sim);
+    hipLaunchKernelGGL(vq_combine_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, part_v, part_i, S, R, indices, best_sim,
+                       (const float*)nullptr);
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+
+// Euclidean lookup.  Workspace, in floats: mu [code_dim] | column partial sums [P][code_dim] | half [n_codes] | ||x - mu||^2 [R] |
+// partial values [S][R] | partial indices [S][R]
+static size_t vq_l2_lds_bytes(int code_dim) { return ((size_t)2 * 64 * (code_dim + 1) + 256) * sizeof(float) + 128 * sizeof(int); }
+extern "C" size_t amdnuwa_vq_nearest_l2_workspace_bytes(long long R, int n_codes, int code_dim) {
+    if (R <= 0 || n_codes <= 0 || code_dim <= 0) return 0;
+    return ((size_t)code_dim * (1 + (size_t)vq_l2_parts(n_codes)) + (size_t)n_codes + (size_t)R +
+            (size_t)vq_slices(R, n_codes) * (size_t)R * 2) * sizeof(float) + 64;
+}
+
+extern "C" int amdnuwa_vq_nearest_l2(const float* x, const float* codebook, long long* indices, float* best_dist, long long R,
+                                     int n_codes, int code_dim, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    if (!x || !codebook || !indices || n_codes <= 0 || code_dim <= 0 || code_dim % 2) return AMDNUWA_ERR_ARG;
+    if (R <= 0) return AMDNUWA_OK;
+    if (!workspace || workspace_bytes < amdnuwa_vq_nearest_l2_workspace_bytes(R, n_codes, code_dim)) return AMDNUWA_ERR_WORKSPACE;
+    const bool sliced = code_dim == 256 && g_amdnuwa_tuning[15] != 1;
+    const size_t lds1 = vq_l2_lds_bytes(code_dim);
+    if (!sliced && lds1 > 160 * 1024) return AMDNUWA_ERR_UNSUPPORTED;
+    const int P = vq_l2_parts(n_codes);
+    float* mu = (float*)workspace;
+    float* mu_part = mu + code_dim;
+    float* half = mu_part + (size_t)P * code_dim;
+    float* xnorm = half + n_codes;
+    hipLaunchKernelGGL(vq_l2_colsum_kernel, dim3((unsigned)((code_dim + 255) / 256), P), dim3(256), 0, stream, codebook, mu_part, n_codes,
+                       code_dim);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(vq_l2_mean_kernel, dim3((unsigned)((code_dim + 255) / 256)), dim3(256), 0, stream, mu_part, mu, P, n_codes, code_dim);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(vq_l2_half_kernel, dim3((n_codes + 3) / 4), dim3(256), 0, stream, codebook, mu, half, n_codes, code_dim);
+    LAUNCH_CHECK();
+    if (!sliced) {
+        (void)hipFuncSetAttribute((const void*)vq_nearest_l2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
+        hipLaunchKernelGGL(vq_nearest_l2_kernel, dim3((unsigned)((R + 63) / 64)), dim3(256), lds1, stream, x, codebook, mu, half, indices,
+                           best_dist, R, n_codes, code_dim);
+        LAUNCH_CHECK();
+        return AMDNUWA_OK;
+    }
+    // the slice count of the cosine form, then shrunk so that every slice starts inside the codebook (no empty slice, no address past it)
+    int S = vq_slices(R, n_codes);
+    const int per_slice = ((n_codes + S - 1) / S + VQ_TC - 1) / VQ_TC * VQ_TC;
+    S = (n_codes + per_slice - 1) / per_slice;
+    float* part_v = xnorm + R;
+    int* part_i = (int*)(part_v + (size_t)S * R);
+    const size_t lds = ((size_t)2 * 256 * VQ_LD + 256) * sizeof(float);
+    (void)hipFuncSetAttribute((const void*)vq_nearest_l2_2_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((vq_nearest_l2_2_kernel<256>), dim3((unsigned)((R + 127) / 128), S), dim3(256), lds, stream, x, codebook, mu, half,
+                       xnorm, part_v, part_i, R, n_codes, per_slice);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(vq_combine_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, part_v, part_i, S, R, indices, best_dist,
+                       (const float*)xnorm);
     LAUNCH_CHECK();
     return AMDNUWA_OK;
 }

@@ -1920,6 +1920,20 @@ def vq_argmax(x, codebook, want_sim=False):
     return (idx, sim) if want_sim else idx
 
 
+def vq_nearest_l2(x, codebook, want_dist=False):
+    """x [R, Dc], codebook [Cn, Dc] fp32 -> int64 indices [R] of the nearest code (Euclidean, lowest index on ties), computed around the
+    codebook mean (amdnuwa_vq_nearest_l2); want_dist: also the squared distance to the picked code [R]."""
+    L = _lib.lib()
+    x, codebook = _f32c(x), _f32c(codebook)
+    R, Dc = x.shape
+    idx = torch.empty((R,), dtype=torch.int64, device=x.device)
+    dist = torch.empty((R,), dtype=torch.float32, device=x.device) if want_dist else None
+    nb = L.amdnuwa_vq_nearest_l2_workspace_bytes(R, codebook.shape[0], Dc)
+    ws = workspace(nb, x.device)
+    check(L.amdnuwa_vq_nearest_l2(_p(x), _p(codebook), _p(idx), _p(dist), R, codebook.shape[0], Dc, _p(ws), nb, _stream()), 'amdnuwa_vq_nearest_l2')
+    return (idx, dist) if want_dist else idx
+
+
 def vqattn_core(qkv, scale, heads, bias=None, rel_table=None):
     """the attention core of VQGanAttention alone: qkv [N, 3*heads*c, ...positions] fp32 with q and k already l2-normalised, scale the
     learned log-scale [heads]; out[n, h*c + cc, i] = sum_j softmax_j(q_i . k_j * exp(scale_h) + bias_h(i, j)) v[cc, j].  The bias is

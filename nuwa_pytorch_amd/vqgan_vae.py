@@ -80,9 +80,10 @@ class _Codebook(nn.Module):
 
 
 class VectorQuantize(nn.Module):
-    """cosine-similarity vector quantiser with EMA codebook (restatement; PARITY UNPINNED).
-    eval path: x = project_in(b (h w) c); idx = argmax_c(l2norm(x) . l2norm(embed)^T) (lowest index on
-    ties); quantized = project_out(embed[idx]); loss = 0."""
+    """vector quantiser with EMA codebook, cosine-similarity or Euclidean (`use_cosine_sim`; restatement; PARITY UNPINNED).
+    eval path: x = project_in(b (h w) c); idx = argmax_c(l2norm(x) . l2norm(embed)^T) with use_cosine_sim, else
+    idx = argmin_c ||x - embed[c]|| (lowest index on ties either way); quantized = project_out(embed[idx]); loss = 0.
+    The device tokenizer (VQGanVAE.get_video_indices) runs either lookup in libamdnuwa: kernels.vq_argmax / kernels.vq_nearest_l2."""
 
     def __init__(self, dim, codebook_size, codebook_dim=None, decay=0.8, commitment_weight=1.,
                  accept_image_fmap=False, kmeans_init=False, use_cosine_sim=False, eps=1e-5, **kwargs):
@@ -119,6 +120,9 @@ class VectorQuantize(nn.Module):
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def _nearest(self, flat):
+        """torch path of encode() / forward().  Its Euclidean branch is torch.cdist, the expanded form ||x||^2 - 2 x.c + ||c||^2 around
+        the origin, which loses the pick on a tight codebook cloud far from the origin; the device tokenizer (kernels.vq_nearest_l2)
+        computes around the codebook mean and is the conditioned one."""
         if self.use_cosine_sim:
             feats = l2norm(flat)
             if self.training and not bool(self.initted):          # first training batch seeds the codebook
@@ -424,8 +428,6 @@ class VQGanVAE(nn.Module):
 
     def _hip_encode_indices(self, images):
         from . import kernels as K
-        if not self.vq.use_cosine_sim:
-            raise NotImplementedError('libamdnuwa VQ lookup implements the cosine-similarity codebook (vq_use_cosine_sim=True)')
         fmap = images.float()
         for enc in self.encoders:
             fmap = self._hip_module(enc, fmap)
@@ -434,7 +436,8 @@ class VQGanVAE(nn.Module):
         if isinstance(pin, nn.Linear):
             fmap = K.conv2d_fwd(fmap, pin.weight[:, :, None, None], pin.bias, 1, 0)
         rows = fmap.permute(0, 2, 3, 1).reshape(B * Hh * Ww, -1)
-        return K.vq_argmax(rows, self.vq.embed).reshape(B, Hh, Ww)
+        lookup = K.vq_argmax if self.vq.use_cosine_sim else K.vq_nearest_l2
+        return lookup(rows, self.vq.embed).reshape(B, Hh, Ww)
 
     @torch.no_grad()
     @eval_decorator

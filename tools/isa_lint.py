@@ -119,7 +119,7 @@ SCRATCH_BOUNDS = [('gemm_nt_256p_kernel', 0), ('gemm_nt_256_kernel', 0), ('gemm_
                   ('gemm_nt_256x3_kernel', 0), ('ln_post_pre_kernel', 0), ('ln_bwd_chain_kernel', 0), ('ln_fwd_kernel', 0), ('s3_fwd_tile_kernel', 0),
                   ('s3_fwd_mfma_kernel', 0), ('s3_bwd_q_mfma_kernel', 60), ('s3_bwd_kv_mfma_kernel', 0), ('xattn4_fwd_kernel', 0), ('xattn3_bwd_kernel', 272),
                   ('ce_fwd_reg_kernel', 0), ('splitk_reduce_kernel', 0), ('rows_stats_kernel', 0), ('rows_apply_kernel', 0), ('rows_reduce_kernel', 0),
-                  ('vqattn_tiled_kernel', 0), ('prefill_ln_kernel', 0), ('prefill_shift_kernel', 0), ('prefill_kv_kernel', 0)]
+                  ('vqattn_tiled_kernel', 0), ('vq_argmax2_kernel', 0), ('vq_nearest_l2', 0), ('prefill_ln_kernel', 0), ('prefill_shift_kernel', 0), ('prefill_kv_kernel', 0)]
 
 
 def check_shipped(lib=None):
