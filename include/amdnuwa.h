@@ -41,7 +41,8 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 *     amdnuwa_prefill_kv, the cache prefill of a sliding generate() window, and amdnuwa_cross2dna_decode with its
                                                 *     _workspace_bytes, the single-query SparseCross2DNA over a window of any size, and amdnuwa_sample_next_row, the
                                                 *     sampling tail of a generate() token, and amdnuwa_vq_nearest_l2 with its _workspace_bytes, the Euclidean
-                                                *     code lookup of the tokenizer) */
+                                                *     code lookup of the tokenizer, and amdnuwa_cross2dna_rows with its _workspace_bytes, the rows form of
+                                                *     amdnuwa_cross2dna_decode for the cache prefill of NUWASketch.generate) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -654,6 +655,27 @@ int amdnuwa_cross2dna_decode(int B, int J, int heads, int dim_head, float scale,
                              const uint16_t* kv, const uint16_t* kv_lo, int ctx_rows, const int* slot_rows, int n_pos, const int* pos,
                              const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o,
                              uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
+/* The ROWS FORM of amdnuwa_cross2dna_decode (added at ABI 21, purely additive): decoder rows 1 .. R-1 of every sample in one call, the
+ * window read in place -- the cache prefill of a NUWASketch.generate whose frame window slides.  q and o are [B * R, ld] bf16 hi (+ lo)
+ * rows, sample-major: the query of row r (1 <= r < R) of sample b is row b * R + r, sits at feature-map position (r - 1) mod n_pos and
+ * attends through slot_rows[(r - 1) mod n_pos], exactly as the single-row call does at pos[0] = r.  There is no device-side position: the
+ * rows are given by the launch.  Row 0 of every sample (<bos>) is NEITHER READ NOR WRITTEN, it stays with the caller; R == 1 returns
+ * AMDNUWA_OK without a launch (and needs no workspace).  kv, slot_rows, key_mask, null_k, null_v, w_th and scale are those of
+ * amdnuwa_cross2dna_decode.  The kernels are the single row's, told by the launch which query a workgroup serves: the same loads,
+ * expression trees, 128-slot splits and meeting order, no atomics -- row (b, r) of o is BIT-IDENTICAL to amdnuwa_cross2dna_decode on
+ * q[b * R + r] at pos[0] = r, with and without the lo images, and two runs are bit-identical.  A query whose table row has an entry
+ * >= ctx_rows writes nothing (decided per query row, alike in all three launches; the other rows are served); negative entries are padding
+ * and never become an address.  Queries are indexed on the x dimension of the grid and taken in chunks of 2048 (three launches per chunk on
+ * `stream`, which share the workspace), so B * (R - 1) may exceed 65 535; B * R must fit an int.  Arguments are checked first (a null
+ * pointer, a non-positive B / R / J / heads / dim_head / ctx_rows / n_pos, lo images not given together, ld < heads * dim_head:
+ * AMDNUWA_ERR_ARG), then the envelope (heads 1..8, dim_head 32 / 64, otherwise AMDNUWA_ERR_UNSUPPORTED), then the workspace:
+ * >= _workspace_bytes = the single-row formula with min(B * R, 2048) -- one chunk -- in place of B,
+ * 4 * min(B * R, 2048) * (heads * (J + 1) + ceil((J + 1) / 128) * (2 * heads + heads * dim_head)) bytes, AMDNUWA_ERR_WORKSPACE otherwise. */
+size_t amdnuwa_cross2dna_rows_workspace_bytes(int B, int R, int J, int heads, int dim_head);
+int amdnuwa_cross2dna_rows(int B, int R, int J, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo, int ldq,
+                           const uint16_t* kv, const uint16_t* kv_lo, int ctx_rows, const int* slot_rows, int n_pos,
+                           const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o,
+                           uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
 /* The end of one generate() token on the device (np.py:55-65, 1713-1720, 1883-1908; added at ABI 21, purely additive): sample a class from
  * the guided logits and assemble the decoder input row that follows.  logits [B][ld] fp32 (C classes, ld >= C); keep >= 1, keep <= C;
  * temperature > 0; u [B][keep] fp32 uniforms, NULL exactly when keep == 1; emb [C][D] and pos [P][D] fp32; pos_idx [cap] int32 and step [1]

@@ -125,6 +125,8 @@ SIGNATURES = {
     'amdnuwa_attn_decode_rows': (I, [I, I, I, I, F, P, P, I, P, P, I, P, P, P, P, P, P, P, P, I, P, SZ, P]),
     'amdnuwa_cross2dna_decode_workspace_bytes': (SZ, [I, I, I, I]),
     'amdnuwa_cross2dna_decode': (I, [I, I, I, I, F, P, P, I, P, P, I, P, I, P, P, P, P, P, P, P, I, P, SZ, P]),
+    'amdnuwa_cross2dna_rows_workspace_bytes': (SZ, [I, I, I, I, I]),
+    'amdnuwa_cross2dna_rows': (I, [I, I, I, I, I, F, P, P, I, P, P, I, P, I, P, P, P, P, P, P, I, P, SZ, P]),
     'amdnuwa_sample_next_row': (I, [I, I, I, F, P, I, P, P, I, P, I, P, I, P, P, P, P]),
     'amdnuwa_xattn_jp': (I, [I]),
     'amdnuwa_xattn_pack': (I, [XG, P, P, I, P, P, P, XK, P]),

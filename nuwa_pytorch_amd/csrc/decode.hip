@@ -427,7 +427,14 @@ __global__ __launch_bounds__(1024) void xattn_decode_kernel(XDecArgs a) {
 // i = (pos - 1) mod n_pos the query's feature-map position; a negative entry is 'same' padding -- hidden, never turned into an address --
 // and the key mask is indexed by context row.  Every workgroup reads the table row of i ONCE, keeps its own split's entries in LDS and
 // checks all of them against cache_rows on the way, so that all workgroups of the three launches agree on whether anything is written.
+//
+// TAB has a ROWS FORM (RowsArgs::R > 0, amdnuwa_cross2dna_rows): the launch serves query rows 1 .. R-1 of every sample at once (the cache
+// prefill of a sliding NUWASketch.generate window).  Only the bookkeeping differs -- which sample's context, which q / o row, which
+// workspace row and which decoder row a workgroup serves come from blockIdx.x (rows_who) instead of (blockIdx.y, the device-side position);
+// the loads, the expression trees, the 128-slot splits and the order in which partial results meet are the single row's own code, so row
+// (b, r) is bit-identical to the single-row launch on q[b * R + r] at pos = r.
 constexpr int ROWS_SPLIT = 128;
+constexpr int ROWS_CHUNK = 2048;     // rows form: queries per set of three launches (bounds the workspace, not the result)
 constexpr float ROWS_NEG = -3.4028234663852886e38f;
 
 struct RowsArgs {
@@ -442,17 +449,40 @@ struct RowsArgs {
     float scale;
     const int* tab;                  // TAB: [n_pos][T] cache row of every slot, < 0 = padding; `first` then holds the decoder row
     int n_pos;
-};
+    int R, u0;                       // TAB rows form (R > 1; 0 = one row per sample): blockIdx.x counts (query, split) from query u0 on,
+};                                   // query u = sample u / (R-1), decoder row 1 + u % (R-1); `first` is not read
+
+// what a workgroup serves: split sp of the query at row qr of q / o, which belongs to sample b (kv, mask) and keeps its scores, statistics
+// and partial rows in workspace row wr; pos = its decoder row in the rows form, -1 = read the device-side one
+struct RowsWho { int sp, b, qr, wr, pos; };
+
+template <bool TAB>
+__device__ __forceinline__ RowsWho rows_who(const RowsArgs& a, bool reduce) {
+    RowsWho w;
+    if (TAB && a.R > 0) {
+        const int ul = reduce ? (int)blockIdx.x : (int)blockIdx.x / a.nsplit, u = a.u0 + ul;
+        w.sp = reduce ? 0 : (int)blockIdx.x - ul * a.nsplit;
+        w.b = u / (a.R - 1);
+        w.pos = 1 + u - w.b * (a.R - 1);
+        w.qr = w.b * a.R + w.pos;
+        w.wr = ul;
+    } else {
+        w.sp = reduce ? 0 : (int)blockIdx.x;
+        w.b = w.qr = w.wr = reduce ? (int)blockIdx.x : (int)blockIdx.y;
+        w.pos = -1;
+    }
+    return w;
+}
 
 __device__ __forceinline__ bool rows_window_ok(const RowsArgs& a, int first) {
     return first >= 0 && (long long)first + a.T <= (long long)a.cache_rows;
 }
 
-// first <- the device-side row; false (for every thread of every workgroup of the launch alike): nothing is written.
+// first <- the device-side row (pos < 0) or pos; false (for every thread of every workgroup that serves this query alike): nothing is written.
 // TAB: krow[j] <- the cache row of slot j0 + j for j < Jl (-1 for the null key's slot 0), visible to the whole workgroup on return
 template <bool TAB>
-__device__ __forceinline__ bool rows_begin(const RowsArgs& a, int* krow, int j0, int Jl, int& first) {
-    first = a.first[0];
+__device__ __forceinline__ bool rows_begin(const RowsArgs& a, int* krow, int j0, int Jl, int pos, int& first) {
+    first = pos < 0 ? a.first[0] : pos;
     if constexpr (!TAB) {
         return rows_window_ok(a, first);
     } else {
@@ -484,11 +514,12 @@ __global__ __launch_bounds__(256) void rows_stats_kernel(RowsArgs a) {
     __shared__ int ok[ROWS_SPLIT];
     __shared__ int krow[ROWS_SPLIT];
     const int NH = a.heads, DH = a.dim_head, inner = NH * DH, QS = DH + 1, J = a.T + 1;
-    const int sp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const RowsWho who = rows_who<TAB>(a, false);
+    const int sp = who.sp, b = who.b, wr = who.wr, tid = threadIdx.x;
     const int j0 = sp * ROWS_SPLIT, Jl = min(ROWS_SPLIT, J - j0);
     int first;
-    if (!rows_begin<TAB>(a, krow, j0, Jl, first)) return;
-    for (int c = tid; c < inner; c += blockDim.x) qs[(c / DH) * QS + c % DH] = ld_hl(a.q, a.ql, (size_t)b * a.ldq + c) * a.scale;
+    if (!rows_begin<TAB>(a, krow, j0, Jl, who.pos, first)) return;
+    for (int c = tid; c < inner; c += blockDim.x) qs[(c / DH) * QS + c % DH] = ld_hl(a.q, a.ql, (size_t)who.qr * a.ldq + c) * a.scale;
     for (int j = tid; j < Jl; j += blockDim.x) ok[j] = rows_slot_ok<TAB>(a, krow, b, j0, j);
     __syncthreads();
     const size_t kvb = (size_t)b * a.cache_rows * 2 * inner;
@@ -506,7 +537,7 @@ __global__ __launch_bounds__(256) void rows_stats_kernel(RowsArgs a) {
             }
         }
         s[h * ROWS_SPLIT + j] = sc;
-        a.sc[((size_t)b * J + jg) * NH + h] = sc;
+        a.sc[((size_t)wr * J + jg) * NH + h] = sc;
     }
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
@@ -518,7 +549,7 @@ __global__ __launch_bounds__(256) void rows_stats_kernel(RowsArgs a) {
         for (int j = lane; j < Jl; j += 64) sum += ok[j] ? __expf(s[h * ROWS_SPLIT + j] - m) : 0.f;
         sum = wave_sum(sum);
         if (lane == 0) {
-            float* st = a.st + (((size_t)b * a.nsplit + sp) * NH + h) * 2;
+            float* st = a.st + (((size_t)wr * a.nsplit + sp) * NH + h) * 2;
             st[0] = m;
             st[1] = sum;
         }
@@ -534,12 +565,13 @@ __global__ __launch_bounds__(256) void rows_apply_kernel(RowsArgs a) {
     __shared__ int ok[ROWS_SPLIT];
     __shared__ int krow[ROWS_SPLIT];
     const int NH = a.heads, DH = a.dim_head, inner = NH * DH, J = a.T + 1;
-    const int sp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const RowsWho who = rows_who<TAB>(a, false);
+    const int sp = who.sp, b = who.b, wr = who.wr, tid = threadIdx.x;
     const int j0 = sp * ROWS_SPLIT, Jl = min(ROWS_SPLIT, J - j0);
     int first;
-    if (!rows_begin<TAB>(a, krow, j0, Jl, first)) return;
+    if (!rows_begin<TAB>(a, krow, j0, Jl, who.pos, first)) return;
     if (tid < NH) {                                               // the statistics of all splits meet in index order (eight loads in
-        const float* st = a.st + ((size_t)b * a.nsplit * NH + tid) * 2;   // flight at a time: one thread walks a chain of latencies)
+        const float* st = a.st + ((size_t)wr * a.nsplit * NH + tid) * 2;   // flight at a time: one thread walks a chain of latencies)
         float M = ROWS_NEG;
         for (int i0 = 0; i0 < a.nsplit; i0 += 8) {
             float mv[8];
@@ -567,7 +599,7 @@ __global__ __launch_bounds__(256) void rows_apply_kernel(RowsArgs a) {
     __syncthreads();
     for (int idx = tid; idx < NH * Jl; idx += blockDim.x) {
         const int j = idx / NH, h = idx - j * NH;
-        const float sv = a.sc[((size_t)b * J + j0 + j) * NH + h];
+        const float sv = a.sc[((size_t)wr * J + j0 + j) * NH + h];
         pr[h * ROWS_SPLIT + j] = ok[j] ? __expf(sv - mz[h]) * mz[8 + h] : 0.f;
     }
     __syncthreads();
@@ -600,17 +632,18 @@ __global__ __launch_bounds__(256) void rows_apply_kernel(RowsArgs a) {
         float t = 0.f;
         for (int gi = 0; gi < ngrp; ++gi) t += red[gi * inner + c];
         if (sp == 0) t = fmaf(pm[(c / DH) * ROWS_SPLIT], a.nv[c], t);
-        a.part[((size_t)b * a.nsplit + sp) * inner + c] = t;
+        a.part[((size_t)wr * a.nsplit + sp) * inner + c] = t;
     }
 }
 
 template <bool TAB>
 __global__ __launch_bounds__(256) void rows_reduce_kernel(RowsArgs a) {
-    const int inner = a.heads * a.dim_head, b = blockIdx.x;
+    const int inner = a.heads * a.dim_head;
+    const RowsWho who = rows_who<TAB>(a, true);
     int first;
-    if (!rows_begin<TAB>(a, nullptr, 0, 0, first)) return;
+    if (!rows_begin<TAB>(a, nullptr, 0, 0, who.pos, first)) return;
     for (int c = threadIdx.x; c < inner; c += blockDim.x) {
-        const float* part = a.part + (size_t)b * a.nsplit * inner + c;
+        const float* part = a.part + (size_t)who.wr * a.nsplit * inner + c;
         float t = 0.f;
         for (int i0 = 0; i0 < a.nsplit; i0 += 8) {                // index order, eight loads in flight
             float pv[8];
@@ -619,7 +652,7 @@ __global__ __launch_bounds__(256) void rows_reduce_kernel(RowsArgs a) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) t += pv[k];
         }
-        st_hl(a.o, a.ol, (size_t)b * a.ldo + c, t);
+        st_hl(a.o, a.ol, (size_t)who.qr * a.ldo + c, t);
     }
 }
 
@@ -777,10 +810,11 @@ size_t rows_ws_floats(int B, int T, int heads, int dim_head, int& nsplit) {
     return (size_t)B * ((size_t)heads * (T + 1) + (size_t)nsplit * (2 * heads + heads * dim_head));
 }
 
-// the three launches of one single-query attention: one workgroup per (split, sample), then one per sample
+// the three launches of one single-query attention: one workgroup per (split, sample), then one per sample; the rows form (a.R > 0)
+// counts B queries from a.u0 on, (query, split) on the x dimension -- the y dimension ends at 65 535
 template <bool TAB>
 void rows_launch(const RowsArgs& a, int B, hipStream_t stream) {
-    const dim3 grid(a.nsplit, B);
+    const dim3 grid = a.R > 0 ? dim3((unsigned)a.nsplit * B) : dim3(a.nsplit, B);
     if (a.dim_head == 64) hipLaunchKernelGGL((rows_stats_kernel<64, TAB>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((rows_stats_kernel<32, TAB>), grid, dim3(256), 0, stream, a);
     hipLaunchKernelGGL((rows_apply_kernel<TAB>), grid, dim3(256), 0, stream, a);
@@ -843,6 +877,40 @@ extern "C" int amdnuwa_cross2dna_decode(int B, int J, int heads, int dim_head, f
     a.st = a.sc + (size_t)B * heads * (J + 1);
     a.part = a.st + (size_t)B * a.nsplit * heads * 2;
     rows_launch<true>(a, B, stream);
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+
+extern "C" size_t amdnuwa_cross2dna_rows_workspace_bytes(int B, int R, int J, int heads, int dim_head) {
+    if (B <= 0 || R <= 0) return 0;
+    const long long rows = (long long)B * R;
+    return amdnuwa_attn_decode_rows_workspace_bytes((int)(rows < ROWS_CHUNK ? rows : ROWS_CHUNK), J, heads, dim_head);
+}
+
+extern "C" int amdnuwa_cross2dna_rows(int B, int R, int J, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo,
+                                      int ldq, const uint16_t* kv, const uint16_t* kv_lo, int ctx_rows, const int* slot_rows, int n_pos,
+                                      const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o,
+                                      uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    if (!q || !kv || !slot_rows || !null_k || !null_v || !w_th || !o) return AMDNUWA_ERR_ARG;
+    if (B <= 0 || R <= 0 || J <= 0 || heads <= 0 || dim_head <= 0 || ctx_rows <= 0 || n_pos <= 0) return AMDNUWA_ERR_ARG;
+    if ((long long)B * R > 0x7fffffffLL) return AMDNUWA_ERR_ARG;                  // (the q / o row index is an int)
+    if ((q_lo != nullptr) != (kv_lo != nullptr) || (q_lo != nullptr) != (o_lo != nullptr)) return AMDNUWA_ERR_ARG;
+    if ((long long)ldq < (long long)heads * dim_head || (long long)ldo < (long long)heads * dim_head) return AMDNUWA_ERR_ARG;
+    if (heads > 8 || (dim_head != 32 && dim_head != 64)) return AMDNUWA_ERR_UNSUPPORTED;
+    if (R == 1) return AMDNUWA_OK;                                                // <bos> alone: the caller's row, nothing to launch
+    const long long all = (long long)B * R;
+    const int rows = (int)(all < ROWS_CHUNK ? all : ROWS_CHUNK), total = B * (R - 1);
+    RowsArgs a{};
+    const size_t nf = rows_ws_floats(rows, J, heads, dim_head, a.nsplit);
+    if (!workspace || workspace_bytes < nf * sizeof(float)) return AMDNUWA_ERR_WORKSPACE;
+    a.q = q; a.ql = q_lo; a.kv = kv; a.kvl = kv_lo; a.first = nullptr; a.mask = key_mask; a.nk = null_k; a.nv = null_v;
+    a.wth = w_th; a.bias = nullptr; a.o = o; a.ol = o_lo; a.ldq = ldq; a.ldo = ldo; a.cache_rows = ctx_rows; a.T = J;
+    a.heads = heads; a.dim_head = dim_head; a.scale = scale; a.tab = slot_rows; a.n_pos = n_pos; a.R = R;
+    a.sc = static_cast<float*>(workspace);
+    a.st = a.sc + (size_t)rows * heads * (J + 1);
+    a.part = a.st + (size_t)rows * a.nsplit * heads * 2;
+    // chunks of at most ROWS_CHUNK queries share the workspace: the launches of a stream run in order
+    for (a.u0 = 0; a.u0 < total; a.u0 += ROWS_CHUNK) rows_launch<true>(a, total - a.u0 < ROWS_CHUNK ? total - a.u0 : ROWS_CHUNK, stream);
     LAUNCH_CHECK();
     return AMDNUWA_OK;
 }

@@ -15,7 +15,8 @@ embedding changes and with it every cached row of every layer.  IncrementalDecod
 with ONE full-sequence pass over the rows the new window already determines -- the same block walk as step() (IncrementalDecoder._walk)
 in its R-rows mode: the rows forms of the two norm / cache kernels (amdnuwa_prefill_ln, amdnuwa_prefill_kv) and the full-sequence
 attention cores of the training path, in the operand forms of the single row -- after which the captured row step serves the new
-frame's tokens again.
+frame's tokens again.  NUWASketch.generate slides the same way (np.py:2470-2474): its SparseCross2DNA blocks take the rows form of their
+single-row kernel (amdnuwa_cross2dna_rows), the window read in place.
 
 NUWAVideoAudio.generate (np.py:2111-2222) decodes two interleaved streams through the DualModalityDecoder (np.py:1299-1487).  Every
 stage is row-causal there too: the audio window attention looks back only, and the chunked video <-> audio attention lets frame t
@@ -208,8 +209,9 @@ class IncrementalDecoder:
 
     def _walk(self, x, R=None, bos=False):
         """The one loop over the blocks.  R None: x fp32 [B, D], the row at pos_dev of every sample, single-row kernels against the caches
-        (step).  R: x [B * R, D], sample-major rows 0 .. R-1 (prefill).  The modes differ in _norm and in the attention core of 's3' and
-        'x'; only the single row has 'xm' / 'xc2' blocks and store hooks (prefill refuses them before it gets here)."""
+        (step).  R: x [B * R, D], sample-major rows 0 .. R-1 (prefill).  The modes differ in _norm and in the attention core of 's3', 'x'
+        and 'xc2' (its rows program, _Cross2DNARows.attend_rows); only the single row has 'xm' blocks and store hooks (prefill refuses
+        them before it gets here)."""
         B, fast, blocks = self.B, ops._fast(), self.blocks
         state = [x] * self.halves
         h = self._enter(x, blocks[0], R)
@@ -251,7 +253,7 @@ class IncrementalDecoder:
                 y = K.gemm_nt(o, W['out'], out_bf16=out16)
             elif blk.kind == 'xc2':
                 W = ops.XInner.weights(inner._cache, inner._params())
-                o = blk.c2.attend(h, W, self.pos_dev, bos)
+                o = blk.c2.attend(h, W, self.pos_dev, bos) if R is None else blk.c2.attend_rows(h, W, R)
                 y = K.gemm_nt(o, W['out'], out_bf16=out16)
             else:
                 W = ops.FFInner.weights(inner._cache, inner._params())
@@ -290,8 +292,9 @@ class IncrementalDecoder:
         B, R, D = x_rows.shape
         if B != self.B or not 1 <= R <= self.rows:
             raise ValueError(f'IncrementalDecoder.prefill: {B} x {R} rows do not fit caches of {self.B} x {self.rows} rows')
-        if any(b.kind in ('xm', 'xc2') or b.store_before or b.store_after for b in self.blocks):
-            raise NotImplementedError('IncrementalDecoder.prefill: no full-sequence cache prefill for cross-modality / SparseCross2DNA blocks')
+        if any(b.kind == 'xm' or b.store_before or b.store_after or (b.kind == 'xc2' and getattr(b, 'c2', None) is None) for b in self.blocks):
+            raise NotImplementedError('IncrementalDecoder.prefill: no full-sequence cache prefill for cross-modality blocks, store hooks '
+                                      'or a SparseCross2DNA block without a rows program')
         return self._walk(x_rows.reshape(B * R, D).contiguous(), R).reshape(B, R, D)
 
 
@@ -321,7 +324,10 @@ class _Cross2DNARows:
     takes the earlier path instead: gather the window's rows, pack them with amdnuwa_xattn_pack (padding slots and masked sketch tokens
     through its key mask), attend with amdnuwa_xattn_decode.  Row 0 (<bos>) attends to ALL context tokens without talking heads
     (np.py:826-849): B rows of glue arithmetic, as in the training path (ops.XC2Inner).  With every context token masked (the
-    second pass of classifier-free guidance) both outputs are constants, computed once."""
+    second pass of classifier-free guidance) both outputs are constants, computed once.
+
+    attend_rows is the rows form for the cache prefill of a sliding window (IncrementalDecoder.prefill): rows 0 .. R-1 of every sample in
+    one pass -- one to_q GEMM, the <bos> glue on rows b * R, amdnuwa_cross2dna_rows for the others."""
 
     def __init__(self, mod, batch, ctx_bf, mask_u8, all_masked, lo):
         dev = ctx_bf.hi.device
@@ -360,6 +366,41 @@ class _Cross2DNARows:
             kv = K.gemm_nt(ctx_bf, W['kv'], out_bf16=True)                   # sketch keys / values: once per sequence
             self.kv = K.BF(kv.hi.reshape(batch, T, 2 * self.inner), None if kv.lo is None else kv.lo.reshape(batch, T, 2 * self.inner))
 
+    def _attend_bos(self, q):
+        """q BF [B, inner]: the <bos> queries -> o BF [B, inner]: all context tokens, no talking heads (np.py:826-849), glue arithmetic"""
+        B, inner, mod = self.B, self.inner, self.mod
+        hd, dh = mod.heads, mod.dim_head
+        q0 = ops._bf_val(q).reshape(B, hd, dh)
+        kvf = ops._bf_val(self.kv).reshape(B, -1, 2, hd, dh)
+        P0 = ops.XC2Inner._bos_scores(q0, kvf[:, :, 0], self.nk.float(), self.mask_u8.bool(), mod.scale)
+        o0 = P0[..., :1] * self.nv.float()[None] + torch.einsum('bht,bthd->bhd', P0[..., 1:], kvf[:, :, 1])
+        o = ops._to_bf(o0.reshape(B, inner).contiguous())
+        return o if self.lo else K.BF(o.hi, None)
+
+    def attend_rows(self, h, W, R):
+        """The rows form (cache prefill): h BF [B * R, D], the pre-normed operand rows 0 .. R-1 of every sample, sample-major -> o BF
+        [B * R, inner].  One to_q GEMM over all rows; rows b * R are the <bos> program of attend(bos=True), rows 1 .. R-1 of every sample
+        ONE call of amdnuwa_cross2dna_rows, each bit-identical to the single-row kernel at pos = r.  The window is read in place whatever
+        AMDNUWA_XC2_DECODE_PACKED says (self.kv exists on both routes).  On the text-masked guidance pass both outputs are constants:
+        nothing is launched."""
+        B, inner, mod = self.B, self.inner, self.mod
+        first = lambda t: None if t is None else t.reshape(B, R, inner)[:, 0]
+        if self.o_const is not None:
+            rep = lambda t: None if t is None else t[:, None].repeat(1, R, 1)      # (a copy also at R = 1: row 0 is overwritten below)
+            o = K.BF(rep(self.o_const.hi), rep(self.o_const.lo))
+            o.hi[:, 0] = self.o_bos.hi
+            if o.lo is not None:
+                o.lo[:, 0] = self.o_bos.lo if self.o_bos.lo is not None else 0
+            return K.BF(o.hi.reshape(B * R, inner), None if o.lo is None else o.lo.reshape(B * R, inner))
+        q = K.gemm_nt(h, W['q'], out_bf16=True)
+        o = K.cross2dna_rows(q, self.kv, self.slot_rows, R, mod.heads, mod.dim_head, self.nk, self.nv, self.wth, mask_u8=self.mask_u8,
+                             scale=mod.scale)
+        o0 = self._attend_bos(K.BF(first(q.hi).contiguous(), None if q.lo is None else first(q.lo).contiguous()))
+        first(o.hi).copy_(o0.hi)
+        if o.lo is not None:
+            first(o.lo).copy_(o0.lo)
+        return o
+
     def attend(self, h, W, pos_dev, bos):
         """h BF [B, D] (pre-normed operand row) -> o BF [B, inner]"""
         if self.o_const is not None:
@@ -368,12 +409,7 @@ class _Cross2DNARows:
         B, inner, mod = self.B, self.inner, self.mod
         hd, dh = mod.heads, mod.dim_head
         if bos:
-            q0 = ops._bf_val(q).reshape(B, hd, dh)
-            kvf = ops._bf_val(self.kv).reshape(B, -1, 2, hd, dh)
-            P0 = ops.XC2Inner._bos_scores(q0, kvf[:, :, 0], self.nk.float(), self.mask_u8.bool(), mod.scale)
-            o0 = P0[..., :1] * self.nv.float()[None] + torch.einsum('bht,bthd->bhd', P0[..., 1:], kvf[:, :, 1])
-            o = ops._to_bf(o0.reshape(B, inner).contiguous())
-            return o if self.lo else K.BF(o.hi, None)
+            return self._attend_bos(q)
         if not self.packed:
             return K.cross2dna_decode(q, self.kv, self.slot_rows, pos_dev, hd, dh, self.nk, self.nv, self.wth, mask_u8=self.mask_u8,
                                       scale=mod.scale)

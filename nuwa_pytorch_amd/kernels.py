@@ -1312,6 +1312,35 @@ def cross2dna_decode(q, kv, slot_rows, pos_dev, heads, dim_head, null_k, null_v,
     return o
 
 
+CROSS2DNA_ROWS_CHUNK = 2048      # query rows amdnuwa_cross2dna_rows takes per set of launches: its workspace is that of one chunk
+
+
+def cross2dna_rows(q, kv, slot_rows, R, heads, dim_head, null_k, null_v, wth, mask_u8=None, scale=None, out=None):
+    """the rows form of cross2dna_decode: q BF [B * R, inner] (unscaled, sample-major: row b * R + r is decoder row r of sample b); kv,
+    slot_rows, null_k / null_v, wth, mask_u8 as there.  Rows 1 .. R-1 of every sample attend in ONE call, row (b, r) bit-identical to
+    cross2dna_decode on q[b * R + r] at pos = r; rows b * R (<bos>) are neither read nor written -- they are the caller's.  Returns o BF
+    [B * R, inner] (`out`: written in place and returned)"""
+    L = _lib.lib()
+    _chk_dev(q.hi, kv.hi, slot_rows, null_k, null_v, wth, mask_u8)
+    BR, inner = q.hi.shape[0], heads * dim_head
+    B = kv.hi.shape[0]
+    assert R >= 1 and BR == B * R and q.hi.shape[1] == inner
+    assert kv.hi.dim() == 3 and kv.hi.is_contiguous() and kv.hi.shape[2] == 2 * inner
+    assert (q.lo is None) == (kv.lo is None) and (kv.lo is None or kv.lo.is_contiguous())
+    ctx_rows = kv.hi.shape[1]
+    assert slot_rows.dtype == torch.int32 and slot_rows.dim() == 2 and slot_rows.is_contiguous()
+    assert mask_u8 is None or (mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (B, ctx_rows) and mask_u8.is_contiguous())
+    n_pos, J = slot_rows.shape
+    o = empty_bf((BR, inner), q.hi.device, lo=q.lo is not None) if out is None else out
+    assert tuple(o.hi.shape) == (BR, inner) and o.hi.is_contiguous() and (o.lo is None) == (q.lo is None) and (o.lo is None or o.lo.is_contiguous())
+    nb = L.amdnuwa_cross2dna_rows_workspace_bytes(B, R, J, heads, dim_head)
+    ws = workspace(nb, q.hi.device)
+    check(L.amdnuwa_cross2dna_rows(B, R, J, heads, dim_head, dim_head ** -0.5 if scale is None else scale, _p(q.hi), _p(q.lo),
+                                   q.hi.stride(0), _p(kv.hi), _p(kv.lo), ctx_rows, _p(slot_rows), n_pos, _p(mask_u8), _p(null_k),
+                                   _p(null_v), _p(wth), _p(o.hi), _p(o.lo), inner, _p(ws), nb, _stream()), 'amdnuwa_cross2dna_rows')
+    return o
+
+
 def sample_next_row(logits, keep, temperature, u, emb, pos, pos_idx, step_dev, ids, x_next, allow_unsupported=False):
     """the sampling tail of one generate() token, in place: logits fp32 [B, C] (rows may be pitched); u fp32 [B, keep] uniforms, None exactly
     when keep == 1; emb fp32 [>= C, D]; pos fp32 [P, D]; pos_idx int32 [cap] and step_dev int32 [1] on the device; ids int64 [B, cap] and

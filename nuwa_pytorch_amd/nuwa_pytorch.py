@@ -1317,7 +1317,8 @@ class NUWASketch(nn.Module):
 
     generate_use_cache = True               # key/value-cached generate() (decode.py); False = the reference's recompute loop
     generate_use_graph = True               # replay each token's decoder work (rows >= 1) as one captured HIP graph
-    generate_slide_cache = False            # past max_video_frames the recompute loop: SparseCross2DNA rows have no cache prefill
+    generate_slide_cache = True             # num_frames > max_video_frames: cached rows + one cache prefill per slide of the frame window
+                                            # (SparseCross2DNA by amdnuwa_cross2dna_rows); False = the whole call on the recompute loop (A/B)
     generate_device_sampler = True          # cached path: sample + id write + next input row on the device, as NUWA.generate_device_sampler
     embed_video = NUWA.embed_video          # <bos> + positional + token embedding, one libamdnuwa node
     _final = NUWA._final                    # final StableLayerNorm + logits (+ cross entropy), fused
@@ -1349,7 +1350,9 @@ class NUWASketch(nn.Module):
         """np.py:2438-2511.  The reference recomputes the whole prefix per token (and, for guidance, feeds the normed conditioned
         output to a sketch-masked second pass).  Every decoder stage is row-causal or row-wise -- SparseCross2DNA looks at the sketch
         only -- so each token costs one new decoder row against per-layer caches (decode.GuidedStepper, as NUWA.generate) whenever the
-        sequence fits the video shape and every block has a single-row path; otherwise the recompute algorithm runs on the same kernels."""
+        sequence fits the video shape and every block has a single-row path; otherwise the recompute algorithm runs on the same kernels.
+        Past max_video_frames the reference slides its look-back window (np.py:2470-2474); as in NUWA.generate every slide is ONE cache
+        prefill (GuidedStepper.prefill; SparseCross2DNA by the rows form of its single-row kernel) and the new frame's tokens are row steps."""
         if sketch.ndim == 4:
             sketch = sketch[:, None]
         sketch_embeds, context_mask = self.embed_sketch(sketch, mask=sketch_mask)
