@@ -42,7 +42,8 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 *     _workspace_bytes, the single-query SparseCross2DNA over a window of any size, and amdnuwa_sample_next_row, the
                                                 *     sampling tail of a generate() token, and amdnuwa_vq_nearest_l2 with its _workspace_bytes, the Euclidean
                                                 *     code lookup of the tokenizer, and amdnuwa_cross2dna_rows with its _workspace_bytes, the rows form of
-                                                *     amdnuwa_cross2dna_decode for the cache prefill of NUWASketch.generate) */
+                                                *     amdnuwa_cross2dna_decode for the cache prefill of NUWASketch.generate, and amdnuwa_attn_rows with its _workspace_bytes,
+                                                *     the rows form of amdnuwa_attn_decode_rows for the cache prefill of a generate() over a long text context) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -637,6 +638,24 @@ int amdnuwa_attn_decode_rows(int B, int T, int heads, int dim_head, float scale,
                              const uint16_t* kv, const uint16_t* kv_lo, int cache_rows, const int* first_row, const uint8_t* key_mask,
                              const float* null_k, const float* null_v, const float* w_th, const float* th_bias, uint16_t* o,
                              uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
+/* The ROWS FORM of amdnuwa_attn_decode_rows (added at ABI 21, purely additive): decoder rows 0 .. R-1 of every sample in one call -- the
+ * cache prefill of a NUWA.generate / NUWAVideoAudio.generate whose frame window slides over a text context of more than 287 tokens.  q and o
+ * are [B * R, ld] bf16 hi (+ lo) rows, sample-major: row b * R + r is decoder row r of sample b.  All R rows of a sample attend the SAME
+ * window: the null key plus rows first_row[0] .. first_row[0] + T - 1 of that sample's kv [B][cache_rows][2 * inner]; key_mask [B][T] or
+ * NULL.  No row is special (text cross-attention treats <bos> like any other row): rows 0 .. R-1 are all read and written.  kv, first_row
+ * (DEVICE memory), null_k, null_v, w_th, th_bias and scale are those of amdnuwa_attn_decode_rows.  The kernels are the single row's, told by
+ * the launch which query a workgroup serves: the same loads, expression trees, 128-slot splits and meeting order, no atomics -- row (b, r)
+ * of o is BIT-IDENTICAL to amdnuwa_attn_decode_rows on q[b * R + r] alone, with and without the lo images, and two runs are bit-identical.
+ * A window that leaves [0, cache_rows) writes nothing.  Queries are indexed on the x dimension of the grid and taken in chunks of 2048
+ * (three launches per chunk on `stream`, which share the workspace), so B * R may exceed 65 535; it must fit an int.  Arguments are checked
+ * first (a null pointer, a non-positive B / R / T / heads / dim_head, cache_rows < T, lo images not given together, ld < heads * dim_head:
+ * AMDNUWA_ERR_ARG), then the envelope (heads 1..8, dim_head 32 / 64, otherwise AMDNUWA_ERR_UNSUPPORTED), then the workspace:
+ * >= _workspace_bytes = the single-row formula with min(B * R, 2048) -- one chunk -- in place of B, AMDNUWA_ERR_WORKSPACE otherwise. */
+size_t amdnuwa_attn_rows_workspace_bytes(int B, int R, int T, int heads, int dim_head);
+int amdnuwa_attn_rows(int B, int R, int T, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo, int ldq,
+                      const uint16_t* kv, const uint16_t* kv_lo, int cache_rows, const int* first_row, const uint8_t* key_mask,
+                      const float* null_k, const float* null_v, const float* w_th, const float* th_bias, uint16_t* o, uint16_t* o_lo, int ldo,
+                      void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
 /* SparseCross2DNA (np.py:761-901, rows after <bos>) for ONE query row per sample, its window read IN PLACE (added at ABI 21, purely
  * additive).  The query of decoder row pos[0] (DEVICE memory, >= 1: a captured launch serves every row) sits at feature-map position
  * i = (pos[0] - 1) mod n_pos.  Slot 0 is the learned null key, always visible; slot 1 + j is context row slot_rows[i][j] of the sample, read

@@ -123,6 +123,8 @@ SIGNATURES = {
     'amdnuwa_xattn_decode': (I, [XG, P, P, I, XK, P, P, P, I, P]),
     'amdnuwa_attn_decode_rows_workspace_bytes': (SZ, [I, I, I, I]),
     'amdnuwa_attn_decode_rows': (I, [I, I, I, I, F, P, P, I, P, P, I, P, P, P, P, P, P, P, P, I, P, SZ, P]),
+    'amdnuwa_attn_rows_workspace_bytes': (SZ, [I, I, I, I, I]),
+    'amdnuwa_attn_rows': (I, [I, I, I, I, I, F, P, P, I, P, P, I, P, P, P, P, P, P, P, P, I, P, SZ, P]),
     'amdnuwa_cross2dna_decode_workspace_bytes': (SZ, [I, I, I, I]),
     'amdnuwa_cross2dna_decode': (I, [I, I, I, I, F, P, P, I, P, P, I, P, I, P, P, P, P, P, P, P, I, P, SZ, P]),
     'amdnuwa_cross2dna_rows_workspace_bytes': (SZ, [I, I, I, I, I]),

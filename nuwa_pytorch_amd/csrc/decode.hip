@@ -428,11 +428,13 @@ __global__ __launch_bounds__(1024) void xattn_decode_kernel(XDecArgs a) {
 // and the key mask is indexed by context row.  Every workgroup reads the table row of i ONCE, keeps its own split's entries in LDS and
 // checks all of them against cache_rows on the way, so that all workgroups of the three launches agree on whether anything is written.
 //
-// TAB has a ROWS FORM (RowsArgs::R > 0, amdnuwa_cross2dna_rows): the launch serves query rows 1 .. R-1 of every sample at once (the cache
-// prefill of a sliding NUWASketch.generate window).  Only the bookkeeping differs -- which sample's context, which q / o row, which
-// workspace row and which decoder row a workgroup serves come from blockIdx.x (rows_who) instead of (blockIdx.y, the device-side position);
-// the loads, the expression trees, the 128-slot splits and the order in which partial results meet are the single row's own code, so row
-// (b, r) is bit-identical to the single-row launch on q[b * R + r] at pos = r.
+// Both mappings have a ROWS FORM (RowsArgs::R > 0): the launch serves R query rows of every sample at once, the cache prefill of a sliding
+// generate() window.  TAB (amdnuwa_cross2dna_rows, NUWASketch): rows 1 .. R-1, each at its own decoder row.  Contiguous window
+// (amdnuwa_attn_rows, text cross-attention over a long context): rows 0 .. R-1, all on the window at the device-side first row.  Only the
+// bookkeeping differs -- which sample's context, which q / o row, which workspace row and (TAB) which decoder row a workgroup serves come
+// from blockIdx.x (rows_who) instead of (blockIdx.y, the device-side position); the loads, the expression trees, the 128-slot splits and the
+// order in which partial results meet are the single row's own code, so row (b, r) is bit-identical to the single-row launch on q[b * R + r]
+// (TAB: at pos = r).
 constexpr int ROWS_SPLIT = 128;
 constexpr int ROWS_CHUNK = 2048;     // rows form: queries per set of three launches (bounds the workspace, not the result)
 constexpr float ROWS_NEG = -3.4028234663852886e38f;
@@ -449,8 +451,8 @@ struct RowsArgs {
     float scale;
     const int* tab;                  // TAB: [n_pos][T] cache row of every slot, < 0 = padding; `first` then holds the decoder row
     int n_pos;
-    int R, u0;                       // TAB rows form (R > 1; 0 = one row per sample): blockIdx.x counts (query, split) from query u0 on,
-};                                   // query u = sample u / (R-1), decoder row 1 + u % (R-1); `first` is not read
+    int R, u0;                       // rows form (R > 0; 0 = one row per sample): blockIdx.x counts (query, split) from query u0 on.  TAB: query u =
+};                                   // sample u / (R-1), decoder row 1 + u % (R-1), `first` is not read; window: sample u / R, q / o row u
 
 // what a workgroup serves: split sp of the query at row qr of q / o, which belongs to sample b (kv, mask) and keeps its scores, statistics
 // and partial rows in workspace row wr; pos = its decoder row in the rows form, -1 = read the device-side one
@@ -459,12 +461,18 @@ struct RowsWho { int sp, b, qr, wr, pos; };
 template <bool TAB>
 __device__ __forceinline__ RowsWho rows_who(const RowsArgs& a, bool reduce) {
     RowsWho w;
-    if (TAB && a.R > 0) {
+    if (a.R > 0) {
         const int ul = reduce ? (int)blockIdx.x : (int)blockIdx.x / a.nsplit, u = a.u0 + ul;
         w.sp = reduce ? 0 : (int)blockIdx.x - ul * a.nsplit;
-        w.b = u / (a.R - 1);
-        w.pos = 1 + u - w.b * (a.R - 1);
-        w.qr = w.b * a.R + w.pos;
+        if constexpr (TAB) {
+            w.b = u / (a.R - 1);
+            w.pos = 1 + u - w.b * (a.R - 1);
+            w.qr = w.b * a.R + w.pos;
+        } else {                     // every row of a sample attends the window at the device-side first row
+            w.b = u / a.R;
+            w.pos = -1;
+            w.qr = u;
+        }
         w.wr = ul;
     } else {
         w.sp = reduce ? 0 : (int)blockIdx.x;
@@ -849,6 +857,38 @@ extern "C" int amdnuwa_attn_decode_rows(int B, int T, int heads, int dim_head, f
     a.st = a.sc + (size_t)B * heads * (T + 1);
     a.part = a.st + (size_t)B * a.nsplit * heads * 2;
     rows_launch<false>(a, B, stream);
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+
+extern "C" size_t amdnuwa_attn_rows_workspace_bytes(int B, int R, int T, int heads, int dim_head) {
+    if (B <= 0 || R <= 0) return 0;
+    const long long rows = (long long)B * R;
+    return amdnuwa_attn_decode_rows_workspace_bytes((int)(rows < ROWS_CHUNK ? rows : ROWS_CHUNK), T, heads, dim_head);
+}
+
+extern "C" int amdnuwa_attn_rows(int B, int R, int T, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo, int ldq,
+                                 const uint16_t* kv, const uint16_t* kv_lo, int cache_rows, const int* first_row, const uint8_t* key_mask,
+                                 const float* null_k, const float* null_v, const float* w_th, const float* th_bias, uint16_t* o,
+                                 uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    if (!q || !kv || !first_row || !null_k || !null_v || !w_th || !o) return AMDNUWA_ERR_ARG;
+    if (B <= 0 || R <= 0 || T <= 0 || heads <= 0 || dim_head <= 0 || cache_rows < T) return AMDNUWA_ERR_ARG;
+    if ((long long)B * R > 0x7fffffffLL) return AMDNUWA_ERR_ARG;                  // (the q / o row index is an int)
+    if ((q_lo != nullptr) != (kv_lo != nullptr) || (q_lo != nullptr) != (o_lo != nullptr)) return AMDNUWA_ERR_ARG;
+    if ((long long)ldq < (long long)heads * dim_head || (long long)ldo < (long long)heads * dim_head) return AMDNUWA_ERR_ARG;
+    if (heads > 8 || (dim_head != 32 && dim_head != 64)) return AMDNUWA_ERR_UNSUPPORTED;
+    const int total = B * R, rows = total < ROWS_CHUNK ? total : ROWS_CHUNK;
+    RowsArgs a{};
+    const size_t nf = rows_ws_floats(rows, T, heads, dim_head, a.nsplit);
+    if (!workspace || workspace_bytes < nf * sizeof(float)) return AMDNUWA_ERR_WORKSPACE;
+    a.q = q; a.ql = q_lo; a.kv = kv; a.kvl = kv_lo; a.first = first_row; a.mask = key_mask; a.nk = null_k; a.nv = null_v;
+    a.wth = w_th; a.bias = th_bias; a.o = o; a.ol = o_lo; a.ldq = ldq; a.ldo = ldo; a.cache_rows = cache_rows; a.T = T;
+    a.heads = heads; a.dim_head = dim_head; a.scale = scale; a.R = R;
+    a.sc = static_cast<float*>(workspace);
+    a.st = a.sc + (size_t)rows * heads * (T + 1);
+    a.part = a.st + (size_t)rows * a.nsplit * heads * 2;
+    // chunks of at most ROWS_CHUNK queries share the workspace: the launches of a stream run in order
+    for (a.u0 = 0; a.u0 < total; a.u0 += ROWS_CHUNK) rows_launch<false>(a, total - a.u0 < ROWS_CHUNK ? total - a.u0 : ROWS_CHUNK, stream);
     LAUNCH_CHECK();
     return AMDNUWA_OK;
 }

@@ -5,7 +5,8 @@ the decoder is causal (Sparse3DNA taps, np.py:420-457; ShiftVideoTokens, np.py:2
 text, FeedForward, the norms), so row `pos` of the decoder depends only on rows <= pos.  IncrementalDecoder keeps, per layer,
   * the pre-norm outputs of the two token-shifted blocks (the shift reads the rows one grid row up / one token left),
   * the Sparse3DNA key / value rows,
-  * the packed text keys / values of the cross-attention (computed once),
+  * the packed text keys / values of the cross-attention (computed once) -- or, for a context of more than 287 tokens and
+    long_context=True, the to_kv rows themselves, attended in place (amdnuwa_attn_decode_rows; amdnuwa_attn_rows in the prefill),
 and computes ONE new row per call with the same libamdnuwa kernels the training path uses (GEMMs, LayerNorms, GEGLU, the
 cross-attention core with n = 1) plus the two single-row kernels of csrc/decode.hip.  The row index lives in device memory,
 so the per-token work of a whole guided step can be captured once in a HIP graph and replayed for every token.
@@ -38,7 +39,18 @@ class _Block:
     """one sub-block of a row program: out_slot <- out_slot + post(inner(pre(in_slot)));  pre / post = None for the un-normed modules
     of the reversible dual decoder's cross-modality layer"""
     __slots__ = ('kind', 'pre', 'post', 'inner', 'fmap', 'hcache', 'kvcache', 'geom', 'pk', 'xg', 'o_const', 'xm', 'src', 'dst',
-                 'store_before', 'store_after', 'c2', 'wth', 'rel')
+                 'store_before', 'store_after', 'c2', 'wth', 'rel', 'long', 'ctx_kv', 'first0', 'mask_u8', 'nk', 'nv')
+
+
+X_PACKED_MAX_KEYS = 287             # context keys (+ the null key = 288 slots) the packed key images of amdnuwa_xattn_decode hold
+
+
+def long_context_ok(mod, n_keys):
+    """Can a text cross-attention block `mod` (nuwa_pytorch.Attention) over a context of n_keys rows take the LONG form of the row program
+    (long_context=True: the to_kv rows attended in place)?  Geometry alone -- what amdnuwa_attn_decode_rows / amdnuwa_attn_rows take, for
+    contexts the packed images do not hold.  Unlike Attention._long_hip_ok it asks neither for a precision mode nor for a shape large
+    enough to be the faster TRAINING route (long_pairs_min, long_wgs_min): one query row per sample never is."""
+    return (not mod.causal) and n_keys is not None and n_keys > X_PACKED_MAX_KEYS and mod.heads <= 8 and mod.dim_head in (32, 64)
 
 
 def _cast_row(x, lo):
@@ -103,9 +115,15 @@ class IncrementalDecoder:
     (a SandwichNorm block, or a bare FeedForward / CrossModalityCrossAttention), optional `context` (text rows for a cross-attention), `xm`
     (_XmDirection this block attends through), `dst` (the residual half it adds into: reversible stacks keep two, np.py's reversible.py;
     the block reads the OTHER half), `store_before` / `store_after` (_XmDirection objects that take this row's input / output as context);
-    `combine` scales the sum of the two halves at the end (1 for the ReversibleTransformer, 0.5 for the reversible dual decoder)."""
+    `combine` scales the sum of the two halves at the end (1 for the ReversibleTransformer, 0.5 for the reversible dual decoder).
 
-    def __init__(self, transformer, batch, max_rows, context, context_mask, pos_dev, block_list=None, halves=1, combine=0.5):
+    long_context=True: a text cross-attention over more than 287 context keys (long_context_ok) becomes the long form of kind 'x' --
+    to_kv(context) kept as rows [B, T, 2 * inner] and attended in place, one query by amdnuwa_attn_decode_rows (window start: a device-side
+    zero, so the step stays capturable), R queries per sample by amdnuwa_attn_rows.  False (the default): such a context is refused and
+    generate() keeps the recompute loop.  Contexts of at most 287 keys take the packed images whatever the switch says."""
+
+    def __init__(self, transformer, batch, max_rows, context, context_mask, pos_dev, block_list=None, halves=1, combine=0.5, *,
+                 long_context=False):
         from .nuwa_pytorch import Attention, FeedForward, Sparse3DNA, SandwichNorm, SparseCross2DNA
         from .video_audio import SparseCausal2DNA
         dev = context.device
@@ -125,6 +143,7 @@ class IncrementalDecoder:
             mod, ctx_arg = spec['mod'], spec.get('context')
             blk = _Block()
             blk.kvcache = blk.geom = blk.pk = blk.xg = blk.o_const = blk.hcache = blk.fmap = blk.c2 = blk.wth = blk.rel = None
+            blk.long, blk.ctx_kv, blk.first0, blk.mask_u8, blk.nk, blk.nv = False, None, None, None, None, None
             blk.xm = spec.get('xm')
             blk.dst = spec.get('dst', 0)
             blk.src = (1 - blk.dst) if halves == 2 else 0
@@ -138,6 +157,11 @@ class IncrementalDecoder:
                     found = mod._inner(ctx_arg, seq_len=max_rows, batch=batch)
                     if found is None and isinstance(mod.fn, SparseCausal2DNA) and mod.fn._hip_ok():
                         found = (mod.fn, None)                         # audio tower built without the channel shift
+                    if found is None and long_context and ctx_arg is not None and isinstance(mod.fn, Attention) and \
+                            long_context_ok(mod.fn, ctx_arg.shape[1]):
+                        # _inner answers for the TRAINING route of a long context (speed thresholds, precision mode); a single row
+                        # asks for the geometry alone
+                        found = (mod.fn, None)
                     if found is None:
                         raise NotImplementedError('IncrementalDecoder: a decoder block is not on the libamdnuwa path')
                     inner, fmap = found
@@ -165,23 +189,38 @@ class IncrementalDecoder:
                 blk.rel = p[5].detach().contiguous() if len(p) > 5 else None
             elif isinstance(inner, Attention):
                 if inner.causal:
-                    # plain causal self-attention has no cached single-row path: generate() keeps the recompute loop for such stacks
+                    # plain causal self-attention has no cached single-row path (it would need a device-side key count and rotary embeddings
+                    # on top of amdnuwa_attn_decode_rows; no model's generate() builds such a stack): the recompute loop, whatever long_context says
                     raise NotImplementedError('IncrementalDecoder: no single-row path for plain (causal) self-attention')
-                if context.shape[1] + 1 > 288:
-                    # the single-query kernel (xattn_decode) reads packed key images of at most 288 keys; a longer context trains on the cattn
-                    # kernels, which have no cached single-row form: generate() keeps the recompute loop
+                T = context.shape[1]
+                blk.long = T > X_PACKED_MAX_KEYS
+                if blk.long and not (long_context and long_context_ok(inner, T)):
+                    # the packed key images of the single-query kernel (xattn_decode) hold at most 288 slots.  A longer context is attended in
+                    # place (the long form below) when the caller asks for it with long_context=True and the geometry is the rows kernels';
+                    # otherwise generate() keeps the recompute loop
                     raise NotImplementedError('IncrementalDecoder: no single-row path for cross-attention over more than 287 context keys')
                 blk.kind = 'x'
                 p = inner._params()
                 W = ops.XInner.weights(inner._cache, p)
-                blk.xg = K.x_geom(batch, 1, context.shape[1], inner.heads, inner.dim_head)
-                blk.wth = p[2].detach().reshape(inner.heads, inner.heads).contiguous()
+                hd, dh = inner.heads, inner.dim_head
+                blk.wth = p[2].detach().reshape(hd, hd).contiguous()
+                blk.nk, blk.nv = p[0].detach().reshape(hd, dh).contiguous(), p[1].detach().reshape(hd, dh).contiguous()
                 kv = K.gemm_nt(ctx_bf, W['kv'], out_bf16=True)                 # text keys / values: once per sequence
-                blk.pk = K.xattn_pack(blk.xg, kv, p[0].detach().reshape(inner.heads, inner.dim_head).contiguous(),
-                                      p[1].detach().reshape(inner.heads, inner.dim_head).contiguous(), mask_u8)
-                if all_masked:
-                    q0 = K.zeros_bf((batch, inner.heads * inner.dim_head), dev, lo=lo)
-                    blk.o_const = K.xattn_decode(blk.xg, q0, blk.pk, blk.wth)
+                q0 = K.zeros_bf((batch, hd * dh), dev, lo=lo) if all_masked else None
+                if blk.long:
+                    # the rows to_kv(context) leaves ARE the layout the rows kernels read: no pack.  The window is the whole context, its
+                    # first row a device-side zero -- the same buffers at every row, so the step replays from a captured graph
+                    blk.ctx_kv = K.BF(kv.hi.reshape(batch, T, 2 * hd * dh), None if kv.lo is None else kv.lo.reshape(batch, T, 2 * hd * dh))
+                    blk.first0 = torch.zeros(1, dtype=torch.int32, device=dev)
+                    blk.mask_u8 = mask_u8
+                    if all_masked:                                             # (mask_u8 is all zero here)
+                        blk.o_const = self._attend_long(blk, q0, None)
+                        blk.ctx_kv = None                                      # never read again: every later row is the constant
+                else:
+                    blk.xg = K.x_geom(batch, 1, T, hd, dh)
+                    blk.pk = K.xattn_pack(blk.xg, kv, blk.nk, blk.nv, mask_u8)
+                    if all_masked:
+                        blk.o_const = K.xattn_decode(blk.xg, q0, blk.pk, blk.wth)
             elif isinstance(inner, SparseCross2DNA):
                 blk.kind = 'xc2'
                 blk.c2 = _Cross2DNARows(inner, batch, ctx_bf, mask_u8, all_masked, lo)
@@ -191,6 +230,17 @@ class IncrementalDecoder:
                 raise NotImplementedError(f'IncrementalDecoder: no single-row path for {type(inner).__name__}')
             self.blocks.append(blk)
         self.bos_row_differs = any(b.kind == 'xc2' for b in self.blocks)       # row 0 takes another code path: not one graph for all rows
+
+    @staticmethod
+    def _attend_long(blk, q, R):
+        """the long form of an 'x' block: q BF [B, inner] (R None) or [B * R, inner] -> o alike; the context rows read in place"""
+        inner = blk.inner
+        T = blk.ctx_kv.hi.shape[1]
+        if R is None:
+            return K.attn_decode_rows(q, blk.ctx_kv, blk.first0, T, inner.heads, inner.dim_head, blk.nk, blk.nv, blk.wth,
+                                      mask_u8=blk.mask_u8, scale=inner.scale)
+        return K.attn_rows(q, blk.ctx_kv, blk.first0, T, R, inner.heads, inner.dim_head, blk.nk, blk.nv, blk.wth, mask_u8=blk.mask_u8,
+                           scale=inner.scale)
 
     def _norm(self, y, resid, post, nxt, R):
         """-> (x, h).  x = resid + post-norm(y) (post None: none, x = y) and, in the same launch, h = the operand rows of block `nxt`: its
@@ -210,8 +260,8 @@ class IncrementalDecoder:
     def _walk(self, x, R=None, bos=False):
         """The one loop over the blocks.  R None: x fp32 [B, D], the row at pos_dev of every sample, single-row kernels against the caches
         (step).  R: x [B * R, D], sample-major rows 0 .. R-1 (prefill).  The modes differ in _norm and in the attention core of 's3', 'x'
-        and 'xc2' (its rows program, _Cross2DNARows.attend_rows); only the single row has 'xm' blocks and store hooks (prefill refuses
-        them before it gets here)."""
+        (long form: the rows form of its single-row kernel) and 'xc2' (its rows program, _Cross2DNARows.attend_rows); only the single row
+        has 'xm' blocks and store hooks (prefill refuses them before it gets here)."""
         B, fast, blocks = self.B, ops._fast(), self.blocks
         state = [x] * self.halves
         h = self._enter(x, blocks[0], R)
@@ -245,7 +295,9 @@ class IncrementalDecoder:
                         o = K.BF(rep(o.hi), rep(o.lo))
                 else:
                     q = K.gemm_nt(h, W['q'], out_bf16=True)
-                    if R is None:
+                    if blk.long:                    # more than 287 context keys: the to_kv rows in place, one query or R per sample
+                        o = self._attend_long(blk, q, R)
+                    elif R is None:
                         o = K.xattn_decode(g, q, blk.pk, blk.wth)
                     else:
                         # blk.pk was packed with an n = 1 geometry: the key images depend on (B, T, heads, dim_head) alone, so R queries attend them
@@ -522,13 +574,13 @@ class DualIncrementalDecoder:
     ReversibleDualModalityDecoder (np.py:1489-1655 + reversible_video_audio.py) -- over two growing sequences: step('v' | 'a', x)
     takes the decoder input row of the next position of that stream and returns the row after all layers (before the final norm)."""
 
-    def __init__(self, dec, batch, rows_v, rows_a, context, context_mask):
+    def __init__(self, dec, batch, rows_v, rows_a, context, context_mask, *, long_context=False):
         dev, lo = context.device, K.want_lo()
         self.pos = {'v': torch.zeros(1, dtype=torch.int32, device=dev), 'a': torch.zeros(1, dtype=torch.int32, device=dev)}
         rows = {'v': rows_v, 'a': rows_a}
         lists, halves, combine = _row_program(dec, context, lambda mod, ctx_stream: _XmDirection(mod, batch, rows[ctx_stream], dev, lo))
         self.streams = {key: IncrementalDecoder(None, batch, rows[key], context, context_mask, self.pos[key], block_list=lists[key],
-                                                halves=halves, combine=combine) for key in 'va'}
+                                                halves=halves, combine=combine, long_context=long_context) for key in 'va'}
 
     def directions(self, which):
         """(_XmDirection objects this stream QUERIES through, those it STORES context rows for)"""
@@ -600,13 +652,13 @@ class DualGuidedStepper:
     logits for that stream's next token; with cond_scale != 1 the final-normed conditioned output row is the input of a second,
     text-masked pass (np.py:2176-2186) and the two logits are mixed."""
 
-    def __init__(self, model, text_embeds, text_mask, rows_v, rows_a, cond_scale, graph=True):
+    def __init__(self, model, text_embeds, text_mask, rows_v, rows_a, cond_scale, graph=True, *, long_context=False):
         self.m, self.cond_scale = model, cond_scale
         dec = model.video_audio_transformer
         B, D = text_embeds.shape[0], text_embeds.shape[-1]
-        self.cond = DualIncrementalDecoder(dec, B, rows_v, rows_a, text_embeds, text_mask)
-        self.uncond = DualIncrementalDecoder(dec, B, rows_v, rows_a, text_embeds, torch.zeros_like(text_mask).bool()) \
-            if cond_scale != 1 else None
+        self.cond = DualIncrementalDecoder(dec, B, rows_v, rows_a, text_embeds, text_mask, long_context=long_context)
+        self.uncond = DualIncrementalDecoder(dec, B, rows_v, rows_a, text_embeds, torch.zeros_like(text_mask).bool(),
+                                             long_context=long_context) if cond_scale != 1 else None
         # One captured HIP graph per stream for its ORDINARY rows (every row but a stream's start token and the first row of a frame,
         # where a cross-modality direction re-packs the other stream's frame on the host): static input / output buffers, positions
         # and context-row writes indexed on the device.
@@ -684,16 +736,17 @@ class GuidedStepper:
     caller then drives the whole call with advance(): per token one draw of the uniforms `u` (none when one logit is kept) and one replay.
     A shape the kernel does not take leaves device_sampler False and the caller on the torch tail."""
 
-    def __init__(self, nuwa, text_embeds, text_mask, max_rows, cond_scale, graph=True, sampler=None):
+    def __init__(self, nuwa, text_embeds, text_mask, max_rows, cond_scale, graph=True, sampler=None, *, long_context=False):
         dev = text_embeds.device
         B, D = text_embeds.shape[0], text_embeds.shape[-1]
         self.nuwa, self.cond_scale, self.max_rows = nuwa, cond_scale, max_rows
         self.pos_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         tr = nuwa.video_transformer
-        self.cond = IncrementalDecoder(tr, B, max_rows, text_embeds, text_mask, self.pos_dev)
+        self.cond = IncrementalDecoder(tr, B, max_rows, text_embeds, text_mask, self.pos_dev, long_context=long_context)
         self.uncond = None
         if cond_scale != 1:
-            self.uncond = IncrementalDecoder(tr, B, max_rows, text_embeds, torch.zeros_like(text_mask).bool(), self.pos_dev)
+            self.uncond = IncrementalDecoder(tr, B, max_rows, text_embeds, torch.zeros_like(text_mask).bool(), self.pos_dev,
+                                             long_context=long_context)
         self.x_in = torch.zeros(B, D, dtype=torch.float32, device=dev)
         self._captured = _CapturedStep('decode step', eager=not graph)
         self._calls = 0

@@ -1288,6 +1288,31 @@ def attn_decode_rows(q, kv, first_dev, T, heads, dim_head, null_k, null_v, wth, 
     return o
 
 
+ATTN_ROWS_CHUNK = 2048           # query rows amdnuwa_attn_rows takes per set of launches: its workspace is that of one chunk
+
+
+def attn_rows(q, kv, first_dev, T, R, heads, dim_head, null_k, null_v, wth, th_bias=None, mask_u8=None, scale=None, out=None):
+    """the rows form of attn_decode_rows: q BF [B * R, inner] (unscaled, sample-major: row b * R + r is decoder row r of sample b); kv,
+    first_dev, null_k / null_v, wth, th_bias, mask_u8 [B, T] as there.  All R rows of a sample attend the same window in ONE call, row
+    (b, r) bit-identical to attn_decode_rows on q[b * R + r] alone.  Returns o BF [B * R, inner] (`out`: written in place and returned)"""
+    L = _lib.lib()
+    _chk_dev(q.hi, kv.hi, first_dev, null_k, null_v, wth, th_bias, mask_u8)
+    BR, inner = q.hi.shape[0], heads * dim_head
+    B = kv.hi.shape[0]
+    assert R >= 1 and BR == B * R and q.hi.shape[1] == inner
+    assert kv.hi.dim() == 3 and kv.hi.is_contiguous() and kv.hi.shape[2] == 2 * inner
+    assert (q.lo is None) == (kv.lo is None) and (kv.lo is None or kv.lo.is_contiguous())
+    assert first_dev.dtype == torch.int32 and (mask_u8 is None or (mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (B, T) and mask_u8.is_contiguous()))
+    o = empty_bf((BR, inner), q.hi.device, lo=q.lo is not None) if out is None else out
+    assert tuple(o.hi.shape) == (BR, inner) and o.hi.is_contiguous() and (o.lo is None) == (q.lo is None) and (o.lo is None or o.lo.is_contiguous())
+    nb = L.amdnuwa_attn_rows_workspace_bytes(B, R, T, heads, dim_head)
+    ws = workspace(nb, q.hi.device)
+    check(L.amdnuwa_attn_rows(B, R, T, heads, dim_head, dim_head ** -0.5 if scale is None else scale, _p(q.hi), _p(q.lo), q.hi.stride(0),
+                              _p(kv.hi), _p(kv.lo), kv.hi.shape[1], _p(first_dev), _p(mask_u8), _p(null_k), _p(null_v), _p(wth),
+                              _p(th_bias), _p(o.hi), _p(o.lo), inner, _p(ws), nb, _stream()), 'amdnuwa_attn_rows')
+    return o
+
+
 def cross2dna_decode(q, kv, slot_rows, pos_dev, heads, dim_head, null_k, null_v, wth, mask_u8=None, scale=None):
     """single-query SparseCross2DNA over a window read in place: q BF [B, inner] (unscaled); kv BF [B, ctx_rows, 2 * inner] (k | v);
     slot_rows int32 [n_pos, J] on the device: the context row of every window slot of every feature-map position, -1 = padding; pos_dev

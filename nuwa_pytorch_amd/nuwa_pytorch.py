@@ -1118,6 +1118,8 @@ class NUWA(nn.Module):
     generate_use_graph = True        # replay each token's decoder work as one captured HIP graph
     generate_slide_cache = True      # num_frames > max_video_frames: keep the cached rows and prefill the caches at every slide of the
                                      # frame window; False = the whole call on the recompute loop (A/B switch)
+    generate_long_context_cache = False   # a text context of more than 287 tokens: True = cached decoding with the context rows attended in
+                                     # place (decode.IncrementalDecoder long_context); False = such a call runs the recompute loop
     generate_device_sampler = True   # cached path: the sample, the id write and the next input row by amdnuwa_sample_next_row at the end
                                      # of the (captured) row step; False = sample_top_fraction + cat + embedding as eager torch launches
 
@@ -1189,7 +1191,8 @@ class NUWA(nn.Module):
         ReversibleTransformer) is on the single-row kernels -- otherwise the reference's recompute algorithm runs on the same kernels.
         Past max_video_frames the reference slides a window over the last frames (np.py:1873-1881): every kept token moves one frame
         earlier, so at a slide the caches are rebuilt by ONE full-sequence pass over the rows the window already determines
-        (GuidedStepper.prefill) and the tokens of the new frame are single-row steps again."""
+        (GuidedStepper.prefill) and the tokens of the new frame are single-row steps again.  A text of more than 287 tokens is cached
+        only with generate_long_context_cache = True (its keys / values attended in place); by default such a call recomputes."""
         text_mask = text != 0
         text_embeds = self.embed_text(text, mask=text_mask)
         total = self.video_fmap_size ** 2 * default(num_frames, self.max_video_frames)
@@ -1213,8 +1216,10 @@ class NUWA(nn.Module):
             max_rows = total if total <= window else window + 1
             sampler = dict(total=total, tokens_per_frame=tpf, max_frames=max_frames, filter_thres=filter_thres,
                            temperature=temperature) if self.generate_device_sampler else None
+            # the switch off: the very call of before (NUWASketch shares this loop and has no text, hence no switch)
+            long_kw = dict(long_context=True) if getattr(self, 'generate_long_context_cache', False) else {}
             try:                                 # plain and reversible decoder alike; a block outside the single-row kernels -> recompute
-                stepper = GuidedStepper(self, context, context_mask, max_rows, cond_scale, graph=self.generate_use_graph, sampler=sampler)
+                stepper = GuidedStepper(self, context, context_mask, max_rows, cond_scale, graph=self.generate_use_graph, sampler=sampler, **long_kw)
             except NotImplementedError:
                 pass
         if stepper is None:

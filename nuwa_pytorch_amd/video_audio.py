@@ -532,6 +532,8 @@ class NUWAVideoAudio(nn.Module):
 
     generate_use_cache = True          # key/value-cached generate() (decode.DualGuidedStepper; plain and reversible dual decoder)
     generate_use_graph = True          # ... with the ordinary rows of each stream replayed from a captured HIP graph
+    generate_long_context_cache = False    # a text context of more than 287 tokens: True = cached decoding with the context rows attended in
+                                       # place (decode.IncrementalDecoder long_context); False = such a call runs the recompute loop
 
     def __init__(self, *, vae, dim, image_size, num_audio_tokens, num_audio_tokens_per_video_frame, audio_tokens_per_timestep=1,
                  max_video_frames=5, text_num_tokens=49408, text_max_seq_len=256, text_enc_depth=6, text_enc_dim_head=64,
@@ -630,9 +632,10 @@ class NUWAVideoAudio(nn.Module):
             try:
                 from .decode import DualGuidedStepper
                 stepper = DualGuidedStepper(self, text_embeds, text_mask, total_video_tokens + 1, total_audio_tokens + 1, cond_scale,
-                                            graph=self.generate_use_graph)
+                                            graph=self.generate_use_graph, **(dict(long_context=True) if self.generate_long_context_cache else {}))
             except NotImplementedError:
-                stepper = None                  # a block outside the single-row kernels: the recompute loop below
+                stepper = None                  # a block outside the single-row kernels (a text context of more than 287 tokens without
+                                                # generate_long_context_cache among them): the recompute loop below
             if stepper is not None:
                 return self._generate_cached(stepper, batch, total_video_tokens, total_audio_tokens, filter_thres, temperature,
                                              decode_max_batchsize)
