@@ -9,6 +9,7 @@ from .nuwa_pytorch import (NUWA, NUWASketch, NUWAVideoAudio, Sparse3DNA, CrossMo
 from .vqgan_vae import VQGanVAE
 from .kernels import set_precision, get_precision
 from .optimizer import get_optimizer
+from .ops import weights_changed
 
 __all__ = ['NUWA', 'NUWASketch', 'NUWAVideoAudio', 'Sparse3DNA', 'CrossModalityCrossAttention', 'VQGanVAE',
-           'set_precision', 'get_precision', 'get_optimizer']
+           'set_precision', 'get_precision', 'get_optimizer', 'weights_changed']

@@ -41,26 +41,45 @@ def _in_phase(name):
     return deco
 
 
-class WeightCache:
-    """bf16 (hi[/lo]) operand copies of fp32 master weights; rebuilt when a parameter changes
-    (optimizer step bumps `_version`) or the precision mode changes."""
+def _storage_key(p):
+    """what identifies the memory a tensor reads: (address of its first element, autograd version, identity of its storage).  Host-only."""
+    return (p.data_ptr(), p._version, p.untyped_storage()._cdata)
 
-    EPOCH = 0          # bumped by optimisers that update parameters behind autograd's back (FusedAdamW)
+
+class WeightCache:
+    """bf16 (hi[/lo]) operand copies of fp32 master weights; rebuilt when a parameter changes (an in-place write bumps `_version`, a new
+    storage has another identity), when weights_changed() says so, or when the precision mode changes.
+
+    An entry HOLDS the storages it was built from: while it lives neither their addresses nor their identities can be handed out again, so a
+    parameter that was given a new storage (`p.data = t`, `module.half().float()`, `.to(device)`) can never present the key of the old one
+    -- not even when the allocator would have returned the old block."""
+
+    EPOCH = 0          # bumped by weights_changed(): writes that neither autograd's version counter nor the storage identity shows
 
     def __init__(self):
         self._store = {}
 
     def get(self, key, params, builder):
-        ver = tuple((p.data_ptr(), p._version) for p in params) + (K.get_precision(), WeightCache.EPOCH, K._BWD_F16)
+        ver = tuple(_storage_key(p) for p in params) + (K.get_precision(), WeightCache.EPOCH, K._BWD_F16)
         ent = self._store.get(key)
         if ent is None or ent[0] != ver:
             with torch.no_grad():
-                ent = (ver, builder())
+                ent = (ver, builder(), tuple(p.untyped_storage() for p in params))
             self._store[key] = ent
         return ent[1]
 
     def clear(self):
         self._store.clear()
+
+
+def weights_changed():
+    """Tell the package that weights (or a context tensor) were written in a way torch cannot see: in place through `.data`, through a raw
+    pointer, by another library.  Everything derived from tensor CONTENTS is dropped and rebuilt on the next call: every WeightCache entry
+    (bf16 hi / lo casts, transposes, the interleaved FeedForward weight, fp16 copies and pairs), the fp16 range verdicts and the bf16 copy of
+    the context.  Writes torch sees (optimizer.step(), load_state_dict, `with torch.no_grad(): p.mul_(..)`, a new storage) need no call."""
+    WeightCache.EPOCH += 1
+    _F16_RANGE.clear()
+    _ctx_cast_reset()
 
 
 def _cast(w):
@@ -79,7 +98,8 @@ def _cast_t(w):
 # weights).  fp16 ends at 65504 -- a larger weight would become inf -- and loses significand bits below 6.1e-5, so a weight
 # tensor takes the fp16 form only while its largest magnitude lies in [F16_WMIN, F16_WMAX]; otherwise the block runs the bf16 hi + lo
 # (3-MFMA) products, which have fp32's range.  One device -> host transfer per call of f16_ranges_prefetch() covers every weight
-# whose (storage, version) has not been judged yet: Transformer.forward_layers calls it once per step for the whole stack.
+# whose memory (storage, address, version: _storage_key) has not been judged yet: Transformer.forward_layers calls it once per step for the
+# whole stack.
 # (Activations are covered in the kernels: every fp16 activation store saturates at +-65504, csrc/common.h pack2_f16_sat.)
 F16_WMAX = 6.0e4
 F16_WMIN = 2.0 ** -10
@@ -100,18 +120,15 @@ def f16_ranges_prefetch(ws):
     ws = list(ws) + _F16_ALSO
     del _F16_ALSO[:]
     for w in ws:
-        k = (w.data_ptr(), w._version)
-        if not _f16_known(w) and k not in seen and w.is_cuda:
-            seen.add(k)
+        if _f16_known(w) is None and id(w) not in seen and w.is_cuda:
+            seen.add(id(w))
             todo.append(w)
     if not todo:
         return
-    if len(_F16_RANGE) > 8192:
-        _F16_RANGE.clear()
     with torch.no_grad():
         am = torch.stack(torch._foreach_norm([w.detach() for w in todo], float('inf'))).cpu().tolist()     # ONE synchronisation
     for w, a in zip(todo, am):
-        _F16_RANGE[(w.data_ptr(), w._version)] = (weakref.ref(w), bool(F16_WMIN <= a <= F16_WMAX))       # (NaN compares false)
+        _f16_record(w, bool(F16_WMIN <= a <= F16_WMAX))       # (NaN compares false)
     # the stream is drained at this point anyway (once per optimiser step): look at the fp16 saturation monitor of the step before
     nsat = K.f16_sat_count(reset=True)
     if nsat:
@@ -120,11 +137,26 @@ def f16_ranges_prefetch(ws):
                       RuntimeWarning, stacklevel=3)
 
 
+def _f16_drop(ref, slot):
+    """the judged tensor died: release its verdict (and the storage it holds)"""
+    ent = _F16_RANGE.get(slot)
+    if ent is not None and ent[0] is ref:
+        del _F16_RANGE[slot]
+
+
+def _f16_record(w, ok):
+    """ONE verdict per tensor object (slot id(w), released when the object dies): the object by weak reference, the key of the memory it was
+    judged on, that storage itself -- held, so that neither its address nor its identity can come back under a new storage while the
+    verdict stands (see WeightCache) -- and the verdict.  Judging the object again replaces the entry and lets the old storage go."""
+    slot = id(w)
+    _F16_RANGE[slot] = (weakref.ref(w, lambda ref, slot=slot: _f16_drop(ref, slot)), _storage_key(w), w.untyped_storage(), ok)
+
+
 def _f16_known(w):
-    """the verdict recorded for THIS tensor object at this version, or None: a verdict is tied to the tensor by a weak reference, so a new
-    weight allocated at a freed weight's address (same data_ptr, same version counter) does not inherit a stale one"""
-    ent = _F16_RANGE.get((w.data_ptr(), w._version))
-    return ent[1] if ent is not None and ent[0]() is w else None
+    """the verdict recorded for THIS tensor object on the memory it reads now, or None: a verdict is tied to the object by a weak reference
+    (a new tensor at a dead one's id does not inherit it) and to the storage, the address and the version it was judged on"""
+    ent = _F16_RANGE.get(id(w))
+    return ent[3] if ent is not None and ent[0]() is w and ent[1] == _storage_key(w) else None
 
 
 def f16_weights_ok(*ws):
@@ -849,30 +881,35 @@ def _ctx_rows(meta):
     return K.cattn_keys(meta['cgeom']) if meta['kind'] == 'cattn' else meta['xgeom'].T
 
 
-_CTX_CAST = [None, -1, None]      # (weak reference to the context tensor, its version, its BF copy)
+_CTX_CAST = [None, -1, None, None]      # (weak reference to the context tensor, the key of its memory, its BF copy, its storage -- held, see WeightCache)
+
+
+def _ctx_cast_reset():
+    _CTX_CAST[:] = [None, -1, None, None]
 
 
 def _ctx_cast_drop(ref):
     """the context tensor died: release its copy"""
     if _CTX_CAST[0] is ref:
-        _CTX_CAST[0], _CTX_CAST[1], _CTX_CAST[2] = None, -1, None
+        _ctx_cast_reset()
 
 
 def _ctx_to_bf(context):
     """context fp32 [B, T, D] -> BF [B*T, D].  Every cross-attention block of a stack receives the SAME context tensor: its cast (27 us at
-    cfg 3, b = 128) runs once per tensor object and version, not once per layer (the copy is read-only: kv projection, its weight gradient).
-    The copy is hi-only or hi + lo as the precision mode wants: a copy cast in another mode is not reused."""
+    cfg 3, b = 128) runs once per tensor object, storage and version, not once per layer (the copy is read-only: kv projection, its weight
+    gradient).  The copy is hi-only or hi + lo as the precision mode wants: a copy cast in another mode is not reused.  weights_changed()
+    drops it."""
     ref = _CTX_CAST[0]
     lo = K.want_lo()
-    if ref is not None and ref() is context and _CTX_CAST[1] == context._version and (_CTX_CAST[2].lo is not None) == lo:
+    if ref is not None and ref() is context and _CTX_CAST[1] == _storage_key(context) and (_CTX_CAST[2].lo is not None) == lo:
         return _CTX_CAST[2]
     B, T, D = context.shape
     out = K.empty_bf((B * T, D), context.device, lo=lo)
     K.cast_pad(context.detach().reshape(B * T, D), out)
     try:
-        _CTX_CAST[0], _CTX_CAST[1], _CTX_CAST[2] = weakref.ref(context, _ctx_cast_drop), context._version, out
+        _CTX_CAST[:] = [weakref.ref(context, _ctx_cast_drop), _storage_key(context), out, context.untyped_storage()]
     except TypeError:
-        _CTX_CAST[0], _CTX_CAST[1], _CTX_CAST[2] = None, -1, None
+        _ctx_cast_reset()
     return out
 
 

@@ -170,7 +170,7 @@ class FusedAdamW(torch.optim.Optimizer):
             clip = self._norm.data_ptr() + 4
         _lib.check(L.amdnuwa_adamw_step(self._table.data_ptr(), self.nchunks, lr, b1, b2, eps, clip, st), 'amdnuwa_adamw_step')
         torch.autograd.graph.increment_version([p for p in self.params if p.grad is not None])   # written behind autograd's back
-        ops.WeightCache.EPOCH += 1               # the bf16 operand copies of the weights are stale now
+        ops.weights_changed()                    # the operand copies of the weights and their fp16 range verdicts are stale now
         return loss
 
     def zero_grad(self, set_to_none=True):

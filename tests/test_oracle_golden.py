@@ -82,12 +82,14 @@ def test_g4_norms_shift():
     torch.testing.assert_close(x2.grad, R['dx2'], **TOL)
 
 
+NUWA_CFG = dict(video_shape=(3, 4, 4), kernel_size=3, dilations=(1, 2), heads=2, depth=3, shift=True, text_depth=2, text_heads=2)
+
+
 @pytest.mark.parametrize('name', ['g5_nuwa_tiny', 'g6_nuwa_tiny_reversible'])
 def test_g5_g6_nuwa(name):
     A, P, G = load(name)
     P = req(P)
-    cfg = dict(video_shape=(3, 4, 4), kernel_size=3, dilations=(1, 2), heads=2, depth=3, shift=True,
-               reversible=bool(A['reversible']), text_depth=2, text_heads=2)
+    cfg = dict(NUWA_CFG, reversible=bool(A['reversible']))
     ctx, mask = O.text_encoder(A['text'], P, cfg)
     torch.testing.assert_close(ctx, A['text_embeds'], **TOL)
     loss, logits = O.decoder_loss(P, cfg, A['video_ids'].reshape(2, -1), ctx, mask, return_logits=True)
