@@ -8,8 +8,10 @@
 // The position is read from DEVICE memory so that one captured HIP graph serves every token of the sequence.
 // Past max_video_frames generate() slides its frame window (np.py:1873-1881): every kept token moves one frame earlier and every cached row
 // changes.  The caches are then rebuilt by one full-sequence pass whose norms / shift / cache writes are the ROWS forms of the kernels above:
-//   * prefill_ln_kernel + prefill_shift_kernel : decode_ln_kernel for rows 0 .. R-1 of every sample at once, bit-identical to it
+//   * prefill_ln_kernel + prefill_shift_kernel : decode_ln_kernel for rows 0 .. R-1 of every sample at once.  Both norms are ONE body
+//                                                (ln_body), so a row is bit-identical to the single-row step
 //   * prefill_kv_kernel                        : the k | v columns of R projected rows into the 3DNA cache
+// The token-shift rule is stated once (ShiftRule) for decode_shift_kernel, the single-row norm and prefill_shift_kernel.
 #include "common.h"
 #include "../../include/amdnuwa.h"
 
@@ -23,6 +25,25 @@ __device__ __forceinline__ void st_hl(bf16_t* hi, bf16_t* lo, size_t i, float v)
     else hi[i] = f2bf(v);
 }
 
+// ---- the token-shift rule, stated once ---------------------------------------------------------------------------------------
+// Channel e of row i of a sample (row 0 is <bos>) takes the same channel of row i - back(e):  back > 0: that many rows back;
+// back == 0: zeros;  back < 0: not shifted, the row keeps its own value.  Only the first two channel quarters are ever shifted.
+//   fmap > 0  ShiftVideoTokens (np.py:210-253): first quarter <- the token one grid row up (i - fmap), second quarter <- the token to
+//             the left (i - 1), zero at the frame border; <bos> is not shifted
+//   fmap < 0  ShiftAudioTokens (np.py:157-183): first half <- row i - 1, <bos> included; zeros for row 0
+// The row's part (two divisions) is the constructor's, so that a loop over channels pays for it once.
+struct ShiftRule {
+    int qd, up, left;
+    __device__ __forceinline__ ShiftRule(int i, int D, int fmap) : qd(D >> 2), up(-1), left(-1) {
+        if (fmap > 0) {
+            if (i > 0) { const int p = i - 1, wq = p % fmap, yq = (p / fmap) % fmap; up = yq > 0 ? fmap : 0; left = wq > 0 ? 1 : 0; }
+        } else {
+            up = left = i > 0 ? 1 : 0;
+        }
+    }
+    __device__ __forceinline__ int back(int e) const { return e < qd ? up : e < 2 * qd ? left : -1; }
+};
+
 // h_new [B, D] (row `pos` of every sample) -> cache[b][pos] and out[b] = shift(h)[pos]
 __global__ __launch_bounds__(256) void decode_shift_kernel(const bf16_t* __restrict__ h_hi, const bf16_t* __restrict__ h_lo,
                                                            bf16_t* __restrict__ c_hi, bf16_t* __restrict__ c_lo,
@@ -31,21 +52,17 @@ __global__ __launch_bounds__(256) void decode_shift_kernel(const bf16_t* __restr
     const int b = blockIdx.x, pos = pos_p[0];
     if (pos < 0 || pos >= cache_rows) return;
     const size_t crow = ((size_t)b * cache_rows + pos) * D, nrow = (size_t)b * D;
-    int yq = 0, wq = 0;
-    if (pos > 0) { const int p = pos - 1; wq = p % fmap; yq = (p / fmap) % fmap; }
-    const int qd = D >> 2;
+    const ShiftRule rule(pos, D, fmap);
     for (int c = threadIdx.x; c < D; c += blockDim.x) {
         const bf16_t hv = h_hi[nrow + c], lv = h_lo ? h_lo[nrow + c] : (bf16_t)0;
         c_hi[crow + c] = hv;
         if (c_lo) c_lo[crow + c] = lv;
         bf16_t oh = hv, ol = lv;
-        if (pos > 0 && c < 2 * qd) {
-            // first quarter <- the token one grid row up, second quarter <- the token to the left; zero at the frame border
-            const bool up = c < qd;
-            const bool has = up ? (yq > 0) : (wq > 0);
-            const size_t srow = crow - (size_t)(up ? fmap : 1) * D;
-            oh = has ? c_hi[srow + c] : (bf16_t)0;
-            ol = (has && c_lo) ? c_lo[srow + c] : (bf16_t)0;
+        const int back = rule.back(c);
+        if (back >= 0) {
+            const size_t srow = crow - (size_t)back * D;
+            oh = back ? c_hi[srow + c] : (bf16_t)0;
+            ol = (back && c_lo) ? c_lo[srow + c] : (bf16_t)0;
         }
         o_hi[nrow + c] = oh;
         if (o_lo) o_lo[nrow + c] = ol;
@@ -57,7 +74,12 @@ __global__ __launch_bounds__(256) void decode_shift_kernel(const bf16_t* __restr
 //                                                    then x_new = y, the fp32 decoder input row)
 //   h     = LN(x_new; next_w, next_b)               (pre-norm of the next block)
 //   cache[b][pos] = h ; out = shift(h)[pos]         (when the next block is token-shifted: cache != NULL)
-// One workgroup per sample; D <= 4096.
+// One workgroup (256 threads) per row; D <= 4096.  ln_body is the one body of both forms:
+//   ROWS = false (decode_ln_kernel)  : row blockIdx.x is sample blockIdx.x at the device-side position pos_p[0]; the shifted channels of out
+//                                      are gathered from the cache in the same launch (earlier rows: earlier launches)
+//   ROWS = true  (prefill_ln_kernel) : row blockIdx.x is row blockIdx.x % R of sample blockIdx.x / R; h goes to the cache row AND to out
+//                                      un-shifted -- the shifted channels are other rows' h, which other workgroups of this launch write;
+//                                      prefill_shift_kernel gathers them in a second, stream-ordered launch
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
     const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -69,14 +91,12 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
-template <bool YBF>
-__global__ __launch_bounds__(256) void decode_ln_kernel(const void* __restrict__ y_, const float* __restrict__ resid,
-                                                        const float* __restrict__ w, const float* __restrict__ b,
-                                                        const float* __restrict__ w2, const float* __restrict__ b2,
-                                                        float* __restrict__ x_new, bf16_t* __restrict__ c_hi,
-                                                        bf16_t* __restrict__ c_lo, bf16_t* __restrict__ o_hi,
-                                                        bf16_t* __restrict__ o_lo, const int* __restrict__ pos_p, int cache_rows,
-                                                        int D, int fmap, float eps) {
+template <bool YBF, bool ROWS>
+__device__ __forceinline__ void ln_body(const void* __restrict__ y_, const float* __restrict__ resid, const float* __restrict__ w,
+                                        const float* __restrict__ b, const float* __restrict__ w2, const float* __restrict__ b2,
+                                        float* __restrict__ x_new, bf16_t* __restrict__ c_hi, bf16_t* __restrict__ c_lo,
+                                        bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo, const int* __restrict__ pos_p, int R,
+                                        int cache_rows, int D, int fmap, float eps) {
     __shared__ float red[8];
     constexpr int MAXI = 4;                         // 4 x 256 threads x 4 elements = 4096
     const int bidx = blockIdx.x, tid = threadIdx.x;
@@ -135,14 +155,16 @@ __global__ __launch_bounds__(256) void decode_ln_kernel(const void* __restrict__
         }
     }
     const float rstd2 = rsqrtf(block_sum(q2, red) / D + eps);
-    int pos = 0, yq = 0, wq = 0;
-    if (c_hi) {
+    int smp = bidx, pos = 0;                         // the cache row: (sample, row of the sample)
+    if constexpr (ROWS) {
+        smp = bidx / R;
+        pos = bidx % R;
+    } else if (c_hi) {
         pos = pos_p[0];
         if (pos < 0 || pos >= cache_rows) return;
-        if (pos > 0 && fmap > 0) { const int p = pos - 1; wq = p % fmap; yq = (p / fmap) % fmap; }
     }
-    const size_t crow = ((size_t)bidx * cache_rows + pos) * D;
-    const int qd = D >> 2;
+    const ShiftRule rule(pos, D, fmap);              // (read by the single-row form alone)
+    const size_t crow = ((size_t)smp * cache_rows + pos) * D;
 #pragma unroll
     for (int it = 0; it < MAXI; ++it) {
         const int e = (tid + it * 256) * 4;
@@ -160,20 +182,36 @@ __global__ __launch_bounds__(256) void decode_ln_kernel(const void* __restrict__
         if (c_hi) {
             *reinterpret_cast<uint2*>(c_hi + crow + e) = oh;
             if (c_lo) *reinterpret_cast<uint2*>(c_lo + crow + e) = ol;
-            if (fmap > 0 && pos > 0 && e < 2 * qd) {  // D % 16 == 0: a 4-element group never straddles a quarter
-                const bool up = e < qd, has = up ? (yq > 0) : (wq > 0);
-                const size_t srow = crow - (size_t)(up ? fmap : 1) * D;
-                oh = has ? *reinterpret_cast<const uint2*>(c_hi + srow + e) : make_uint2(0u, 0u);
-                ol = (has && c_lo) ? *reinterpret_cast<const uint2*>(c_lo + srow + e) : make_uint2(0u, 0u);
-            } else if (fmap < 0 && e < 2 * qd) {      // ShiftAudioTokens (np.py:157-183): the first half of the channels comes from
-                const size_t srow = crow - (size_t)D; //  the previous row, <bos> included; zeros for row 0
-                oh = pos > 0 ? *reinterpret_cast<const uint2*>(c_hi + srow + e) : make_uint2(0u, 0u);
-                ol = (pos > 0 && c_lo) ? *reinterpret_cast<const uint2*>(c_lo + srow + e) : make_uint2(0u, 0u);
+            if constexpr (!ROWS) {
+                const int back = rule.back(e);       // D % 16 == 0: a 4-element group never straddles a quarter
+                if (back >= 0) {
+                    const size_t srow = crow - (size_t)back * D;
+                    oh = back ? *reinterpret_cast<const uint2*>(c_hi + srow + e) : make_uint2(0u, 0u);
+                    ol = (back && c_lo) ? *reinterpret_cast<const uint2*>(c_lo + srow + e) : make_uint2(0u, 0u);
+                }
             }
         }
         *reinterpret_cast<uint2*>(o_hi + row + e) = oh;
         if (o_lo) *reinterpret_cast<uint2*>(o_lo + row + e) = ol;
     }
+}
+
+template <bool YBF>
+__global__ __launch_bounds__(256) void decode_ln_kernel(const void* __restrict__ y_, const float* __restrict__ resid, const float* __restrict__ w,
+                                                        const float* __restrict__ b, const float* __restrict__ w2, const float* __restrict__ b2,
+                                                        float* __restrict__ x_new, bf16_t* __restrict__ c_hi, bf16_t* __restrict__ c_lo,
+                                                        bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo, const int* __restrict__ pos_p,
+                                                        int cache_rows, int D, int fmap, float eps) {
+    ln_body<YBF, false>(y_, resid, w, b, w2, b2, x_new, c_hi, c_lo, o_hi, o_lo, pos_p, 0, cache_rows, D, fmap, eps);
+}
+
+// the rows form: R rows per sample in one launch (its shifted channels: prefill_shift_kernel, below)
+template <bool YBF>
+__global__ __launch_bounds__(256) void prefill_ln_kernel(const void* __restrict__ y_, const float* __restrict__ resid, const float* __restrict__ w,
+                                                         const float* __restrict__ b, const float* __restrict__ w2, const float* __restrict__ b2,
+                                                         float* __restrict__ x_new, bf16_t* __restrict__ c_hi, bf16_t* __restrict__ c_lo,
+                                                         bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo, int R, int cache_rows, int D, float eps) {
+    ln_body<YBF, true>(y_, resid, w, b, w2, b2, x_new, c_hi, c_lo, o_hi, o_lo, nullptr, R, cache_rows, D, 0, eps);
 }
 
 // ---- single-query attention pieces shared by the 3DNA and the text cross-attention decode kernels -------------------------
@@ -668,103 +706,12 @@ __global__ __launch_bounds__(256) void rows_reduce_kernel(RowsArgs a) {
 // When generate() slides its frame window every kept token moves one frame earlier, so every cached row changes.  The kept rows are
 // recomputed in ONE full-sequence pass; these kernels leave the caches exactly as R single-row steps at pos = 0 .. R-1 would have.
 //
-// prefill_ln_kernel is decode_ln_kernel for row (sample, i) = (blockIdx.x / R, blockIdx.x % R): the same loads, the same expression
-// trees and the same block reduction, so every value is bit-identical to the row step's.  It writes h to the cache row AND to out
-// un-shifted; the shifted channel quarters of out are other rows' h, which other workgroups of this launch write -- they are gathered
-// by prefill_shift_kernel in a second, stream-ordered launch.
-template <bool YBF>
-__global__ __launch_bounds__(256) void prefill_ln_kernel(const void* __restrict__ y_, const float* __restrict__ resid,
-                                                         const float* __restrict__ w, const float* __restrict__ b,
-                                                         const float* __restrict__ w2, const float* __restrict__ b2,
-                                                         float* __restrict__ x_new, bf16_t* __restrict__ c_hi,
-                                                         bf16_t* __restrict__ c_lo, bf16_t* __restrict__ o_hi,
-                                                         bf16_t* __restrict__ o_lo, int R, int cache_rows, int D, float eps) {
-    __shared__ float red[8];
-    constexpr int MAXI = 4;                         // 4 x 256 threads x 4 elements = 4096
-    const int bidx = blockIdx.x, tid = threadIdx.x;
-    const size_t row = (size_t)bidx * D;
-    float4 v[MAXI];
-    float s = 0.f;
-#pragma unroll
-    for (int it = 0; it < MAXI; ++it) {
-        const int e = (tid + it * 256) * 4;
-        v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (e < D) {
-            if (YBF) {
-                const uint2 u = *reinterpret_cast<const uint2*>((const bf16_t*)y_ + row + e);
-                v[it] = make_float4(lo_f(u.x), hi_f(u.x), lo_f(u.y), hi_f(u.y));
-            } else {
-                v[it] = *reinterpret_cast<const float4*>((const float*)y_ + row + e);
-            }
-            s += (v[it].x + v[it].y) + (v[it].z + v[it].w);
-        }
-    }
-    if (resid) {
-        const float mean = block_sum(s, red) / D;
-        float q = 0.f;
-#pragma unroll
-        for (int it = 0; it < MAXI; ++it) {
-            const int e = (tid + it * 256) * 4;
-            if (e < D) {
-                const float a = v[it].x - mean, b_ = v[it].y - mean, c = v[it].z - mean, d = v[it].w - mean;
-                q += (a * a + b_ * b_) + (c * c + d * d);
-            }
-        }
-        const float rstd = rsqrtf(block_sum(q, red) / D + eps);
-        s = 0.f;
-#pragma unroll
-        for (int it = 0; it < MAXI; ++it) {
-            const int e = (tid + it * 256) * 4;
-            if (e < D) {
-                const float4 wv = *reinterpret_cast<const float4*>(w + e), bv = *reinterpret_cast<const float4*>(b + e);
-                const float4 rv = *reinterpret_cast<const float4*>(resid + row + e);
-                v[it] = make_float4(rv.x + ((v[it].x - mean) * rstd * wv.x + bv.x), rv.y + ((v[it].y - mean) * rstd * wv.y + bv.y),
-                                    rv.z + ((v[it].z - mean) * rstd * wv.z + bv.z), rv.w + ((v[it].w - mean) * rstd * wv.w + bv.w));
-                *reinterpret_cast<float4*>(x_new + row + e) = v[it];
-                s += (v[it].x + v[it].y) + (v[it].z + v[it].w);
-            }
-        }
-    }
-    if (!w2) return;                                 // last block of the stack: no next pre-norm
-    const float mean2 = block_sum(s, red) / D;
-    float q2 = 0.f;
-#pragma unroll
-    for (int it = 0; it < MAXI; ++it) {
-        const int e = (tid + it * 256) * 4;
-        if (e < D) {
-            const float a = v[it].x - mean2, b_ = v[it].y - mean2, c = v[it].z - mean2, d = v[it].w - mean2;
-            q2 += (a * a + b_ * b_) + (c * c + d * d);
-        }
-    }
-    const float rstd2 = rsqrtf(block_sum(q2, red) / D + eps);
-    const size_t crow = ((size_t)(bidx / R) * cache_rows + bidx % R) * D;
-#pragma unroll
-    for (int it = 0; it < MAXI; ++it) {
-        const int e = (tid + it * 256) * 4;
-        if (e >= D) continue;
-        const float4 wv = *reinterpret_cast<const float4*>(w2 + e), bv = *reinterpret_cast<const float4*>(b2 + e);
-        const float h[4] = {(v[it].x - mean2) * rstd2 * wv.x + bv.x, (v[it].y - mean2) * rstd2 * wv.y + bv.y,
-                            (v[it].z - mean2) * rstd2 * wv.z + bv.z, (v[it].w - mean2) * rstd2 * wv.w + bv.w};
-        bf16_t hh[4], hl[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (o_lo) f2bf_hilo(h[i], hh[i], hl[i]);
-            else { hh[i] = f2bf(h[i]); hl[i] = 0; }
-        }
-        const uint2 oh = make_uint2(pack2(hh[0], hh[1]), pack2(hh[2], hh[3])), ol = make_uint2(pack2(hl[0], hl[1]), pack2(hl[2], hl[3]));
-        if (c_hi) {
-            *reinterpret_cast<uint2*>(c_hi + crow + e) = oh;
-            if (c_lo) *reinterpret_cast<uint2*>(c_lo + crow + e) = ol;
-        }
-        *reinterpret_cast<uint2*>(o_hi + row + e) = oh;
-        if (o_lo) *reinterpret_cast<uint2*>(o_lo + row + e) = ol;
-    }
-}
-
-// the shifted half of out [B*R, D] from the cache rows a finished prefill_ln launch wrote: one thread per vector V (16 bytes, or 8 when
-// a channel quarter is no multiple of 8 elements) of the first D / 2 channels of a row, consecutive threads on consecutive vectors.
-//   fmap > 0  ShiftVideoTokens: first quarter <- row i - fmap, second quarter <- row i - 1, zero at the frame border; row 0 keeps h
-//   fmap < 0  ShiftAudioTokens: first half <- row i - 1, zeros for row 0
+// The norms are prefill_ln_kernel, the ROWS form of ln_body above: a row is bit-identical to the row step's because it runs the row
+// step's own code.
+//
+// prefill_shift_kernel: the shifted half of out [B*R, D] from the cache rows a finished prefill_ln launch wrote (ShiftRule says from which):
+// one thread per vector V (16 bytes, or 8 when a channel quarter is no multiple of 8 elements) of the first D / 2 channels of a row,
+// consecutive threads on consecutive vectors.
 template <typename V> __device__ __forceinline__ V vec_zero();
 template <> __device__ __forceinline__ uint4 vec_zero<uint4>() { return make_uint4(0u, 0u, 0u, 0u); }
 template <> __device__ __forceinline__ uint2 vec_zero<uint2>() { return make_uint2(0u, 0u); }
@@ -774,20 +721,14 @@ __global__ __launch_bounds__(256) void prefill_shift_kernel(const bf16_t* __rest
                                                             bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo, int B, int R,
                                                             int cache_rows, int D, int fmap) {
     constexpr int EV = sizeof(V) / sizeof(bf16_t);
-    const int per_row = (D >> 1) / EV, qd = D >> 2;
+    const int per_row = (D >> 1) / EV;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)B * R * per_row) return;
     const int e = (int)(idx % per_row) * EV;
     const size_t r = idx / per_row;
     const int i = (int)(r % R), smp = (int)(r / R);
-    int back;                                        // rows back to the source row; 0 = zeros
-    if (fmap > 0) {
-        if (i == 0) return;                          // <bos> is not shifted
-        const int p = i - 1, wq = p % fmap, yq = (p / fmap) % fmap;
-        back = e < qd ? (yq > 0 ? fmap : 0) : (wq > 0 ? 1 : 0);
-    } else {
-        back = i > 0 ? 1 : 0;
-    }
+    const int back = ShiftRule(i, D, fmap).back(e);
+    if (back < 0) return;                            // <bos> of a video map is not shifted: out keeps h
     const size_t src = ((size_t)smp * cache_rows + (i - back)) * D + e, dst = r * D + e;
     if (back) {
         *reinterpret_cast<V*>(o_hi + dst) = *reinterpret_cast<const V*>(c_hi + src);
@@ -829,6 +770,55 @@ void rows_launch(const RowsArgs& a, int B, hipStream_t stream) {
     hipLaunchKernelGGL((rows_reduce_kernel<TAB>), dim3(B), dim3(256), 0, stream, a);
 }
 
+// ---- what the four attention entry points share.  Each keeps its own B / R checks, says what `first` holds, and sets tab / n_pos / R ----
+RowsArgs rows_args(int T, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo, int ldq, const uint16_t* kv,
+                   const uint16_t* kv_lo, int cache_rows, const int* first, const uint8_t* mask, const float* nk, const float* nv,
+                   const float* wth, const float* bias, uint16_t* o, uint16_t* o_lo, int ldo) {
+    RowsArgs a{};
+    a.q = q; a.ql = q_lo; a.kv = kv; a.kvl = kv_lo; a.first = first; a.mask = mask; a.nk = nk; a.nv = nv;
+    a.wth = wth; a.bias = bias; a.o = o; a.ol = o_lo; a.ldq = ldq; a.ldo = ldo; a.cache_rows = cache_rows; a.T = T;
+    a.heads = heads; a.dim_head = dim_head; a.scale = scale;
+    return a;
+}
+
+// the argument checks (AMDNUWA_OK = pass).  TAB: the rows come from a.tab, else from the window at a.first.  amdnuwa_attn_decode_rows
+// alone passes lo_agree = false (it never required q_lo / kv_lo / o_lo to agree) and unsupported_first = true (it reports
+// ERR_UNSUPPORTED before it looks at the pitches).
+template <bool TAB>
+int rows_check(const RowsArgs& a, bool lo_agree, bool unsupported_first) {
+    if (!a.q || !a.kv || !a.nk || !a.nv || !a.wth || !a.o || a.T < 1 || a.heads <= 0 || a.dim_head <= 0) return AMDNUWA_ERR_ARG;
+    if (TAB ? (!a.tab || a.cache_rows <= 0 || a.n_pos <= 0) : (!a.first || a.cache_rows < a.T)) return AMDNUWA_ERR_ARG;
+    if (lo_agree && ((a.ql != nullptr) != (a.kvl != nullptr) || (a.ql != nullptr) != (a.ol != nullptr))) return AMDNUWA_ERR_ARG;
+    const bool unsupported = a.heads > 8 || (a.dim_head != 32 && a.dim_head != 64);
+    if (unsupported && unsupported_first) return AMDNUWA_ERR_UNSUPPORTED;
+    const long long inner = (long long)a.heads * a.dim_head;
+    if (a.ldq < inner || a.ldo < inner) return AMDNUWA_ERR_ARG;
+    return unsupported ? AMDNUWA_ERR_UNSUPPORTED : AMDNUWA_OK;
+}
+
+// carves the workspace (scores | stats | partial rows of ws_rows queries) and launches: `total` queries, at once (a.R == 0) or in chunks of
+// at most ROWS_CHUNK that share the workspace -- the launches of a stream run in order
+template <bool TAB>
+int rows_run(RowsArgs& a, int ws_rows, int total, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    const size_t nf = rows_ws_floats(ws_rows, a.T, a.heads, a.dim_head, a.nsplit);
+    if (!workspace || workspace_bytes < nf * sizeof(float)) return AMDNUWA_ERR_WORKSPACE;
+    a.sc = static_cast<float*>(workspace);
+    a.st = a.sc + (size_t)ws_rows * a.heads * (a.T + 1);
+    a.part = a.st + (size_t)ws_rows * a.nsplit * a.heads * 2;
+    if (a.R > 0)
+        for (a.u0 = 0; a.u0 < total; a.u0 += ROWS_CHUNK) rows_launch<TAB>(a, total - a.u0 < ROWS_CHUNK ? total - a.u0 : ROWS_CHUNK, stream);
+    else
+        rows_launch<TAB>(a, total, stream);
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+
+// queries whose scores, statistics and partial rows a rows form keeps at a time: one chunk's (B, R > 0)
+int rows_ws_rows(int B, int R) {
+    const long long rows = (long long)B * R;
+    return (int)(rows < ROWS_CHUNK ? rows : ROWS_CHUNK);
+}
+
 }  // namespace
 
 extern "C" size_t amdnuwa_attn_decode_rows_workspace_bytes(int B, int T, int heads, int dim_head) {
@@ -842,55 +832,27 @@ extern "C" int amdnuwa_attn_decode_rows(int B, int T, int heads, int dim_head, f
                                         const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th,
                                         const float* th_bias, uint16_t* o, uint16_t* o_lo, int ldo, void* workspace,
                                         size_t workspace_bytes, hipStream_t stream) {
-    if (!q || !kv || !first_row || !null_k || !null_v || !w_th || !o) return AMDNUWA_ERR_ARG;
-    if (heads <= 0 || dim_head <= 0 || T < 1 || cache_rows < T) return AMDNUWA_ERR_ARG;
-    if (heads > 8 || (dim_head != 32 && dim_head != 64)) return AMDNUWA_ERR_UNSUPPORTED;
-    if (ldq < heads * dim_head || ldo < heads * dim_head) return AMDNUWA_ERR_ARG;
-    if (B <= 0) return AMDNUWA_OK;
-    RowsArgs a{};
-    const size_t nf = rows_ws_floats(B, T, heads, dim_head, a.nsplit);
-    if (!workspace || workspace_bytes < nf * sizeof(float)) return AMDNUWA_ERR_WORKSPACE;
-    a.q = q; a.ql = q_lo; a.kv = kv; a.kvl = kv_lo; a.first = first_row; a.mask = key_mask; a.nk = null_k; a.nv = null_v;
-    a.wth = w_th; a.bias = th_bias; a.o = o; a.ol = o_lo; a.ldq = ldq; a.ldo = ldo; a.cache_rows = cache_rows; a.T = T;
-    a.heads = heads; a.dim_head = dim_head; a.scale = scale;
-    a.sc = static_cast<float*>(workspace);
-    a.st = a.sc + (size_t)B * heads * (T + 1);
-    a.part = a.st + (size_t)B * a.nsplit * heads * 2;
-    rows_launch<false>(a, B, stream);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    RowsArgs a = rows_args(T, heads, dim_head, scale, q, q_lo, ldq, kv, kv_lo, cache_rows, first_row, key_mask, null_k, null_v, w_th,
+                           th_bias, o, o_lo, ldo);
+    if (const int bad = rows_check<false>(a, /*lo_agree=*/false, /*unsupported_first=*/true)) return bad;
+    if (B <= 0) return AMDNUWA_OK;                                                // an empty batch, once its arguments are valid
+    return rows_run<false>(a, B, B, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t amdnuwa_attn_rows_workspace_bytes(int B, int R, int T, int heads, int dim_head) {
-    if (B <= 0 || R <= 0) return 0;
-    const long long rows = (long long)B * R;
-    return amdnuwa_attn_decode_rows_workspace_bytes((int)(rows < ROWS_CHUNK ? rows : ROWS_CHUNK), T, heads, dim_head);
+    return B <= 0 || R <= 0 ? 0 : amdnuwa_attn_decode_rows_workspace_bytes(rows_ws_rows(B, R), T, heads, dim_head);
 }
 
 extern "C" int amdnuwa_attn_rows(int B, int R, int T, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo, int ldq,
                                  const uint16_t* kv, const uint16_t* kv_lo, int cache_rows, const int* first_row, const uint8_t* key_mask,
                                  const float* null_k, const float* null_v, const float* w_th, const float* th_bias, uint16_t* o,
                                  uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    if (!q || !kv || !first_row || !null_k || !null_v || !w_th || !o) return AMDNUWA_ERR_ARG;
-    if (B <= 0 || R <= 0 || T <= 0 || heads <= 0 || dim_head <= 0 || cache_rows < T) return AMDNUWA_ERR_ARG;
-    if ((long long)B * R > 0x7fffffffLL) return AMDNUWA_ERR_ARG;                  // (the q / o row index is an int)
-    if ((q_lo != nullptr) != (kv_lo != nullptr) || (q_lo != nullptr) != (o_lo != nullptr)) return AMDNUWA_ERR_ARG;
-    if ((long long)ldq < (long long)heads * dim_head || (long long)ldo < (long long)heads * dim_head) return AMDNUWA_ERR_ARG;
-    if (heads > 8 || (dim_head != 32 && dim_head != 64)) return AMDNUWA_ERR_UNSUPPORTED;
-    const int total = B * R, rows = total < ROWS_CHUNK ? total : ROWS_CHUNK;
-    RowsArgs a{};
-    const size_t nf = rows_ws_floats(rows, T, heads, dim_head, a.nsplit);
-    if (!workspace || workspace_bytes < nf * sizeof(float)) return AMDNUWA_ERR_WORKSPACE;
-    a.q = q; a.ql = q_lo; a.kv = kv; a.kvl = kv_lo; a.first = first_row; a.mask = key_mask; a.nk = null_k; a.nv = null_v;
-    a.wth = w_th; a.bias = th_bias; a.o = o; a.ol = o_lo; a.ldq = ldq; a.ldo = ldo; a.cache_rows = cache_rows; a.T = T;
-    a.heads = heads; a.dim_head = dim_head; a.scale = scale; a.R = R;
-    a.sc = static_cast<float*>(workspace);
-    a.st = a.sc + (size_t)rows * heads * (T + 1);
-    a.part = a.st + (size_t)rows * a.nsplit * heads * 2;
-    // chunks of at most ROWS_CHUNK queries share the workspace: the launches of a stream run in order
-    for (a.u0 = 0; a.u0 < total; a.u0 += ROWS_CHUNK) rows_launch<false>(a, total - a.u0 < ROWS_CHUNK ? total - a.u0 : ROWS_CHUNK, stream);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    if (B <= 0 || R <= 0 || (long long)B * R > 0x7fffffffLL) return AMDNUWA_ERR_ARG;   // (the q / o row index is an int)
+    RowsArgs a = rows_args(T, heads, dim_head, scale, q, q_lo, ldq, kv, kv_lo, cache_rows, first_row, key_mask, null_k, null_v, w_th,
+                           th_bias, o, o_lo, ldo);
+    a.R = R;
+    if (const int bad = rows_check<false>(a, /*lo_agree=*/true, /*unsupported_first=*/false)) return bad;
+    return rows_run<false>(a, rows_ws_rows(B, R), B * R, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t amdnuwa_cross2dna_decode_workspace_bytes(int B, int J, int heads, int dim_head) {
@@ -902,57 +864,29 @@ extern "C" int amdnuwa_cross2dna_decode(int B, int J, int heads, int dim_head, f
                                         const int* pos, const uint8_t* key_mask, const float* null_k, const float* null_v,
                                         const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes,
                                         hipStream_t stream) {
-    if (!q || !kv || !slot_rows || !pos || !null_k || !null_v || !w_th || !o) return AMDNUWA_ERR_ARG;
-    if (B <= 0 || J <= 0 || heads <= 0 || dim_head <= 0 || ctx_rows <= 0 || n_pos <= 0) return AMDNUWA_ERR_ARG;
-    if ((q_lo != nullptr) != (kv_lo != nullptr) || (q_lo != nullptr) != (o_lo != nullptr)) return AMDNUWA_ERR_ARG;
-    if ((long long)ldq < (long long)heads * dim_head || (long long)ldo < (long long)heads * dim_head) return AMDNUWA_ERR_ARG;
-    if (heads > 8 || (dim_head != 32 && dim_head != 64)) return AMDNUWA_ERR_UNSUPPORTED;
-    RowsArgs a{};
-    const size_t nf = rows_ws_floats(B, J, heads, dim_head, a.nsplit);
-    if (!workspace || workspace_bytes < nf * sizeof(float)) return AMDNUWA_ERR_WORKSPACE;
-    a.q = q; a.ql = q_lo; a.kv = kv; a.kvl = kv_lo; a.first = pos; a.mask = key_mask; a.nk = null_k; a.nv = null_v;
-    a.wth = w_th; a.bias = nullptr; a.o = o; a.ol = o_lo; a.ldq = ldq; a.ldo = ldo; a.cache_rows = ctx_rows; a.T = J;
-    a.heads = heads; a.dim_head = dim_head; a.scale = scale; a.tab = slot_rows; a.n_pos = n_pos;
-    a.sc = static_cast<float*>(workspace);
-    a.st = a.sc + (size_t)B * heads * (J + 1);
-    a.part = a.st + (size_t)B * a.nsplit * heads * 2;
-    rows_launch<true>(a, B, stream);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    if (B <= 0 || !pos) return AMDNUWA_ERR_ARG;
+    RowsArgs a = rows_args(J, heads, dim_head, scale, q, q_lo, ldq, kv, kv_lo, ctx_rows, pos, key_mask, null_k, null_v, w_th, nullptr, o,
+                           o_lo, ldo);                                            // (`first` holds the decoder row)
+    a.tab = slot_rows; a.n_pos = n_pos;
+    if (const int bad = rows_check<true>(a, /*lo_agree=*/true, /*unsupported_first=*/false)) return bad;
+    return rows_run<true>(a, B, B, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t amdnuwa_cross2dna_rows_workspace_bytes(int B, int R, int J, int heads, int dim_head) {
-    if (B <= 0 || R <= 0) return 0;
-    const long long rows = (long long)B * R;
-    return amdnuwa_attn_decode_rows_workspace_bytes((int)(rows < ROWS_CHUNK ? rows : ROWS_CHUNK), J, heads, dim_head);
+    return B <= 0 || R <= 0 ? 0 : amdnuwa_attn_decode_rows_workspace_bytes(rows_ws_rows(B, R), J, heads, dim_head);
 }
 
 extern "C" int amdnuwa_cross2dna_rows(int B, int R, int J, int heads, int dim_head, float scale, const uint16_t* q, const uint16_t* q_lo,
                                       int ldq, const uint16_t* kv, const uint16_t* kv_lo, int ctx_rows, const int* slot_rows, int n_pos,
                                       const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o,
                                       uint16_t* o_lo, int ldo, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    if (!q || !kv || !slot_rows || !null_k || !null_v || !w_th || !o) return AMDNUWA_ERR_ARG;
-    if (B <= 0 || R <= 0 || J <= 0 || heads <= 0 || dim_head <= 0 || ctx_rows <= 0 || n_pos <= 0) return AMDNUWA_ERR_ARG;
-    if ((long long)B * R > 0x7fffffffLL) return AMDNUWA_ERR_ARG;                  // (the q / o row index is an int)
-    if ((q_lo != nullptr) != (kv_lo != nullptr) || (q_lo != nullptr) != (o_lo != nullptr)) return AMDNUWA_ERR_ARG;
-    if ((long long)ldq < (long long)heads * dim_head || (long long)ldo < (long long)heads * dim_head) return AMDNUWA_ERR_ARG;
-    if (heads > 8 || (dim_head != 32 && dim_head != 64)) return AMDNUWA_ERR_UNSUPPORTED;
+    if (B <= 0 || R <= 0 || (long long)B * R > 0x7fffffffLL) return AMDNUWA_ERR_ARG;   // (the q / o row index is an int)
+    RowsArgs a = rows_args(J, heads, dim_head, scale, q, q_lo, ldq, kv, kv_lo, ctx_rows, nullptr, key_mask, null_k, null_v, w_th, nullptr,
+                           o, o_lo, ldo);                                         // (`first` is not read: row r is at decoder row r)
+    a.tab = slot_rows; a.n_pos = n_pos; a.R = R;
+    if (const int bad = rows_check<true>(a, /*lo_agree=*/true, /*unsupported_first=*/false)) return bad;
     if (R == 1) return AMDNUWA_OK;                                                // <bos> alone: the caller's row, nothing to launch
-    const long long all = (long long)B * R;
-    const int rows = (int)(all < ROWS_CHUNK ? all : ROWS_CHUNK), total = B * (R - 1);
-    RowsArgs a{};
-    const size_t nf = rows_ws_floats(rows, J, heads, dim_head, a.nsplit);
-    if (!workspace || workspace_bytes < nf * sizeof(float)) return AMDNUWA_ERR_WORKSPACE;
-    a.q = q; a.ql = q_lo; a.kv = kv; a.kvl = kv_lo; a.first = nullptr; a.mask = key_mask; a.nk = null_k; a.nv = null_v;
-    a.wth = w_th; a.bias = nullptr; a.o = o; a.ol = o_lo; a.ldq = ldq; a.ldo = ldo; a.cache_rows = ctx_rows; a.T = J;
-    a.heads = heads; a.dim_head = dim_head; a.scale = scale; a.tab = slot_rows; a.n_pos = n_pos; a.R = R;
-    a.sc = static_cast<float*>(workspace);
-    a.st = a.sc + (size_t)rows * heads * (J + 1);
-    a.part = a.st + (size_t)rows * a.nsplit * heads * 2;
-    // chunks of at most ROWS_CHUNK queries share the workspace: the launches of a stream run in order
-    for (a.u0 = 0; a.u0 < total; a.u0 += ROWS_CHUNK) rows_launch<true>(a, total - a.u0 < ROWS_CHUNK ? total - a.u0 : ROWS_CHUNK, stream);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return rows_run<true>(a, rows_ws_rows(B, R), B * (R - 1), workspace, workspace_bytes, stream);   // (the workspace is sized by B * R)
 }
 
 extern "C" int amdnuwa_decode_shift(const uint16_t* h_hi, const uint16_t* h_lo, uint16_t* cache_hi, uint16_t* cache_lo,

@@ -59,6 +59,11 @@ def _cast_row(x, lo):
     return out
 
 
+def _repeat_rows(o, R):
+    """BF row [B, inner] -> the same row R times, sample-major [B * R, inner]: materialised, a writable copy also at R = 1"""
+    return K.BF(*(None if t is None else t[:, None].repeat(1, R, 1).reshape(t.shape[0] * R, -1) for t in (o.hi, o.lo)))
+
+
 def _row_program(dec, context, xm=None):
     """The row program of a decoder: ({stream: [block spec, ...]}, halves, combine); a single-stream decoder is stream 'v'.  A spec is the
     dict IncrementalDecoder's `block_list` takes: `mod`, `context`, `xm`, `dst`, `store_before` / `store_after`.
@@ -289,10 +294,7 @@ class IncrementalDecoder:
                 W = ops.XInner.weights(inner._cache, inner._params())
                 g = blk.xg
                 if blk.o_const is not None:         # the all-masked pass: the same row for every position
-                    o = blk.o_const
-                    if R is not None:
-                        rep = lambda t: None if t is None else t[:, None].expand(B, R, t.shape[-1]).reshape(B * R, -1).contiguous()
-                        o = K.BF(rep(o.hi), rep(o.lo))
+                    o = blk.o_const if R is None else _repeat_rows(blk.o_const, R)
                 else:
                     q = K.gemm_nt(h, W['q'], out_bf16=True)
                     if blk.long:                    # more than 287 context keys: the to_kv rows in place, one query or R per sample
@@ -438,12 +440,11 @@ class _Cross2DNARows:
         B, inner, mod = self.B, self.inner, self.mod
         first = lambda t: None if t is None else t.reshape(B, R, inner)[:, 0]
         if self.o_const is not None:
-            rep = lambda t: None if t is None else t[:, None].repeat(1, R, 1)      # (a copy also at R = 1: row 0 is overwritten below)
-            o = K.BF(rep(self.o_const.hi), rep(self.o_const.lo))
-            o.hi[:, 0] = self.o_bos.hi
+            o = _repeat_rows(self.o_const, R)                                      # (a copy also at R = 1: row 0 is overwritten below)
+            first(o.hi)[:] = self.o_bos.hi
             if o.lo is not None:
-                o.lo[:, 0] = self.o_bos.lo if self.o_bos.lo is not None else 0
-            return K.BF(o.hi.reshape(B * R, inner), None if o.lo is None else o.lo.reshape(B * R, inner))
+                first(o.lo)[:] = self.o_bos.lo if self.o_bos.lo is not None else 0
+            return o
         q = K.gemm_nt(h, W['q'], out_bf16=True)
         o = K.cross2dna_rows(q, self.kv, self.slot_rows, R, mod.heads, mod.dim_head, self.nk, self.nv, self.wth, mask_u8=self.mask_u8,
                              scale=mod.scale)

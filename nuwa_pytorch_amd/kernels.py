@@ -1201,18 +1201,25 @@ def decode_shift(h, cache, pos_dev, fmap):
     return out
 
 
+def _ln_rows(y, resid, post, nxt, R, cache, pos_dev, fmap, eps):
+    """decode_ln (R = None: one row per sample, at the device-side position) and prefill_ln (R rows per sample): outputs and the call"""
+    L = _lib.lib()
+    yp, ybf, (rows, D), dev = _f32_or_bf(y)
+    assert R is None or (rows % R == 0 and (cache is None or cache.hi.shape[0] == rows // R))
+    x_new = torch.empty((rows, D), dtype=torch.float32, device=dev) if resid is not None else None
+    h = empty_bf((rows, D), dev) if nxt is not None else BF(None, None)
+    ch, cl, crows = (cache.hi, cache.lo, cache.hi.shape[1]) if cache is not None else (None, None, 0)
+    fn, where = ('amdnuwa_decode_ln', (_p(pos_dev), rows)) if R is None else ('amdnuwa_prefill_ln', (rows // R, R))
+    check(getattr(L, fn)(yp, 1 if ybf else 0, _p(resid), _p(post[0]) if post else None, _p(post[1]) if post else None,
+                         _p(nxt[0]) if nxt else None, _p(nxt[1]) if nxt else None, _p(x_new), _p(ch), _p(cl), _p(h.hi), _p(h.lo),
+                         *where, crows, D, fmap, eps, _stream()), fn)
+    return x_new, (h if nxt is not None else None)
+
+
 def decode_ln(y, resid, post, nxt, cache=None, pos_dev=None, fmap=0, eps=1e-5):
     """the norms around a block for the single new row: post = (w, b) or None, nxt = (w, b) or None.
     returns (x_new fp32 [B, D] or None when resid is None, h BF [B, D] or None when nxt is None)"""
-    L = _lib.lib()
-    yp, ybf, (B, D), dev = _f32_or_bf(y)
-    x_new = torch.empty((B, D), dtype=torch.float32, device=dev) if resid is not None else None
-    h = empty_bf((B, D), dev) if nxt is not None else BF(None, None)
-    ch, cl, rows = (cache.hi, cache.lo, cache.hi.shape[1]) if cache is not None else (None, None, 0)
-    check(L.amdnuwa_decode_ln(yp, 1 if ybf else 0, _p(resid), _p(post[0]) if post else None, _p(post[1]) if post else None,
-                              _p(nxt[0]) if nxt else None, _p(nxt[1]) if nxt else None, _p(x_new), _p(ch), _p(cl), _p(h.hi),
-                              _p(h.lo), _p(pos_dev), B, rows, D, fmap, eps, _stream()), 'amdnuwa_decode_ln')
-    return x_new, (h if nxt is not None else None)
+    return _ln_rows(y, resid, post, nxt, None, cache, pos_dev, fmap, eps)
 
 
 def s3_decode(g, qkv, kv_cache, pos_dev, wth, rel_bias=None):
@@ -1229,17 +1236,7 @@ def s3_decode(g, qkv, kv_cache, pos_dev, wth, rel_bias=None):
 def prefill_ln(y, resid, post, nxt, R, cache=None, fmap=0, eps=1e-5):
     """decode_ln for R rows per sample at once (rows sample-major: y / resid [B*R, D]): bit-identical to R decode_ln calls at
     pos = 0 .. R-1; rows [0, R) of cache BF [B, rows, D] are written.  Returns (x_new fp32 [B*R, D] or None, h BF [B*R, D] or None)"""
-    L = _lib.lib()
-    yp, ybf, (BR, D), dev = _f32_or_bf(y)
-    assert BR % R == 0
-    x_new = torch.empty((BR, D), dtype=torch.float32, device=dev) if resid is not None else None
-    h = empty_bf((BR, D), dev) if nxt is not None else BF(None, None)
-    ch, cl, rows = (cache.hi, cache.lo, cache.hi.shape[1]) if cache is not None else (None, None, 0)
-    assert cache is None or cache.hi.shape[0] == BR // R
-    check(L.amdnuwa_prefill_ln(yp, 1 if ybf else 0, _p(resid), _p(post[0]) if post else None, _p(post[1]) if post else None,
-                               _p(nxt[0]) if nxt else None, _p(nxt[1]) if nxt else None, _p(x_new), _p(ch), _p(cl), _p(h.hi),
-                               _p(h.lo), BR // R, R, rows, D, fmap, eps, _stream()), 'amdnuwa_prefill_ln')
-    return x_new, (h if nxt is not None else None)
+    return _ln_rows(y, resid, post, nxt, R, cache, None, fmap, eps)
 
 
 def prefill_kv(qkv, kv_cache, R):
@@ -1269,48 +1266,47 @@ def attn_decode_rows_splits(T):
     return (T + 1 + ATTN_DECODE_ROWS_SPLIT - 1) // ATTN_DECODE_ROWS_SPLIT
 
 
+def _rows_attention(fn, q, kv, T, R, heads, dim_head, mid, consts, mask_u8, mask_cols, scale, out=None, lo_agree=True):
+    """what the four single-query attention wrappers share: the device check, the shape / dtype / contiguity asserts, the output (`out`
+    honoured) and workspace allocation, and the call of entry point `fn`.  R: rows per sample, None = the single-row form (one q row per
+    sample); mid: the entry point's arguments between cache_rows and key_mask (device int32 tensors and ints, in its order); consts: the
+    fp32 tensors between key_mask and o; mask_u8 [B, mask_cols] or None"""
+    L = _lib.lib()
+    _chk_dev(q.hi, kv.hi, *(t for t in mid if torch.is_tensor(t)), *consts, mask_u8)
+    assert kv.hi.dim() == 3 and kv.hi.is_contiguous()
+    B, inner = kv.hi.shape[0], heads * dim_head
+    rows, dims = (B, (B, T)) if R is None else (B * R, (B, R, T))
+    assert q.hi.shape[0] == rows and kv.hi.shape[2] == 2 * inner and (R is None or (R >= 1 and q.hi.shape[1] == inner))
+    assert not lo_agree or ((q.lo is None) == (kv.lo is None) and (kv.lo is None or kv.lo.is_contiguous()))
+    assert all(t.dtype == torch.int32 for t in mid if torch.is_tensor(t))
+    assert mask_u8 is None or (mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (B, mask_cols) and mask_u8.is_contiguous())
+    o = empty_bf((rows, inner), q.hi.device, lo=q.lo is not None) if out is None else out
+    assert tuple(o.hi.shape) == (rows, inner) and o.hi.is_contiguous() and (o.lo is None) == (q.lo is None) and (o.lo is None or o.lo.is_contiguous())
+    nb = getattr(L, fn + '_workspace_bytes')(*dims, heads, dim_head)
+    ws = workspace(nb, q.hi.device)
+    check(getattr(L, fn)(*dims, heads, dim_head, dim_head ** -0.5 if scale is None else scale, _p(q.hi), _p(q.lo), q.hi.stride(0),
+                         _p(kv.hi), _p(kv.lo), kv.hi.shape[1], *(_p(t) if torch.is_tensor(t) else t for t in mid), _p(mask_u8),
+                         *(_p(t) for t in consts), _p(o.hi), _p(o.lo), inner, _p(ws), nb, _stream()), fn)
+    return o
+
+
 def attn_decode_rows(q, kv, first_dev, T, heads, dim_head, null_k, null_v, wth, th_bias=None, mask_u8=None, scale=None):
     """single-query attention over T cached rows: q BF [B, inner] (unscaled); kv BF [B, cache_rows, 2 * inner] (k | v); first_dev int32
     [1] on the device: the cache row of the first key; null_k / null_v fp32 [heads, dim_head]; wth fp32 [heads, heads]; th_bias fp32
     [heads] or None; mask_u8 [B, T] or None.  Returns o BF [B, inner]"""
-    L = _lib.lib()
-    _chk_dev(q.hi, kv.hi, first_dev, null_k, null_v, wth, th_bias, mask_u8)
-    B, inner = q.hi.shape[0], heads * dim_head
-    assert kv.hi.dim() == 3 and kv.hi.is_contiguous() and kv.hi.shape[0] == B and kv.hi.shape[2] == 2 * inner
-    assert first_dev.dtype == torch.int32 and (mask_u8 is None or (mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (B, T) and mask_u8.is_contiguous()))
-    o = empty_bf((B, inner), q.hi.device, lo=q.lo is not None)
-    nb = L.amdnuwa_attn_decode_rows_workspace_bytes(B, T, heads, dim_head)
-    ws = workspace(nb, q.hi.device)
-    check(L.amdnuwa_attn_decode_rows(B, T, heads, dim_head, dim_head ** -0.5 if scale is None else scale, _p(q.hi), _p(q.lo),
-                                     q.hi.stride(0), _p(kv.hi), _p(kv.lo), kv.hi.shape[1], _p(first_dev), _p(mask_u8), _p(null_k),
-                                     _p(null_v), _p(wth), _p(th_bias), _p(o.hi), _p(o.lo), inner, _p(ws), nb, _stream()),
-          'amdnuwa_attn_decode_rows')
-    return o
+    return _rows_attention('amdnuwa_attn_decode_rows', q, kv, T, None, heads, dim_head, (first_dev,), (null_k, null_v, wth, th_bias),
+                           mask_u8, T, scale, lo_agree=False)     # (the one entry point that never asked q.lo and kv.lo to agree)
 
 
-ATTN_ROWS_CHUNK = 2048           # query rows amdnuwa_attn_rows takes per set of launches: its workspace is that of one chunk
+ATTN_ROWS_CHUNK = 2048           # query rows amdnuwa_attn_rows / amdnuwa_cross2dna_rows take per set of launches: the workspace is one chunk's
 
 
 def attn_rows(q, kv, first_dev, T, R, heads, dim_head, null_k, null_v, wth, th_bias=None, mask_u8=None, scale=None, out=None):
     """the rows form of attn_decode_rows: q BF [B * R, inner] (unscaled, sample-major: row b * R + r is decoder row r of sample b); kv,
     first_dev, null_k / null_v, wth, th_bias, mask_u8 [B, T] as there.  All R rows of a sample attend the same window in ONE call, row
     (b, r) bit-identical to attn_decode_rows on q[b * R + r] alone.  Returns o BF [B * R, inner] (`out`: written in place and returned)"""
-    L = _lib.lib()
-    _chk_dev(q.hi, kv.hi, first_dev, null_k, null_v, wth, th_bias, mask_u8)
-    BR, inner = q.hi.shape[0], heads * dim_head
-    B = kv.hi.shape[0]
-    assert R >= 1 and BR == B * R and q.hi.shape[1] == inner
-    assert kv.hi.dim() == 3 and kv.hi.is_contiguous() and kv.hi.shape[2] == 2 * inner
-    assert (q.lo is None) == (kv.lo is None) and (kv.lo is None or kv.lo.is_contiguous())
-    assert first_dev.dtype == torch.int32 and (mask_u8 is None or (mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (B, T) and mask_u8.is_contiguous()))
-    o = empty_bf((BR, inner), q.hi.device, lo=q.lo is not None) if out is None else out
-    assert tuple(o.hi.shape) == (BR, inner) and o.hi.is_contiguous() and (o.lo is None) == (q.lo is None) and (o.lo is None or o.lo.is_contiguous())
-    nb = L.amdnuwa_attn_rows_workspace_bytes(B, R, T, heads, dim_head)
-    ws = workspace(nb, q.hi.device)
-    check(L.amdnuwa_attn_rows(B, R, T, heads, dim_head, dim_head ** -0.5 if scale is None else scale, _p(q.hi), _p(q.lo), q.hi.stride(0),
-                              _p(kv.hi), _p(kv.lo), kv.hi.shape[1], _p(first_dev), _p(mask_u8), _p(null_k), _p(null_v), _p(wth),
-                              _p(th_bias), _p(o.hi), _p(o.lo), inner, _p(ws), nb, _stream()), 'amdnuwa_attn_rows')
-    return o
+    return _rows_attention('amdnuwa_attn_rows', q, kv, T, R, heads, dim_head, (first_dev,), (null_k, null_v, wth, th_bias), mask_u8, T,
+                           scale, out=out)
 
 
 def cross2dna_decode(q, kv, slot_rows, pos_dev, heads, dim_head, null_k, null_v, wth, mask_u8=None, scale=None):
@@ -1318,26 +1314,13 @@ def cross2dna_decode(q, kv, slot_rows, pos_dev, heads, dim_head, null_k, null_v,
     slot_rows int32 [n_pos, J] on the device: the context row of every window slot of every feature-map position, -1 = padding; pos_dev
     int32 [1] on the device: the decoder row of the query (>= 1); null_k / null_v fp32 [heads, dim_head]; wth fp32 [heads, heads]; mask_u8
     [B, ctx_rows] or None.  Returns o BF [B, inner]"""
-    L = _lib.lib()
-    _chk_dev(q.hi, kv.hi, slot_rows, pos_dev, null_k, null_v, wth, mask_u8)
-    B, inner = q.hi.shape[0], heads * dim_head
-    assert kv.hi.dim() == 3 and kv.hi.is_contiguous() and kv.hi.shape[0] == B and kv.hi.shape[2] == 2 * inner
-    assert (q.lo is None) == (kv.lo is None) and (kv.lo is None or kv.lo.is_contiguous())
-    ctx_rows = kv.hi.shape[1]
-    assert slot_rows.dtype == torch.int32 and slot_rows.dim() == 2 and slot_rows.is_contiguous() and pos_dev.dtype == torch.int32
-    assert mask_u8 is None or (mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (B, ctx_rows) and mask_u8.is_contiguous())
+    assert slot_rows.dim() == 2 and slot_rows.is_contiguous() and kv.hi.dim() == 3
     n_pos, J = slot_rows.shape
-    o = empty_bf((B, inner), q.hi.device, lo=q.lo is not None)
-    nb = L.amdnuwa_cross2dna_decode_workspace_bytes(B, J, heads, dim_head)
-    ws = workspace(nb, q.hi.device)
-    check(L.amdnuwa_cross2dna_decode(B, J, heads, dim_head, dim_head ** -0.5 if scale is None else scale, _p(q.hi), _p(q.lo),
-                                     q.hi.stride(0), _p(kv.hi), _p(kv.lo), ctx_rows, _p(slot_rows), n_pos, _p(pos_dev), _p(mask_u8),
-                                     _p(null_k), _p(null_v), _p(wth), _p(o.hi), _p(o.lo), inner, _p(ws), nb, _stream()),
-          'amdnuwa_cross2dna_decode')
-    return o
+    return _rows_attention('amdnuwa_cross2dna_decode', q, kv, J, None, heads, dim_head, (slot_rows, n_pos, pos_dev), (null_k, null_v, wth),
+                           mask_u8, kv.hi.shape[1], scale)
 
 
-CROSS2DNA_ROWS_CHUNK = 2048      # query rows amdnuwa_cross2dna_rows takes per set of launches: its workspace is that of one chunk
+CROSS2DNA_ROWS_CHUNK = ATTN_ROWS_CHUNK
 
 
 def cross2dna_rows(q, kv, slot_rows, R, heads, dim_head, null_k, null_v, wth, mask_u8=None, scale=None, out=None):
@@ -1345,25 +1328,10 @@ def cross2dna_rows(q, kv, slot_rows, R, heads, dim_head, null_k, null_v, wth, ma
     slot_rows, null_k / null_v, wth, mask_u8 as there.  Rows 1 .. R-1 of every sample attend in ONE call, row (b, r) bit-identical to
     cross2dna_decode on q[b * R + r] at pos = r; rows b * R (<bos>) are neither read nor written -- they are the caller's.  Returns o BF
     [B * R, inner] (`out`: written in place and returned)"""
-    L = _lib.lib()
-    _chk_dev(q.hi, kv.hi, slot_rows, null_k, null_v, wth, mask_u8)
-    BR, inner = q.hi.shape[0], heads * dim_head
-    B = kv.hi.shape[0]
-    assert R >= 1 and BR == B * R and q.hi.shape[1] == inner
-    assert kv.hi.dim() == 3 and kv.hi.is_contiguous() and kv.hi.shape[2] == 2 * inner
-    assert (q.lo is None) == (kv.lo is None) and (kv.lo is None or kv.lo.is_contiguous())
-    ctx_rows = kv.hi.shape[1]
-    assert slot_rows.dtype == torch.int32 and slot_rows.dim() == 2 and slot_rows.is_contiguous()
-    assert mask_u8 is None or (mask_u8.dtype == torch.uint8 and tuple(mask_u8.shape) == (B, ctx_rows) and mask_u8.is_contiguous())
+    assert slot_rows.dim() == 2 and slot_rows.is_contiguous() and kv.hi.dim() == 3
     n_pos, J = slot_rows.shape
-    o = empty_bf((BR, inner), q.hi.device, lo=q.lo is not None) if out is None else out
-    assert tuple(o.hi.shape) == (BR, inner) and o.hi.is_contiguous() and (o.lo is None) == (q.lo is None) and (o.lo is None or o.lo.is_contiguous())
-    nb = L.amdnuwa_cross2dna_rows_workspace_bytes(B, R, J, heads, dim_head)
-    ws = workspace(nb, q.hi.device)
-    check(L.amdnuwa_cross2dna_rows(B, R, J, heads, dim_head, dim_head ** -0.5 if scale is None else scale, _p(q.hi), _p(q.lo),
-                                   q.hi.stride(0), _p(kv.hi), _p(kv.lo), ctx_rows, _p(slot_rows), n_pos, _p(mask_u8), _p(null_k),
-                                   _p(null_v), _p(wth), _p(o.hi), _p(o.lo), inner, _p(ws), nb, _stream()), 'amdnuwa_cross2dna_rows')
-    return o
+    return _rows_attention('amdnuwa_cross2dna_rows', q, kv, J, R, heads, dim_head, (slot_rows, n_pos), (null_k, null_v, wth), mask_u8,
+                           kv.hi.shape[1], scale, out=out)
 
 
 def sample_next_row(logits, keep, temperature, u, emb, pos, pos_idx, step_dev, ids, x_next, allow_unsupported=False):
