@@ -381,6 +381,26 @@ int amdnuwa_sparse3dna_bwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, 
                                const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16, uint16_t* dv_f16,
                                int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace, size_t workspace_bytes,
                                amdnuwa_stream stream);
+/* Attention dropout inside the causal window (the `self.dropout(attn)` of reference nuwa_pytorch.py:554-564, Sparse3DNA, and 746-752,
+ * SparseCausal2DNA as a (time, 1, 1) grid; additive at ABI 21).  With P = softmax over the J slots and P' = W_th . P, the V product and dV take
+ * P'' = keep . P' . drop_scale, and the backward takes dP' = keep . (dO . V^T) . drop_scale; everything below dP' is amdnuwa_sparse3dna_bwd's.
+ * keep: uint8 [B][ntok - 1][J][heads], the index order of the ds / P' workspace, nonzero = keep (the caller draws it; the same array goes to the
+ * forward and to the backward); drop_scale = 1 / (1 - p), finite and >= 1.  Slots hidden by the causal padding ignore the mask; the <bos>
+ * query row still outputs its own value row.  An all-ones mask with drop_scale = 1 gives the bits of amdnuwa_sparse3dna_fwd / _bwd.
+ * Runs the VALU window kernels (row and column-tiled, bf16 and hi + lo operands), never the MFMA band kernels: every geometry
+ * amdnuwa_s3_supported() takes, causal only (g->noncausal: AMDNUWA_ERR_UNSUPPORTED) -- amdnuwa_s3_drop_supported().  keep == NULL or a
+ * drop_scale that is not finite or < 1: AMDNUWA_ERR_ARG.  The backward uses the workspace of amdnuwa_sparse3dna_bwd_workspace_bytes(). */
+int amdnuwa_s3_drop_supported(const amdnuwa_s3_geom* g, int lo_operands);
+int amdnuwa_sparse3dna_fwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                                const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, const uint8_t* keep, float drop_scale,
+                                amdnuwa_stream stream);
+int amdnuwa_sparse3dna_bwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                                const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo, uint16_t* dq,
+                                uint16_t* dk, uint16_t* dv, uint16_t* dq_lo, uint16_t* dk_lo, uint16_t* dv_lo, int ldd,
+                                float* dw_th, int accumulate, void* workspace, size_t workspace_bytes, const uint8_t* keep,
+                                float drop_scale, amdnuwa_stream stream);
 
 /* SparseCross2DNA (np.py:761-901): NUWASketch's decoder cross-attention.  Queries = the video rows q [B*ntok, ldq] (row 0 of every
  * sample is <bos>); keys / values = the sketch context k, v [B*ctx_rows, ldkv], ctx_rows = g->kf * H * W (g->kf = sketch frames).

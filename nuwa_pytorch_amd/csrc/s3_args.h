@@ -38,6 +38,24 @@ struct S3Args {
                                                           // tile = TW + (kw-1)*dw halo.  NT = 1: one workgroup per row (TW = SW = W); the per-workgroup partials are [row][tile]
 };
 
+// Attention dropout (the DROP forms of the VALU forward and query-side backward): keep mask [B][nq][J][NH] in the index order of the ds / P'
+// workspace (nonzero = keep) and s = 1 / (1 - p): P'' = keep . P' . s feeds the V product and dV, dP' = keep . dP'' . s.  Only the DROP
+// instantiations take the two extra words: the kernel argument of the unmasked ones stays S3Args itself.
+struct S3DropArgs : S3Args { const uint8_t* keep; float drop_s; };
+template <bool DROP> struct S3KArgsSel { using type = S3Args; };
+template <> struct S3KArgsSel<true> { using type = S3DropArgs; };
+template <bool DROP> using S3KArgs = typename S3KArgsSel<DROP>::type;
+template <bool DROP> inline S3KArgs<DROP> s3_kargs(const S3Args& a, const uint8_t* keep, float drop_s) {
+    if constexpr (DROP) {
+        S3DropArgs d{};
+        static_cast<S3Args&>(d) = a;
+        d.keep = keep; d.drop_s = drop_s;
+        return d;
+    } else {
+        return a;
+    }
+}
+
 // Column tiling of a grid row.  A row whose thread map ((w*heads + h)*4 + c) fits 512 threads is ONE tile without halo (the row kernels of
 // sparse3dna.hip); a wider one is cut into nt tiles of tw consecutive columns, tw*heads*4 <= 512, the tiles balanced (tw = ceil(W / nt)).
 // A tile stages its own columns plus the halo the kw taps reach: (kw-1)*dw columns in all -- to the left of the queries (right of the keys)
@@ -51,8 +69,9 @@ inline S3Tile s3_tile(const amdnuwa_s3_geom* g) {
     return {tw, nt, tw + (int)halo};
 }
 // launchers of the column-tiled kernels (sparse3dna_wide.hip); `a` is complete, a.NT > 1.  lds_* = dynamic LDS bytes of the launch.
-int s3w_fwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds, hipStream_t stream);
-int s3w_bwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds_q, size_t lds_kv, hipStream_t stream);
+// keep != NULL launches the masked (DROP) forms of the forward and of the query-side backward
+int s3w_fwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds, const uint8_t* keep, float drop_s, hipStream_t stream);
+int s3w_bwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds_q, size_t lds_kv, const uint8_t* keep, float drop_s, hipStream_t stream);
 
 namespace {
 
@@ -109,6 +128,8 @@ __device__ __forceinline__ float quad_sum(float v) {
     v += dpp_quad(v, 0);
     return v;
 }
+// factor of one (query, slot, head) entry under attention dropout: s where the mask keeps it, exactly 0 where it drops it
+__device__ __forceinline__ float keep_factor(uint8_t k, float s) { return k ? s : 0.f; }
 __device__ __forceinline__ float quad_max(float v) {
     v = fmaxf(v, dpp_quad(v, 1));
     v = fmaxf(v, dpp_quad(v, 0));

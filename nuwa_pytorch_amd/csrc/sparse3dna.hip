@@ -20,6 +20,7 @@
 //   bwd_fin: fixed-order reduction of the partials (dW_th, dk[bos], dv[bos] + dO[bos]).
 //
 // hi/lo: every bf16 input may come with a bf16 residual (value = hi + lo); arithmetic is fp32 FMA.
+#include <cmath>
 #include "common.h"
 #include "s3_args.h"
 
@@ -145,8 +146,9 @@ __device__ __forceinline__ void scores_softmax(const S3Args& a, int b, int f, in
     __syncthreads();
 }
 
-template <int DH, bool LO>
-__global__ __launch_bounds__(512, 4) void s3_fwd_kernel(S3Args a) {
+// DROP: attention dropout (np.py:554-564): P'' = keep . P' . s replaces P' in the V product; the mask byte of an entry is read where P' is formed
+template <int DH, bool LO, bool DROP = false>
+__global__ __launch_bounds__(512, 4) void s3_fwd_kernel(S3KArgs<DROP> a) {
     constexpr int CH = DH / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int J = a.kf * a.kh * a.kw + 1;
@@ -191,6 +193,14 @@ __global__ __launch_bounds__(512, 4) void s3_fwd_kernel(S3Args a) {
             for (int hh = 0; hh < 8; ++hh) s += (g < a.NH && hh < a.NH ? wsh[g * a.NH + hh] : 0.f) * pv[hh];
             out[g] = s;
         }
+        if constexpr (DROP) {
+            const int iq = 1 + ry * a.W + item / J;
+            if (iq < a.ntok) {
+                const uint8_t* kp = a.keep + (((size_t)b * (a.ntok - 1) + (iq - 1)) * J + item % J) * a.NH;
+#pragma unroll
+                for (int g = 0; g < 8; ++g) if (g < a.NH) out[g] *= keep_factor(kp[g], a.drop_s);
+            }
+        }
 #pragma unroll
         for (int g = 0; g < 8; ++g) if (g < a.NH) SP[item * a.NH + g] = out[g];
     }
@@ -224,8 +234,10 @@ __global__ __launch_bounds__(512, 4) void s3_fwd_kernel(S3Args a) {
     }
 }
 
-template <int DH, bool LO>
-__global__ __launch_bounds__(512, 4) void s3_bwd_q_kernel(S3Args a) {
+// DROP: the workspace receives P'' = keep . P' . s (what dV is taken with) and dP' = keep . dP'' . s; both are formed in one item pass after the
+// dO.V sweep, so the mask byte of an entry is read once there (+ one byte per (query, head) for the <bos> value partial)
+template <int DH, bool LO, bool DROP = false>
+__global__ __launch_bounds__(512, 4) void s3_bwd_q_kernel(S3KArgs<DROP> a) {
     constexpr int CH = DH / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int J = a.kf * a.kh * a.kw + 1;
@@ -278,21 +290,23 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_kernel(S3Args a) {
         }
     }
     scores_softmax<DH, LO>(a, b, f, y, w, h, c, act, qvalid, qf, qp, SP, st_hi, J);
-    // P' = mix(P) -> global (needed by bwd_kv); P stays in SP
-    for (int item = t; item < a.W * J; item += blockDim.x) {
-        const int wq = item / J, j = item % J;
-        const int iq = 1 + ry * a.W + wq;
-        float pv[8];
+    // P' = mix(P) -> global (needed by bwd_kv); P stays in SP  (DROP: P'' instead, formed after the dO.V sweep below)
+    if constexpr (!DROP) {
+        for (int item = t; item < a.W * J; item += blockDim.x) {
+            const int wq = item / J, j = item % J;
+            const int iq = 1 + ry * a.W + wq;
+            float pv[8];
 #pragma unroll
-        for (int hh = 0; hh < 8; ++hh) pv[hh] = hh < a.NH ? SP[item * a.NH + hh] : 0.f;
-        if (iq < a.ntok) {
-            float* dst = a.pm + (((size_t)b * nq + (iq - 1)) * J + j) * a.NH;
+            for (int hh = 0; hh < 8; ++hh) pv[hh] = hh < a.NH ? SP[item * a.NH + hh] : 0.f;
+            if (iq < a.ntok) {
+                float* dst = a.pm + (((size_t)b * nq + (iq - 1)) * J + j) * a.NH;
 #pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                float s = 0.f;
+                for (int g = 0; g < 8; ++g) {
+                    float s = 0.f;
 #pragma unroll
-                for (int hh = 0; hh < 8; ++hh) s += (g < a.NH && hh < a.NH ? wsh[g * a.NH + hh] : 0.f) * pv[hh];
-                if (g < a.NH) dst[g] = s;
+                    for (int hh = 0; hh < 8; ++hh) s += (g < a.NH && hh < a.NH ? wsh[g * a.NH + hh] : 0.f) * pv[hh];
+                    if (g < a.NH) dst[g] = s;
+                }
             }
         }
     }
@@ -323,6 +337,31 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_kernel(S3Args a) {
         if (c == 0) DP[(w * J + j) * a.NH + h] = s;
     });
     __syncthreads();
+    if constexpr (DROP) {
+        // P'' = keep . mix(P) . s -> global (what bwd_kv takes dV with) and dP' = keep . dP'' . s: one mask byte per entry, read here
+        for (int item = t; item < a.W * J; item += blockDim.x) {
+            const int wq = item / J, j = item % J;
+            const int iq = 1 + ry * a.W + wq;
+            float pv[8];
+#pragma unroll
+            for (int hh = 0; hh < 8; ++hh) pv[hh] = hh < a.NH ? SP[item * a.NH + hh] : 0.f;
+            if (iq < a.ntok) {
+                const size_t ci = (((size_t)b * nq + (iq - 1)) * J + j) * a.NH;
+#pragma unroll
+                for (int g = 0; g < 8; ++g) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int hh = 0; hh < 8; ++hh) s += (g < a.NH && hh < a.NH ? wsh[g * a.NH + hh] : 0.f) * pv[hh];
+                    if (g < a.NH) {
+                        const float kf_ = keep_factor(a.keep[ci + g], a.drop_s);
+                        a.pm[ci + g] = s * kf_;
+                        DP[item * a.NH + g] *= kf_;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
     // dW_th[g][h] partial = sum_{w,j} dP'[g] * P[h]   (thread = (g,h) pair x 8 item groups)
     {
         const int pair = t & 63, grp = t >> 6, ng = blockDim.x >> 6;
@@ -382,6 +421,7 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_kernel(S3Args a) {
         const float d0 = DP[(w * J + 0) * a.NH + h];
         float pm0 = 0.f;                                        // P'[w][0][g = h] = sum_hh Wth[h][hh] P[w][0][hh]
         for (int hh = 0; hh < a.NH; ++hh) pm0 += wsh[h * a.NH + hh] * SP[(w * J + 0) * a.NH + hh];
+        if constexpr (DROP) pm0 *= keep_factor(a.keep[((size_t)b * nq + (i - 1)) * J * a.NH + h], a.drop_s);
 #pragma unroll
         for (int e = 0; e < CH; ++e) {
             const float qe = LO ? qf[e] : ((e & 1) ? hi_f(qp[e >> 1]) : lo_f(qp[e >> 1]));
@@ -2780,9 +2820,19 @@ int s3_fwd_tile_launch(const S3Args& a, const amdnuwa_s3_geom* g, int tr, hipStr
 
 }  // namespace
 
-extern "C" int amdnuwa_sparse3dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
-                                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
-                                      const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, hipStream_t stream) {
+// the masked (attention dropout) forms: the causal window on the VALU kernels of either geometry (row / column tiles) and operand form
+static int drop_geom(const amdnuwa_s3_geom* g, bool lo) {
+    const int rc = check_geom(g);
+    if (rc) return rc;
+    if (s3_lds_need(g, lo) > S3_LDS_MAX || g->noncausal) return AMDNUWA_ERR_UNSUPPORTED;
+    return AMDNUWA_OK;
+}
+static bool drop_args_ok(const uint8_t* keep, float drop_scale) { return keep && std::isfinite(drop_scale) && drop_scale >= 1.f; }
+
+// keep == NULL: amdnuwa_sparse3dna_fwd.  keep != NULL: amdnuwa_sparse3dna_fwd_drop (the DROP forms of the VALU kernels, never the MFMA ones)
+static int s3_fwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                      const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, const uint8_t* keep, float drop_s, hipStream_t stream) {
     int rc = check_geom(g);
     if (rc) return rc;
     if (s3_lds_need(g, k_lo != nullptr) > S3_LDS_MAX) return AMDNUWA_ERR_UNSUPPORTED;
@@ -2799,16 +2849,16 @@ extern "C" int amdnuwa_sparse3dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* 
     //               1 = stage the kh rows of a tap frame at once (needs kh <= KHMAX)
     // (slab staging of a whole tap frame measured slower than row staging: retired)
     const size_t lds = s3_lds(g, k_lo != nullptr).fwd;
-    if (a.NT > 1) return s3w_fwd_launch(a, g->dim_head, k_lo != nullptr, lds, stream);      // column tiles of a wide row
+    if (a.NT > 1) return s3w_fwd_launch(a, g->dim_head, k_lo != nullptr, lds, keep, drop_s, stream);      // column tiles of a wide row
     dim3 grid(g->B * g->F * g->H), block(block_threads(g));
-#define S3F(DH_, LO_)                                                                                             \
+#define S3F(DH_, LO_, DR_)                                                                                        \
     do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3_fwd_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((s3_fwd_kernel<DH_, LO_>), grid, block, lds, stream, a);                               \
+        (void)hipFuncSetAttribute((const void*)s3_fwd_kernel<DH_, LO_, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((s3_fwd_kernel<DH_, LO_, DR_>), grid, block, lds, stream, s3_kargs<DR_>(a, keep, drop_s)); \
     } while (0)
     const bool lo_mode = k_lo != nullptr;
     // MFMA forward (tuning key 3: 1 = keep the dot2 kernel): bf16 operands, 16 queries per grid row, 8 heads x 64
-    if (!lo_mode && !g->noncausal && !(g_amdnuwa_tuning[3] & 1) && g->W == 16 && g->heads == 8 && g->dim_head == 64 && g->kw <= S3M_KW &&
+    if (!keep && !lo_mode && !g->noncausal && !(g_amdnuwa_tuning[3] & 1) && g->W == 16 && g->heads == 8 && g->dim_head == 64 && g->kw <= S3M_KW &&
         g->kf * g->kh <= S3M_PLANES && ld % 8 == 0 && ldo % 4 == 0) {
         a.dbg = g_amdnuwa_tuning[9];
         const int tr = s3_tile_rows(g);
@@ -2819,11 +2869,32 @@ extern "C" int amdnuwa_sparse3dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* 
         LAUNCH_CHECK();
         return AMDNUWA_OK;
     }
-    if (g->dim_head == 64) { if (lo_mode) S3F(64, true); else S3F(64, false); }
-    else { if (lo_mode) S3F(32, true); else S3F(32, false); }
+    if (keep) {
+        if (g->dim_head == 64) { if (lo_mode) S3F(64, true, true); else S3F(64, false, true); }
+        else { if (lo_mode) S3F(32, true, true); else S3F(32, false, true); }
+    } else if (g->dim_head == 64) { if (lo_mode) S3F(64, true, false); else S3F(64, false, false); }
+    else { if (lo_mode) S3F(32, true, false); else S3F(32, false, false); }
 #undef S3F
     LAUNCH_CHECK();
     return AMDNUWA_OK;
+}
+
+extern "C" int amdnuwa_sparse3dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                                      const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, hipStream_t stream) {
+    return s3_fwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, o, o_lo, ldo, nullptr, 1.f, stream);
+}
+
+extern "C" int amdnuwa_s3_drop_supported(const amdnuwa_s3_geom* g, int lo_operands) { return drop_geom(g, lo_operands != 0) == AMDNUWA_OK ? 1 : 0; }
+
+extern "C" int amdnuwa_sparse3dna_fwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                           const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                                           const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, const uint8_t* keep,
+                                           float drop_scale, hipStream_t stream) {
+    const int rc = drop_geom(g, k_lo != nullptr);
+    if (rc) return rc;
+    if (!drop_args_ok(keep, drop_scale)) return AMDNUWA_ERR_ARG;
+    return s3_fwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, o, o_lo, ldo, keep, drop_scale, stream);
 }
 
 // the geometry of the MFMA band kernels: the causal decoder window on a 16-wide grid, 8 heads x 64
@@ -2872,12 +2943,14 @@ extern "C" size_t amdnuwa_sparse3dna_bwd_workspace_bytes(const amdnuwa_s3_geom* 
            amdnuwa_colsum_workspace_bytes((long long)g->B * nq, (int)(J * g->heads));
 }
 
-extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
-                                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
-                                      const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo,
-                                      uint16_t* dq, uint16_t* dk, uint16_t* dv, uint16_t* dq_lo, uint16_t* dk_lo,
-                                      uint16_t* dv_lo, int ldd, float* dw_th, int accumulate, void* workspace,
-                                      size_t workspace_bytes, hipStream_t stream) {
+// keep == NULL: amdnuwa_sparse3dna_bwd.  keep != NULL: amdnuwa_sparse3dna_bwd_drop (the DROP form of the VALU query side; the key side is the
+// same kernel, it reads P'' where it read P')
+static int s3_bwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                      const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo,
+                      uint16_t* dq, uint16_t* dk, uint16_t* dv, uint16_t* dq_lo, uint16_t* dk_lo,
+                      uint16_t* dv_lo, int ldd, float* dw_th, int accumulate, void* workspace,
+                      size_t workspace_bytes, const uint8_t* keep, float drop_s, hipStream_t stream) {
     int rc = check_geom(g);
     if (rc) return rc;
     if (s3_lds_need(g, k_lo != nullptr) > S3_LDS_MAX) return AMDNUWA_ERR_UNSUPPORTED;
@@ -2908,7 +2981,7 @@ extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* 
     const size_t lds_q = l.bq, lds_kv = l.bkv;
     dim3 grid((unsigned)rows), block(block_threads(g));
     // MFMA query-side kernel (tuning key 4: 1 = keep the dot2 kernel): bf16 operands, 16 queries per grid row, 8 heads x 64
-    const bool q_mfma = !has_lo && !dO_lo && !g->noncausal && g_amdnuwa_tuning[4] != 1 && g->W == 16 && g->heads == 8 && g->dim_head == 64 &&
+    const bool q_mfma = !keep && !has_lo && !dO_lo && !g->noncausal && g_amdnuwa_tuning[4] != 1 && g->W == 16 && g->heads == 8 && g->dim_head == 64 &&
                         g->kw <= S3M_KW && g->kf * g->kh <= S3M_PLANES && ld % 8 == 0 && lddo % 8 == 0 && ldd % 4 == 0;
     // recomputing key side (tuning key 4 = 4; OFF by default: it removes the 3.9 GB workspace round trip -- backward traffic 2.85x ->
     // 1.5x algorithmic -- but runs 15-22 % slower: its per-plane head exchange serialises the eight waves and its 180 registers allow one
@@ -2919,7 +2992,7 @@ extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* 
     a.packed = (q_mfma && g_amdnuwa_tuning[4] != 2 && !g->d_rel_bias && g_amdnuwa_tuning[24] != 1 && !a.sep_passes) ? 1 : 0;
     const size_t nspm = (size_t)g->W * (J * g->heads + 4);                          // the MFMA kernels' padded tables (s3m_ts)
     const size_t lds_qm = (nspm * 4 > 8 * 4096 ? nspm * 4 : 8 * 4096) + nspm * 4 + (8 * 64 + 16 * 8) * 4 + 8 * 2048;   // + the score staging tiles
-#define S3B(DH_, LO_)                                                                                             \
+#define S3B(DH_, LO_, DR_)                                                                                        \
     do {                                                                                                          \
         if (q_mfma && a.bias) {                                                                                   \
             (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm); \
@@ -2928,8 +3001,8 @@ extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* 
             (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm); \
             hipLaunchKernelGGL(s3_bwd_q_mfma_kernel<false>, grid, dim3(512), lds_qm, stream, a);                  \
         } else {                                                                                                  \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_q_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q); \
-            hipLaunchKernelGGL((s3_bwd_q_kernel<DH_, LO_>), grid, block, lds_q, stream, a);                       \
+            (void)hipFuncSetAttribute((const void*)s3_bwd_q_kernel<DH_, LO_, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q); \
+            hipLaunchKernelGGL((s3_bwd_q_kernel<DH_, LO_, DR_>), grid, block, lds_q, stream, s3_kargs<DR_>(a, keep, drop_s)); \
         }                                                                                                         \
         LAUNCH_CHECK();                                                                                           \
         if (kv_rc) {                                                                                              \
@@ -2949,10 +3022,13 @@ extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* 
     const bool lo_mode = has_lo || dO_lo != nullptr;
     if (lo_mode && (!has_lo || !dO_lo)) return AMDNUWA_ERR_ARG;     // parity mode needs lo parts for q/k/v AND dO
     if (a.NT > 1) {                                                 // column tiles of a wide row
-        const int rcw = s3w_bwd_launch(a, g->dim_head, lo_mode, lds_q, lds_kv, stream);
+        const int rcw = s3w_bwd_launch(a, g->dim_head, lo_mode, lds_q, lds_kv, keep, drop_s, stream);
         if (rcw) return rcw;
-    } else if (g->dim_head == 64) { if (lo_mode) S3B(64, true); else S3B(64, false); }
-    else { if (lo_mode) S3B(32, true); else S3B(32, false); }
+    } else if (keep) {
+        if (g->dim_head == 64) { if (lo_mode) S3B(64, true, true); else S3B(64, false, true); }
+        else { if (lo_mode) S3B(32, true, true); else S3B(32, false, true); }
+    } else if (g->dim_head == 64) { if (lo_mode) S3B(64, true, false); else S3B(64, false, false); }
+    else { if (lo_mode) S3B(32, true, false); else S3B(32, false, false); }
 #undef S3B
     LAUNCH_CHECK();
     hipLaunchKernelGGL(s3_bwd_fin_kernel, dim3(g->B * (((int)inner + 63) / 64) + (g->heads * g->heads + 15) / 16), dim3(1024), 0, stream, a, g->dim_head);
@@ -2964,6 +3040,29 @@ extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* 
         if (rc2) return rc2;
     }
     return AMDNUWA_OK;
+}
+
+extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                                      const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo,
+                                      uint16_t* dq, uint16_t* dk, uint16_t* dv, uint16_t* dq_lo, uint16_t* dk_lo,
+                                      uint16_t* dv_lo, int ldd, float* dw_th, int accumulate, void* workspace,
+                                      size_t workspace_bytes, hipStream_t stream) {
+    return s3_bwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, dO, dO_lo, lddo, dq, dk, dv, dq_lo, dk_lo, dv_lo, ldd, dw_th, accumulate,
+                      workspace, workspace_bytes, nullptr, 1.f, stream);
+}
+
+extern "C" int amdnuwa_sparse3dna_bwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                           const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                                           const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo,
+                                           uint16_t* dq, uint16_t* dk, uint16_t* dv, uint16_t* dq_lo, uint16_t* dk_lo,
+                                           uint16_t* dv_lo, int ldd, float* dw_th, int accumulate, void* workspace,
+                                           size_t workspace_bytes, const uint8_t* keep, float drop_scale, hipStream_t stream) {
+    const int rc = drop_geom(g, k_lo != nullptr);
+    if (rc) return rc;
+    if (!drop_args_ok(keep, drop_scale)) return AMDNUWA_ERR_ARG;
+    return s3_bwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, dO, dO_lo, lddo, dq, dk, dv, dq_lo, dk_lo, dv_lo, ldd, dw_th, accumulate,
+                      workspace, workspace_bytes, keep, drop_scale, stream);
 }
 
 // fp16-gradient form of the backward ('bf16x3-fwd' with block class 's' of AMDNUWA_BWD_F16): q / k / v are the fp16 copies the forward core
@@ -3055,7 +3154,7 @@ extern "C" int amdnuwa_cross2dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q
     a.q = q; a.ql = q_lo; a.ld = ldq; a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th;
     const bool lo_mode = k_lo != nullptr;
     const size_t lds = s3_lds(g, lo_mode).fwd;
-    if (a.NT > 1) return s3w_fwd_launch(a, g->dim_head, lo_mode, lds, stream);
+    if (a.NT > 1) return s3w_fwd_launch(a, g->dim_head, lo_mode, lds, nullptr, 1.f, stream);
     dim3 grid(g->B * g->F * g->H), block(block_threads(g));
 #define S3F(DH_, LO_)                                                                                             \
     do {                                                                                                          \
@@ -3112,7 +3211,7 @@ extern "C" int amdnuwa_cross2dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q
         hipLaunchKernelGGL((s3_bwd_kv_kernel<DH_, LO_>), grid_kv, block, lds_kv, stream, a);                      \
     } while (0)
     if (a.NT > 1) {
-        const int rcw = s3w_bwd_launch(a, g->dim_head, lo_mode, lds_q, lds_kv, stream);
+        const int rcw = s3w_bwd_launch(a, g->dim_head, lo_mode, lds_q, lds_kv, nullptr, 1.f, stream);
         if (rcw) return rcw;
     } else if (g->dim_head == 64) { if (lo_mode) S3XB(64, true); else S3XB(64, false); }
     else { if (lo_mode) S3XB(32, true); else S3XB(32, false); }

@@ -133,8 +133,8 @@ __device__ __forceinline__ void scores_softmax_w(const S3Args& a, const TilePos&
     __syncthreads();
 }
 
-template <int DH, bool LO>
-__global__ __launch_bounds__(512, 4) void s3w_fwd_kernel(S3Args a) {
+template <int DH, bool LO, bool DROP = false>      // DROP: attention dropout, as in s3_fwd_kernel
+__global__ __launch_bounds__(512, 4) void s3w_fwd_kernel(S3KArgs<DROP> a) {
     constexpr int CH = DH / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int J = a.kf * a.kh * a.kw + 1;
@@ -178,6 +178,14 @@ __global__ __launch_bounds__(512, 4) void s3w_fwd_kernel(S3Args a) {
             for (int hh = 0; hh < 8; ++hh) s += (g < a.NH && hh < a.NH ? wsh[g * a.NH + hh] : 0.f) * pv[hh];
             out[g] = s;
         }
+        if constexpr (DROP) {
+            const int iq = 1 + p.ry * a.W + p.w0 + item / J;
+            if (iq < a.ntok) {
+                const uint8_t* kp = a.keep + (((size_t)p.b * (a.ntok - 1) + (iq - 1)) * J + item % J) * a.NH;
+#pragma unroll
+                for (int g = 0; g < 8; ++g) if (g < a.NH) out[g] *= keep_factor(kp[g], a.drop_s);
+            }
+        }
 #pragma unroll
         for (int g = 0; g < 8; ++g) if (g < a.NH) SP[item * a.NH + g] = out[g];
     }
@@ -211,8 +219,8 @@ __global__ __launch_bounds__(512, 4) void s3w_fwd_kernel(S3Args a) {
     }
 }
 
-template <int DH, bool LO>
-__global__ __launch_bounds__(512, 4) void s3w_bwd_q_kernel(S3Args a) {
+template <int DH, bool LO, bool DROP = false>      // DROP: attention dropout, as in s3_bwd_q_kernel
+__global__ __launch_bounds__(512, 4) void s3w_bwd_q_kernel(S3KArgs<DROP> a) {
     constexpr int CH = DH / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int J = a.kf * a.kh * a.kw + 1;
@@ -267,21 +275,23 @@ __global__ __launch_bounds__(512, 4) void s3w_bwd_q_kernel(S3Args a) {
         }
     }
     scores_softmax_w<DH, LO>(a, p, w, wt, h, c, act, qvalid, qf, qp, SP, st_hi, J);
-    // P' = mix(P) -> global (needed by bwd_kv); P stays in SP
-    for (int item = t; item < nit; item += blockDim.x) {
-        const int wq = item / J, j = item % J;
-        const int iq = 1 + p.ry * a.W + p.w0 + wq;
-        float pv[8];
+    // P' = mix(P) -> global (needed by bwd_kv); P stays in SP  (DROP: P'' instead, formed after the dO.V sweep below)
+    if constexpr (!DROP) {
+        for (int item = t; item < nit; item += blockDim.x) {
+            const int wq = item / J, j = item % J;
+            const int iq = 1 + p.ry * a.W + p.w0 + wq;
+            float pv[8];
 #pragma unroll
-        for (int hh = 0; hh < 8; ++hh) pv[hh] = hh < a.NH ? SP[item * a.NH + hh] : 0.f;
-        if (iq < a.ntok) {
-            float* dst = a.pm + (((size_t)b * nq + (iq - 1)) * J + j) * a.NH;
+            for (int hh = 0; hh < 8; ++hh) pv[hh] = hh < a.NH ? SP[item * a.NH + hh] : 0.f;
+            if (iq < a.ntok) {
+                float* dst = a.pm + (((size_t)b * nq + (iq - 1)) * J + j) * a.NH;
 #pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                float s = 0.f;
+                for (int g = 0; g < 8; ++g) {
+                    float s = 0.f;
 #pragma unroll
-                for (int hh = 0; hh < 8; ++hh) s += (g < a.NH && hh < a.NH ? wsh[g * a.NH + hh] : 0.f) * pv[hh];
-                if (g < a.NH) dst[g] = s;
+                    for (int hh = 0; hh < 8; ++hh) s += (g < a.NH && hh < a.NH ? wsh[g * a.NH + hh] : 0.f) * pv[hh];
+                    if (g < a.NH) dst[g] = s;
+                }
             }
         }
     }
@@ -312,6 +322,31 @@ __global__ __launch_bounds__(512, 4) void s3w_bwd_q_kernel(S3Args a) {
         if (c == 0) DP[(wt * J + j) * a.NH + h] = s;
     });
     __syncthreads();
+    if constexpr (DROP) {
+        // P'' = keep . mix(P) . s -> global (what bwd_kv takes dV with) and dP' = keep . dP'' . s: one mask byte per entry, read here
+        for (int item = t; item < nit; item += blockDim.x) {
+            const int wq = item / J, j = item % J;
+            const int iq = 1 + p.ry * a.W + p.w0 + wq;
+            float pv[8];
+#pragma unroll
+            for (int hh = 0; hh < 8; ++hh) pv[hh] = hh < a.NH ? SP[item * a.NH + hh] : 0.f;
+            if (iq < a.ntok) {
+                const size_t ci = (((size_t)b * nq + (iq - 1)) * J + j) * a.NH;
+#pragma unroll
+                for (int g = 0; g < 8; ++g) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int hh = 0; hh < 8; ++hh) s += (g < a.NH && hh < a.NH ? wsh[g * a.NH + hh] : 0.f) * pv[hh];
+                    if (g < a.NH) {
+                        const float kf_ = keep_factor(a.keep[ci + g], a.drop_s);
+                        a.pm[ci + g] = s * kf_;
+                        DP[item * a.NH + g] *= kf_;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
     // dW_th[g][h] partial = sum_{wt,j} dP'[g] * P[h]   (thread = (g,h) pair x item groups)
     {
         const int pair = t & 63, grp = t >> 6, ng = blockDim.x >> 6;
@@ -371,6 +406,7 @@ __global__ __launch_bounds__(512, 4) void s3w_bwd_q_kernel(S3Args a) {
         const float d0 = DP[(wt * J + 0) * a.NH + h];
         float pm0 = 0.f;                                        // P'[wt][0][g = h] = sum_hh Wth[h][hh] P[wt][0][hh]
         for (int hh = 0; hh < a.NH; ++hh) pm0 += wsh[h * a.NH + hh] * SP[(wt * J + 0) * a.NH + hh];
+        if constexpr (DROP) pm0 *= keep_factor(a.keep[((size_t)b * nq + (i - 1)) * J * a.NH + h], a.drop_s);
 #pragma unroll
         for (int e = 0; e < CH; ++e) {
             const float qe = LO ? qf[e] : ((e & 1) ? hi_f(qp[e >> 1]) : lo_f(qp[e >> 1]));
@@ -498,33 +534,39 @@ int tile_threads(const S3Args& a) { return ((a.TW * a.NH * 4 + 63) / 64) * 64; }
 
 }  // namespace
 
-int s3w_fwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds, hipStream_t stream) {
+int s3w_fwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds, const uint8_t* keep, float drop_s, hipStream_t stream) {
     const dim3 grid((unsigned)((size_t)a.B * a.F * a.H * a.NT)), block(tile_threads(a));
-#define S3WF(DH_, LO_)                                                                                            \
+#define S3WF(DH_, LO_, DR_)                                                                                          \
     do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3w_fwd_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((s3w_fwd_kernel<DH_, LO_>), grid, block, lds, stream, a);                              \
+        (void)hipFuncSetAttribute((const void*)s3w_fwd_kernel<DH_, LO_, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((s3w_fwd_kernel<DH_, LO_, DR_>), grid, block, lds, stream, s3_kargs<DR_>(a, keep, drop_s)); \
     } while (0)
-    if (dim_head == 64) { if (lo) S3WF(64, true); else S3WF(64, false); }
-    else { if (lo) S3WF(32, true); else S3WF(32, false); }
+    if (keep) {
+        if (dim_head == 64) { if (lo) S3WF(64, true, true); else S3WF(64, false, true); }
+        else { if (lo) S3WF(32, true, true); else S3WF(32, false, true); }
+    } else if (dim_head == 64) { if (lo) S3WF(64, true, false); else S3WF(64, false, false); }
+    else { if (lo) S3WF(32, true, false); else S3WF(32, false, false); }
 #undef S3WF
     LAUNCH_CHECK();
     return AMDNUWA_OK;
 }
 
 // query side over the B*F*H*NT (query row, tile) workgroups, then the key side over the B*FK*H*NT (key row, tile) ones
-int s3w_bwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds_q, size_t lds_kv, hipStream_t stream) {
+int s3w_bwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds_q, size_t lds_kv, const uint8_t* keep, float drop_s, hipStream_t stream) {
     const dim3 grid_q((unsigned)((size_t)a.B * a.F * a.H * a.NT)), grid_kv((unsigned)((size_t)a.B * a.FK * a.H * a.NT)), block(tile_threads(a));
-#define S3WB(DH_, LO_)                                                                                            \
+#define S3WB(DH_, LO_, DR_)                                                                                          \
     do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3w_bwd_q_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q); \
-        hipLaunchKernelGGL((s3w_bwd_q_kernel<DH_, LO_>), grid_q, block, lds_q, stream, a);                        \
+        (void)hipFuncSetAttribute((const void*)s3w_bwd_q_kernel<DH_, LO_, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q); \
+        hipLaunchKernelGGL((s3w_bwd_q_kernel<DH_, LO_, DR_>), grid_q, block, lds_q, stream, s3_kargs<DR_>(a, keep, drop_s)); \
         LAUNCH_CHECK();                                                                                           \
         (void)hipFuncSetAttribute((const void*)s3w_bwd_kv_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv); \
         hipLaunchKernelGGL((s3w_bwd_kv_kernel<DH_, LO_>), grid_kv, block, lds_kv, stream, a);                     \
     } while (0)
-    if (dim_head == 64) { if (lo) S3WB(64, true); else S3WB(64, false); }
-    else { if (lo) S3WB(32, true); else S3WB(32, false); }
+    if (keep) {
+        if (dim_head == 64) { if (lo) S3WB(64, true, true); else S3WB(64, false, true); }
+        else { if (lo) S3WB(32, true, true); else S3WB(32, false, true); }
+    } else if (dim_head == 64) { if (lo) S3WB(64, true, false); else S3WB(64, false, false); }
+    else { if (lo) S3WB(32, true, false); else S3WB(32, false, false); }
 #undef S3WB
     LAUNCH_CHECK();
     return AMDNUWA_OK;

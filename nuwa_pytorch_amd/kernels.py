@@ -1076,14 +1076,41 @@ def s3_f16_supported(g):
     return bool(_lib.lib().amdnuwa_s3_f16_supported(C.byref(g)))
 
 
+def s3_drop_supported(g, lo=None):
+    """do the masked (attention dropout) forms of the window kernels take this geometry in the current precision mode?"""
+    lo = (get_precision() != 'bf16') if lo is None else lo
+    return bool(_lib.lib().amdnuwa_s3_drop_supported(C.byref(g), 1 if lo else 0))
+
+
+def _s3_keep(g, keep, drop_scale):
+    """the keep mask of sparse3dna_fwd / _bwd as the uint8 [B, ntok - 1, J, heads] array the kernels read"""
+    J = g.kf * g.kh * g.kw + 1
+    if tuple(keep.shape) != (g.B, g.ntok - 1, J, g.heads) or keep.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f'keep must be bool / uint8 [B, ntok - 1, J, heads] = {(g.B, g.ntok - 1, J, g.heads)}, got {keep.dtype} {tuple(keep.shape)}')
+    keep = keep.contiguous()
+    return keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+
+
 @_family('s3', _s3_work('fwd'))
-def sparse3dna_fwd(g, qkv, wth, rel_bias=None, o_f16=False):
+def sparse3dna_fwd(g, qkv, wth, rel_bias=None, o_f16=False, keep=None, drop_scale=1.0):
     """qkv: BF [B*ntok, 3*inner] (q | k | v);  returns o BF [B*ntok, inner].  rel_bias: fp32 [J, heads] or None.
-    o_f16 (fp16 operand form only): o = BF(bf16 copy, None, fp16 copy) -- the operand of the two-MFMA to_out product"""
+    o_f16 (fp16 operand form only): o = BF(bf16 copy, None, fp16 copy) -- the operand of the two-MFMA to_out product.
+    keep (attention dropout): bool / uint8 [B, ntok - 1, J, heads], nonzero = keep, with drop_scale = 1 / (1 - p): the masked forms of the
+    VALU kernels (bf16 or hi + lo operands; the fp16 operand form has none)"""
     L = _lib.lib()
     g.rel_bias, g.d_rel_bias = _p(rel_bias), None
     inner = g.heads * g.dim_head
     R = g.B * g.ntok
+    if keep is not None:
+        if qkv.f16 is not None or qkv.hi is None:
+            raise RuntimeError('sparse3dna_fwd: the masked window kernels take bf16 or hi + lo operands, not the fp16 form')
+        k8 = _s3_keep(g, keep, drop_scale)
+        o = empty_bf((R, inner), qkv.hi.device, lo=qkv.lo is not None)
+        q, k, v = (view(qkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
+        check(L.amdnuwa_sparse3dna_fwd_drop(C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
+                                            _p(wth), _p(o.hi), _p(o.lo), inner, _p(k8), float(drop_scale), _stream()),
+              'amdnuwa_sparse3dna_fwd_drop')
+        return o
     if qkv.f16 is not None:            # fp16 operand form: single fp16 MFMAs; output hi + lo, or (o_f16) a bf16 copy + an fp16 copy
         q16, k16, v16 = (qkv.f16[:, i * inner:(i + 1) * inner] for i in range(3))
         dev = qkv.f16.device
@@ -1130,9 +1157,9 @@ def sparse3dna_bwd16(g, qkv16, wth, dO16, s2):
 
 
 @_family('s3', _s3_work('bwd'))
-def sparse3dna_bwd(g, qkv, wth, dO, rel_bias=None):
+def sparse3dna_bwd(g, qkv, wth, dO, rel_bias=None, keep=None, drop_scale=1.0):
     """returns (dqkv BF [R, 3*inner], dw_th fp32 [h, h]) -- and d(rel_bias) fp32 [J, heads] as a third item when rel_bias is given
-    (callers that pass rel_bias=None through the keyword get a 3-tuple with None)"""
+    (callers that pass rel_bias=None through the keyword get a 3-tuple with None).  keep / drop_scale: the forward's (sparse3dna_fwd)"""
     L = _lib.lib()
     drel = torch.empty_like(rel_bias) if rel_bias is not None else None
     g.rel_bias, g.d_rel_bias = _p(rel_bias), _p(drel)
@@ -1145,10 +1172,17 @@ def sparse3dna_bwd(g, qkv, wth, dO, rel_bias=None):
     dq, dk, dv = (view(dqkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
     nb = L.amdnuwa_sparse3dna_bwd_workspace_bytes(C.byref(g))
     ws = workspace(nb, dev)
-    check(L.amdnuwa_sparse3dna_bwd(C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
-                                   _p(wth), _p(dO.hi), _p(dO.lo), dO.hi.stride(0), _p(dq.hi), _p(dk.hi), _p(dv.hi),
-                                   _p(dq.lo), _p(dk.lo), _p(dv.lo), dqkv.hi.stride(0), _p(dwth), 0, _p(ws), nb, _stream()),
-          'amdnuwa_sparse3dna_bwd')
+    if keep is not None:
+        k8 = _s3_keep(g, keep, drop_scale)
+        check(L.amdnuwa_sparse3dna_bwd_drop(C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
+                                            _p(wth), _p(dO.hi), _p(dO.lo), dO.hi.stride(0), _p(dq.hi), _p(dk.hi), _p(dv.hi),
+                                            _p(dq.lo), _p(dk.lo), _p(dv.lo), dqkv.hi.stride(0), _p(dwth), 0, _p(ws), nb, _p(k8),
+                                            float(drop_scale), _stream()), 'amdnuwa_sparse3dna_bwd_drop')
+    else:
+        check(L.amdnuwa_sparse3dna_bwd(C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
+                                       _p(wth), _p(dO.hi), _p(dO.lo), dO.hi.stride(0), _p(dq.hi), _p(dk.hi), _p(dv.hi),
+                                       _p(dq.lo), _p(dk.lo), _p(dv.lo), dqkv.hi.stride(0), _p(dwth), 0, _p(ws), nb, _stream()),
+              'amdnuwa_sparse3dna_bwd')
     g.d_rel_bias = None
     return dqkv, dwth, drel
 

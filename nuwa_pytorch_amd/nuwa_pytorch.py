@@ -538,11 +538,15 @@ class Sparse3DNA(nn.Module):
         return p
 
     def _meta(self, B, n, device, **_):
-        if self.training and self.dropout.p > 0:
-            raise NotImplementedError('dropout inside Sparse3DNA is not supported (never enabled by Transformer, quirk Q14)')
         assert n - 1 <= self.max_num_tokens, 'sequence longer than the video shape allows'
         g = K.s3_geom(B, n, self.video_shape, self.kernel_size, self.dilation, self.heads, self.dim_head, causal=self.causal)
-        return dict(kind='s3', cache=self._cache, geom=g)
+        meta = dict(kind='s3', cache=self._cache, geom=g)
+        if self.training and self.dropout.p > 0:
+            # attention dropout in training (np.py:558): the masked window kernels (ops.S3Inner draws the mask from torch's RNG stream).  Causal
+            # window only -- the symmetric one keeps its PyTorch-op formulation (_hip_ok); an unsupported geometry raises from the library
+            assert self.causal
+            meta['drop_p'] = float(self.dropout.p)
+        return meta
 
     def _hip_ok(self):
         """geometry the 3DNA kernels take: head size 32 / 64, up to 8 heads, feature maps up to 64 wide (rows of more than 128 / heads

@@ -202,9 +202,15 @@ def block_plan(kind, R, D, p, meta, has_resid=False, ln=True):
     return plan(R, D, p, meta, has_resid, ln) if plan is not None else Plan()
 
 
+def _attn_keep_mask(B, nq, J, heads, p, device):
+    """keep mask of the nn.Dropout(p) on the window attention map (np.py:558, 748), in the kernels' [B, query, slot, head] order (torch's RNG
+    stream; tests replace this function by a fixed mask)"""
+    return torch.rand((B, nq, J, heads), device=device) >= p
+
+
 class S3Inner:
     """to_q/to_kv -> Sparse3DNA core -> to_out (np.py:481-613).  params: to_q.w, to_kv.w, talking_heads.w,
-    to_out.w, to_out.b"""
+    to_out.w, to_out.b.  meta['drop_p'] (attention dropout in training): the masked window kernels; the mask is saved for the backward"""
     nparams = 5
 
     @staticmethod
@@ -240,6 +246,10 @@ class S3Inner:
         's'): that, the two-MFMA to_out, no relative-position bias, and the band kernels and the five backward products take the shapes"""
         wq, wkv, wo = S3Inner.guarded(p)
         g, inner = meta['geom'], wq.shape[0]
+        if meta.get('drop_p'):
+            # live attention dropout: the masked core is the VALU window kernels on bf16 hi[/lo] operands -- no fp16 core (and so no fp16
+            # projections around it), no band kernels (the entry points never pick them under a mask), no fp16-gradient backward
+            return Plan(guarded=(wq, wkv, wo))
         a16 = bool(meta.get('shift') is None and K.qkv_f16() and K.s3_f16_supported(g) and K.gemm_nt_f16ops_ok(R, 3 * inner, D, out_bf16=True) and
                    f16_weights_ok(wq, wkv))
         core16 = a16 or bool(K.cores_f16() and K.want_lo() and K.s3_f16_supported(g))
@@ -270,6 +280,11 @@ class S3Inner:
         else:       # core16: q / k / v leave the 3-MFMA projection as a bf16 copy (backward) + an fp16 copy, and the core runs single fp16 MFMAs
             h = _f16_to_pair(h)
             qkv = K.gemm_nt(h, W['qkv'], out_bf16=True, shift=meta.get('shift'), out_f16=pl.core16)
+        drop_p = float(meta.get('drop_p') or 0.0)
+        if drop_p:              # attn_dropout > 0 in training (np.py:558, 748): nn.Dropout on the mixed attention map, inside the core
+            keep = _attn_keep_mask(g.B, g.ntok - 1, g.kf * g.kh * g.kw + 1, g.heads, drop_p, qkv.hi.device)
+            o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel, keep=keep, drop_scale=1.0 / (1.0 - drop_p))
+            return K.gemm_nt(o, W['out'], bias=bo.detach(), out_bf16=_fast()), (*_sv(h, qkv, o), keep)
         # two-MFMA to_out (o16): the fp16 core hands its output over as a bf16 copy (backward) + an fp16 copy (this product's A operand)
         o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel, o_f16=pl.o16)
         y = K.gemm_nt_f16x2(o.f16, W['out_16'], bias=bo.detach()) if pl.o16 else K.gemm_nt(o, W['out'], bias=bo.detach(), out_bf16=_fast())
@@ -277,7 +292,8 @@ class S3Inner:
 
     @staticmethod
     def bwd(saved, dy, p, meta, need_dbias=True, dy_f32=None):
-        h, qkv, o = saved
+        h, qkv, o = saved[:3]
+        keep = saved[3] if len(saved) > 3 else None          # attention dropout: the keep mask of the forward
         W = S3Inner.weights(meta['cache'], p)
         wq, wkv, wth, wo, bo = p[:5]
         rel = p[5].detach().contiguous() if len(p) > 5 else None
@@ -297,7 +313,8 @@ class S3Inner:
         d_o = K.gemm_nt(dy, W['outT'], out_bf16=True)
         dwo = torch.empty_like(wo)
         K.gemm_tn(dy, o, dwo)
-        dqkv, dwth, drel = K.sparse3dna_bwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), d_o, rel_bias=rel)
+        dqkv, dwth, drel = K.sparse3dna_bwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), d_o, rel_bias=rel, keep=keep,
+                                            drop_scale=1.0 / (1.0 - float(meta['drop_p'])) if keep is not None else 1.0)
         dh = K.gemm_nt(dqkv, W['qkvT'], out_bf16=_fast_bwd())
         sh = meta.get('shift')
         dwqkv = torch.empty((3 * inner, wq.shape[1]), dtype=torch.float32, device=wq.device)   # one wgrad GEMM for [to_q; to_kv]

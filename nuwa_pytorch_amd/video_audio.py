@@ -74,9 +74,17 @@ class SparseCausal2DNA(nn.Module):
     # the same attention IS a Sparse3DNA over a (time, 1, 1) grid with kernel (k, 1, 1) and the per-tap bias: it runs on the
     # libamdnuwa 3DNA kernels (to_qkv split into the q / kv halves they expect; to_out has no bias -> zeros), stand-alone through
     # ops.InnerFn or, inside a SandwichNorm, as the inner stage of the fused block node
+    def _drop_p(self):
+        """the rate of the live attention dropout (np.py:748), 0 in eval mode"""
+        return float(self.dropout.p) if self.training and self.dropout.p > 0 else 0.
+
     def _hip_ok(self):
-        return self.use_hip and self.dim_head in (32, 64) and self.heads <= 8 and self.kernel_size[0] > 1 and \
-            not (self.training and self.dropout.p > 0)
+        ok = self.use_hip and self.dim_head in (32, 64) and self.heads <= 8 and self.kernel_size[0] > 1
+        if ok and self._drop_p():
+            # live attention dropout: the masked forms of the window kernels (whether they take the window does not depend on the length)
+            from . import kernels as K
+            return K.s3_drop_supported(K.s3_geom(1, 2, (1, 1, 1), (self.kernel_size[0], 1, 1), (self.dilation[0], 1, 1), self.heads, self.dim_head))
+        return ok
 
     def _params(self):
         h, inner = self.heads, self.heads * self.dim_head
@@ -89,15 +97,16 @@ class SparseCausal2DNA(nn.Module):
     def _meta(self, B, n, device, **_):
         from . import kernels as K
         g = K.s3_geom(B, n, (max(n - 1, 1), 1, 1), (self.kernel_size[0], 1, 1), (self.dilation[0], 1, 1), self.heads, self.dim_head)
-        return dict(kind='s3', cache=self._cache, geom=g)
+        meta = dict(kind='s3', cache=self._cache, geom=g)
+        if self._drop_p():          # ops.S3Inner draws the keep mask from torch's RNG stream and runs the masked window kernels
+            meta['drop_p'] = self._drop_p()
+        return meta
 
     def _forward_hip(self, x):
         return ops.InnerFn.apply(x, None, self._meta(x.shape[0], x.shape[1], x.device), *self._params())
 
     def forward(self, x, **kwargs):
         b, n, h = x.shape[0], x.shape[1], self.heads
-        if self.training and self.dropout.p > 0:
-            raise NotImplementedError('attention dropout inside SparseCausal2DNA is not built')
         if x.is_cuda and self._hip_ok():
             return self._forward_hip(x)
         q, k, v = self.to_qkv(x).chunk(3, dim=-1)
@@ -116,7 +125,7 @@ class SparseCausal2DNA(nn.Module):
         sim = sim.masked_fill(~ok[None, None], NEG)
         sim0 = einsum('b h i d, b h d -> b h i', qa, k[:, :, 0])[..., None]      # <bos> key, no bias, never masked
         attn = torch.cat((sim0, sim), dim=-1).softmax(dim=-1, dtype=torch.float32)
-        attn = einsum('g h, b h i j -> b g i j', self.talking_heads.weight.reshape(h, h), attn)
+        attn = self.dropout(einsum('g h, b h i j -> b g i j', self.talking_heads.weight.reshape(h, h), attn))      # np.py:747-748
         out = einsum('b h i j, b h i j d -> b h i d', attn[..., 1:], vg) + attn[..., :1] * v[:, :, :1]
         out = torch.cat((v[:, :, :1], out), dim=2)                               # <bos> row: its own value
         return self.to_out(out.permute(0, 2, 1, 3).reshape(b, n, -1))
@@ -164,9 +173,8 @@ class CrossModalityCrossAttention(nn.Module):
             batch * min(-(-n_queries // 64), -(-n_keys // 64)) >= self.long_wgs_min
 
     def forward(self, seq, context, mask=None, context_mask=None):
-        if self.training and self.dropout.p > 0:
-            raise NotImplementedError('attention dropout inside CrossModalityCrossAttention is not built')
         b, n_in, dim = seq.shape
+        live_dropout = self.training and self.dropout.p > 0       # the cross-attention kernels take no mask: the PyTorch-op formulation below
         c, cc, h = self.chunk_size, self.context_chunk_size, self.heads
         body = seq[:, 1:] if self.has_start_token else seq
         s_len = body.shape[1]
@@ -183,7 +191,8 @@ class CrossModalityCrossAttention(nn.Module):
             return torch.zeros_like(seq)
         qf = self.norm(body[:, :nf * c].reshape(b, nf, c, dim))
         cf = self.context_norm(ctx[:, :nf * cc].reshape(b, nf, cc, -1))
-        if self.use_hip and seq.is_cuda and self.dim_head in (32, 64) and h <= 8 and (cc + 1 <= 288 or self._long_hip_ok(b * nf, c, cc)):
+        if self.use_hip and not live_dropout and seq.is_cuda and self.dim_head in (32, 64) and h <= 8 and \
+                (cc + 1 <= 288 or self._long_hip_ok(b * nf, c, cc)):
             # every (sample, frame) pair is one sample of the libamdnuwa cross-attention kernels (null k/v, key mask, talking heads) -- of
             # the linear-memory cattn kernels when a context frame has more rows than those take;
             # the Conv3d BIAS adds bias[g] to every attention weight, i.e. bias[g] * (null_v[g] + sum_j v_j[g]) to the head output
@@ -216,7 +225,7 @@ class CrossModalityCrossAttention(nn.Module):
         if exists(cmask):
             km = F.pad(cmask[:, :nf * cc].reshape(b, nf, cc), (1, 0), value=True)                # the null key is always visible
             sim = sim.masked_fill(~km[:, None, :, None, :], NEG)
-        attn = sim.softmax(dim=-1, dtype=torch.float32)
+        attn = self.dropout(sim.softmax(dim=-1, dtype=torch.float32))        # np.py:1048-1051: dropout BEFORE the talking-heads Conv3d here
         attn = einsum('g h, b h f i j -> b g f i j', self.talking_heads.weight.reshape(h, h), attn) + \
             self.talking_heads.bias[None, :, None, None, None]
         out = einsum('b h f i j, b h f j d -> b h f i d', attn, v)
