@@ -74,6 +74,8 @@ const char* amdnuwa_error_string(int code);
  *   key 25 batched narrow TN (N <= 64, 128 < M <= 384: the cross attention's dK / dV): 1 = 128-row tiles instead of one workgroup per batch element,
  *          2 = always through the split-K reduction (no direct store of a one-split result), 3 = the general whole-M kernel also where the lean
  *          form applies (whole 32-row K-steps per split, plane offsets below 4 GiB: gemm_tn_wmf_kernel, bit-identical results)
+ *   key 26 Sparse3DNA attention dropout (amdnuwa_sparse3dna_fwd_drop / _bwd_drop) at the geometry of the MFMA band kernels: 1 = keep the masked
+ *          VALU window kernels there (0 = the masked band kernels, as the unmasked calls)
  * (keys run 0..31; the K-step 64 form of the 256x256 ring stages full 128-byte DMA lines in two 64 KiB stages, `auto` uses it for
  *  1024 <= K < 2048; any non-zero key 0 disables the few-row weight-streaming path that M <= 32 normally takes) */
 int amdnuwa_set_tuning(int key, int value);
@@ -386,10 +388,15 @@ int amdnuwa_sparse3dna_bwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, 
  * P'' = keep . P' . drop_scale, and the backward takes dP' = keep . (dO . V^T) . drop_scale; everything below dP' is amdnuwa_sparse3dna_bwd's.
  * keep: uint8 [B][ntok - 1][J][heads], the index order of the ds / P' workspace, nonzero = keep (the caller draws it; the same array goes to the
  * forward and to the backward); drop_scale = 1 / (1 - p), finite and >= 1.  Slots hidden by the causal padding ignore the mask; the <bos>
- * query row still outputs its own value row.  An all-ones mask with drop_scale = 1 gives the bits of amdnuwa_sparse3dna_fwd / _bwd.
- * Runs the VALU window kernels (row and column-tiled, bf16 and hi + lo operands), never the MFMA band kernels: every geometry
- * amdnuwa_s3_supported() takes, causal only (g->noncausal: AMDNUWA_ERR_UNSUPPORTED) -- amdnuwa_s3_drop_supported().  keep == NULL or a
- * drop_scale that is not finite or < 1: AMDNUWA_ERR_ARG.  The backward uses the workspace of amdnuwa_sparse3dna_bwd_workspace_bytes(). */
+ * query row still outputs its own value row.  An all-ones mask with drop_scale = 1 gives the bits of amdnuwa_sparse3dna_fwd / _bwd, at every
+ * geometry: a masked call runs the masked form of the kernel the unmasked call picks under exactly the same conditions -- the MFMA band kernels
+ * (16-wide grid, 8 heads x 64, kw <= 3, bf16 operands; also with a relative-position bias and d_rel_bias, which put the backward on the fp32
+ * workspace) and the VALU window kernels (row and column-tiled, bf16 and hi + lo operands) everywhere else.  Tuning key 26 = 1 keeps the VALU
+ * kernels at band geometry (A/B runs).  The recomputing key side (tuning key 4 = 4) rebuilds P' from statistics and knows no mask: a masked call
+ * takes the workspace key side whatever that key says.  Every geometry amdnuwa_s3_supported() takes, causal only (g->noncausal:
+ * AMDNUWA_ERR_UNSUPPORTED) -- amdnuwa_s3_drop_supported().  keep == NULL or a drop_scale that is not finite or < 1: AMDNUWA_ERR_ARG; the band
+ * kernels read the 8 mask bytes of a (query, slot) as one word, so at band geometry a keep that is not 8-byte aligned is AMDNUWA_ERR_ARG too.
+ * The backward uses the workspace of amdnuwa_sparse3dna_bwd_workspace_bytes(). */
 int amdnuwa_s3_drop_supported(const amdnuwa_s3_geom* g, int lo_operands);
 int amdnuwa_sparse3dna_fwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
                                 const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
@@ -401,6 +408,19 @@ int amdnuwa_sparse3dna_bwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, con
                                 uint16_t* dk, uint16_t* dv, uint16_t* dq_lo, uint16_t* dk_lo, uint16_t* dv_lo, int ldd,
                                 float* dw_th, int accumulate, void* workspace, size_t workspace_bytes, const uint8_t* keep,
                                 float drop_scale, amdnuwa_stream stream);
+/* The same mask in the fp16 operand forms (additive at ABI 21): the arguments of amdnuwa_sparse3dna_fwd_f16 / amdnuwa_sparse3dna_bwd_f16 plus keep
+ * and drop_scale, with the meaning above (keep 8-byte aligned).  Geometry of amdnuwa_s3_f16_supported() / amdnuwa_sparse3dna_bwd_f16_supported(),
+ * AMDNUWA_ERR_UNSUPPORTED otherwise; keep == NULL or a drop_scale that is not finite or < 1: AMDNUWA_ERR_ARG, before the device is touched.  All
+ * three output forms of the forward (o + o_lo, o + fp16 o_lo, fp16 o_lo alone).  In the backward the 0 / 1 of the mask is applied before dP'
+ * leaves for fp16 and drop_scale in fp32 behind it, so the fp16 range of dP' (|S dO| . 2^-6) and the saturation counter are those of the unmasked
+ * call.  An all-ones mask with drop_scale = 1 gives the bits of the unmasked calls. */
+int amdnuwa_sparse3dna_fwd_f16_drop(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16, int ld,
+                                    const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, const uint8_t* keep,
+                                    float drop_scale, amdnuwa_stream stream);
+int amdnuwa_sparse3dna_bwd_f16_drop(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16, int ld,
+                                    const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16, uint16_t* dv_f16,
+                                    int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace, size_t workspace_bytes,
+                                    const uint8_t* keep, float drop_scale, amdnuwa_stream stream);
 
 /* SparseCross2DNA (np.py:761-901): NUWASketch's decoder cross-attention.  Queries = the video rows q [B*ntok, ldq] (row 0 of every
  * sample is <bos>); keys / values = the sketch context k, v [B*ctx_rows, ldkv], ctx_rows = g->kf * H * W (g->kf = sketch frames).

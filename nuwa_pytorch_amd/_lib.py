@@ -115,6 +115,8 @@ SIGNATURES = {
     'amdnuwa_s3_drop_supported': (I, [SG, I]),
     'amdnuwa_sparse3dna_fwd_drop': (I, [SG, P, P, P, P, P, P, I, P, P, P, I, P, F, P]),
     'amdnuwa_sparse3dna_bwd_drop': (I, [SG, P, P, P, P, P, P, I, P, P, P, I, P, P, P, P, P, P, I, P, I, P, SZ, P, F, P]),
+    'amdnuwa_sparse3dna_fwd_f16_drop': (I, [SG, P, P, P, I, P, P, P, I, I, P, F, P]),
+    'amdnuwa_sparse3dna_bwd_f16_drop': (I, [SG, P, P, P, I, P, P, I, P, P, P, I, P, I, P, P, SZ, P, F, P]),
     'amdnuwa_cross2dna_fwd': (I, [SG, P, P, I, I, P, P, P, P, I, P, P, P, P, P, P, P, P, I, P]),
     'amdnuwa_cross2dna_bwd_workspace_bytes': (SZ, [SG]),
     'amdnuwa_cross2dna_bwd': (I, [SG, P, P, I, I, P, P, P, P, I, P, P, P, P, P, P, P, P, I, P, P, I, P, P, P, P, I, P, P, P, P, SZ, P]),

@@ -834,6 +834,12 @@ __device__ __forceinline__ void lds_store8_done(float* p, const float (&v)[8]) {
 #endif
 }
 
+// Attention dropout in the band kernels (their DROP forms): the 8 mask bytes of one (query, slot) item are one aligned 8-byte load (4 bytes
+// for a lane that owns 4 heads); head g's byte selects the factor s or exactly 0.  `item` = ((b * nq + query) * J + slot).
+__device__ __forceinline__ uint2 s3m_keep8(const uint8_t* keep, size_t item) { return *reinterpret_cast<const uint2*>(keep + item * S3M_NH); }
+__device__ __forceinline__ bool s3m_kept(uint2 m, int g) { return (((g < 4 ? m.x : m.y) >> (8 * (g & 3))) & 0xffu) != 0u; }
+__device__ __forceinline__ bool s3m_kept(uint32_t m, int g) { return ((m >> (8 * g)) & 0xffu) != 0u; }
+
 // fills pslot / ptok (thread 0) and returns after a barrier; `cnt` = &pslot[S3M_PLANES]
 __device__ __forceinline__ void rowm_planes(const S3Args& a, int f, int y, int* pslot, int* ptok) {
     // closed form, one thread per plane (was a serial loop of thread 0): taps ta >= ta0 / tb >= tb0 reach a frame / row inside the grid
@@ -1274,8 +1280,9 @@ __device__ __forceinline__ void rowm_softmax(float* TAB, int J, float* gst = nul
 
 // F16: a.q / a.k / a.v hold fp16 values, the score and apply products run on the fp16 MFMA, and o leaves as a bf16 hi + lo pair
 // (a.ol): the forward Sparse3DNA core of the 'bf16x3-fwd' precision mode.
-template <bool F16>
-__global__ __launch_bounds__(512, 2) void s3_fwd_mfma_kernel(S3Args a) {
+// DROP: P'' = keep . P' . s is formed in the head-mix pass (one 8-byte mask load per item of a query that exists)
+template <bool F16, bool DROP = false>
+__global__ __launch_bounds__(512, 2) void s3_fwd_mfma_kernel(S3KArgs<DROP> a) {
     constexpr int NH = S3M_NH, DH = S3M_DH, W = S3M_W;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int J = a.kf * a.kh * a.kw + 1;
@@ -1329,6 +1336,14 @@ __global__ __launch_bounds__(512, 2) void s3_fwd_mfma_kernel(S3Args a) {
             for (int hh = 0; hh < 8; ++hh) s += wr[g * NH + hh] * pv[hh];
             S3_MIX_PIN_ASM(s);                   // (one head at a time: see lds_store8_done)
             out[g] = s;
+        }
+        if constexpr (DROP) {
+            const int wq = (int)(((float)item + 0.5f) * (1.f / (float)J)), iq = 1 + ry * W + wq;
+            if (iq < a.ntok) {                   // (an absent query has no mask row)
+                const uint2 m = s3m_keep8(a.keep, ((size_t)b * (a.ntok - 1) + (iq - 1)) * J + (item - wq * J));
+#pragma unroll
+                for (int g = 0; g < 8; ++g) out[g] = s3m_kept(m, g) ? out[g] * a.drop_s : 0.f;
+            }
         }
         lds_store8_done(SP + ib, out);
     }
@@ -1794,8 +1809,10 @@ __device__ __forceinline__ void tile_band_apply_fast(const S3Args& a, const Tile
     }
 }
 
-template <int ROWS, bool F16, bool BIAS>      // BIAS: a.bias != NULL (the relative-position bias of cfg 5; compiled out of the training kernels otherwise)
-__global__ __launch_bounds__(512, ROWS >= 4 ? 1 : 2) void s3_fwd_tile_kernel(S3Args a) {
+// BIAS: a.bias != NULL (the relative-position bias of cfg 5; compiled out of the training kernels otherwise)
+// DROP: P'' = keep . P' . s is formed in the head-mix pass (one 8-byte mask load per item of a query that exists)
+template <int ROWS, bool F16, bool BIAS, bool DROP = false>
+__global__ __launch_bounds__(512, ROWS >= 4 ? 1 : 2) void s3_fwd_tile_kernel(S3KArgs<DROP> a) {
     constexpr int NH = S3M_NH, DH = S3M_DH, W = S3M_W;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int J = a.kf * a.kh * a.kw + 1, WTS = W * s3m_ts(J);
@@ -1859,6 +1876,14 @@ __global__ __launch_bounds__(512, ROWS >= 4 ? 1 : 2) void s3_fwd_tile_kernel(S3A
             S3_MIX_PIN_ASM(s);                   // (one head at a time: see lds_store8_done)
             out[g] = s;
         }
+        if constexpr (DROP) {
+            const int wq = (int)(((float)item + 0.5f) * rJ), iq = 1 + (ry0 + i * a.dh) * W + wq;
+            if (iq < a.ntok) {                   // (an absent query has no mask row)
+                const uint2 m = s3m_keep8(a.keep, ((size_t)b * (a.ntok - 1) + (iq - 1)) * J + (item - wq * J));
+#pragma unroll
+                for (int g = 0; g < 8; ++g) out[g] = s3m_kept(m, g) ? out[g] * a.drop_s : 0.f;
+            }
+        }
         lds_store8_done(SP + ib, out);
     }
     __syncthreads();
@@ -1898,8 +1923,12 @@ __global__ __launch_bounds__(512, ROWS >= 4 ? 1 : 2) void s3_fwd_tile_kernel(S3A
 // LDS: R1 = SP (P) until ds exists, then the 8 transposed K tiles | DP | RED [8][64] | PM0 [W][NH]
 typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 constexpr float S3Q_DPS = 0.015625f;      // factor on dP' (and everything derived from it up to ds) in the fp16-gradient form: see the item pass
-template <bool BIAS, bool G16 = false>     // G16: the fp16-gradient form (S3Args::gs2)
-__global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      // (4 waves per SIMD = two workgroups per CU: <= 128 registers)
+// DROP (attention dropout): dP' = keep . (dO . V^T) . s in ONE pass over the DP table right behind the band sweep that writes it (nothing is added to
+// the mixing loops), and every place that forms P' for the key side and for PM0 forms P'' = keep . P' . s; the key side reads P'' where it read P'.
+// G16 + DROP: the table pass selects 0 or 1 only, so what the saturating fp16 conversion of dP' sees is the unmasked form's range (|S dO| . 2^-6);
+// s rides in fp32 on the constant that takes the S3Q_DPS factor back (`dps_back`: ds pass and dW_th reduction).
+template <bool BIAS, bool G16 = false, bool DROP = false>     // G16: the fp16-gradient form (S3Args::gs2)
+__global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3KArgs<DROP> a) {      // (4 waves per SIMD = two workgroups per CU: <= 128 registers)
     constexpr int NH = S3M_NH, DH = S3M_DH, W = S3M_W, inner = NH * DH;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int J = a.kf * a.kh * a.kw + 1, TS = s3m_ts(J), nsp = W * TS;
@@ -1953,6 +1982,27 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      
     float* gst = a.stats ? a.stats + ((size_t)b * nq + (size_t)ry * W) * NH * 4 : nullptr;
     const int wvalid = a.ntok - 1 - ry * W;                                                 // queries of this row that exist
     if (!(a.dbg & 64)) rowm_softmax(SP, J, gst, wvalid, BIAS ? 1.f : a.scale);             // P   (more probe bits of key 17: 64 no softmax, 128 no item pass, 256 no ds pass, 512 no pack pass, 1024 no <bos> partials, 2048 no table init)
+    [[maybe_unused]] float dps_back = 1.f / S3Q_DPS;                                                        // G16: takes the S3Q_DPS factor on dP' back (DROP: and applies s, in fp32)
+    if constexpr (DROP) {
+        dps_back *= a.drop_s;
+        // dP' = keep . dP'' . s over the DP table: a thread owns whole items (the softmax above touches SP only, so the barrier below serves both).
+        // Entries of absent queries and of slots behind the causal padding hold 0 and stay 0; an absent query has no mask row and reads none.
+        const float sdp = G16 ? 1.f : a.drop_s;
+        for (int item = t; item < W * J; item += blockDim.x) {
+            const int wq = (int)(((float)item + 0.5f) * rJ), iq = 1 + ry * W + wq;
+            if (iq < a.ntok) {
+                const uint2 m = s3m_keep8(a.keep, ((size_t)b * nq + (iq - 1)) * J + (item - wq * J));
+                const int ib = item * NH + wq * S3M_PAD;
+                float4 d0 = *reinterpret_cast<const float4*>(DP + ib), d1 = *reinterpret_cast<const float4*>(DP + ib + 4);
+                d0.x = s3m_kept(m, 0) ? d0.x * sdp : 0.f; d0.y = s3m_kept(m, 1) ? d0.y * sdp : 0.f;
+                d0.z = s3m_kept(m, 2) ? d0.z * sdp : 0.f; d0.w = s3m_kept(m, 3) ? d0.w * sdp : 0.f;
+                d1.x = s3m_kept(m, 4) ? d1.x * sdp : 0.f; d1.y = s3m_kept(m, 5) ? d1.y * sdp : 0.f;
+                d1.z = s3m_kept(m, 6) ? d1.z * sdp : 0.f; d1.w = s3m_kept(m, 7) ? d1.w * sdp : 0.f;
+                *reinterpret_cast<float4*>(DP + ib) = d0;
+                *reinterpret_cast<float4*>(DP + ib + 4) = d1;
+            }
+        }
+    }
     __syncthreads();
     // ONE pass over the (query, slot) items, all 8 heads of an item in the thread's registers (tuning key 19 = 1 restores the three
     // separate passes it replaces):
@@ -2019,7 +2069,7 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      
         for (int i = 0; i < 4; ++i) tw[i] = CW[i] + __shfl(CW[i], (lane + 40) & 63, 64);
         if (n16 < 8 && kg < 2) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) RED[wv * 64 + (4 * kg + i) * NH + n16] = tw[i] * (1.f / S3Q_DPS);
+            for (int i = 0; i < 4; ++i) RED[wv * 64 + (4 * kg + i) * NH + n16] = tw[i] * dps_back;
         }
         __syncthreads();
         if (t < NH * NH) {
@@ -2074,6 +2124,13 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      
                 }
                 if (half == 0) {
                     if (!a.packed) {
+                        if constexpr (DROP) {              // P'' = keep . P' . s (the mask is loaded here, behind the mix: nothing live across it)
+                            if (iq < a.ntok) {
+                                const uint2 m = s3m_keep8(a.keep, ((size_t)b * nq + (iq - 1)) * J + j);
+#pragma unroll
+                                for (int g = 0; g < 8; ++g) res[g] = s3m_kept(m, g) ? res[g] * a.drop_s : 0.f;
+                            }
+                        }
                         if (iq < a.ntok && !gst && !(a.dbg & 2)) {
                             float4* dst = reinterpret_cast<float4*>(a.pm + (((size_t)b * nq + (iq - 1)) * J + j) * NH);
                             dst[0] = make_float4(res[0], res[1], res[2], res[3]);
@@ -2125,11 +2182,14 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      
     #pragma unroll
             for (int hh = 0; hh < 8; ++hh) pv[hh] = SP[item * NH + wq * S3M_PAD + hh];
             float* dst = a.pm + (((size_t)b * nq + (iq - 1)) * J + j) * NH;
+            [[maybe_unused]] uint2 km = make_uint2(0u, 0u);
+            if constexpr (DROP) { if (iq < a.ntok) km = s3m_keep8(a.keep, ((size_t)b * nq + (iq - 1)) * J + j); }
     #pragma unroll
             for (int g = 0; g < 8; ++g) {
                 float s = 0.f;
     #pragma unroll
                 for (int hh = 0; hh < 8; ++hh) s += wr[g * NH + hh] * pv[hh];
+                if constexpr (DROP) s = s3m_kept(km, g) ? s * a.drop_s : 0.f;       // P''
                 if (iq < a.ntok && !gst && !(a.dbg & 2)) dst[g] = s;
                 if (j == 0) PM0[wq * NH + g] = iq < a.ntok ? s : 0.f;
             }
@@ -2202,7 +2262,7 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      
                 if (j < J) {
                     const int idx = w * TS + j * NH + h;
                     float dsv = pv[k] * (dv[k] - d);
-                    if constexpr (G16) { dsv *= 1.f / S3Q_DPS; ds_amax = fmaxf(ds_amax, fabsf(dsv)); dsv = f16_clamp(dsv); }
+                    if constexpr (G16) { dsv *= dps_back; ds_amax = fmaxf(ds_amax, fabsf(dsv)); dsv = f16_clamp(dsv); }
                     DP[idx] = dsv;
                     if (i < a.ntok && !gst && !a.packed && !(a.dbg & 2)) a.ds[(((size_t)b * nq + (i - 1)) * J + j) * NH + h] = dsv;
                 }
@@ -2215,7 +2275,7 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      
         for (int j = cc; j < J; j += 4) {
             const int idx = w * TS + j * NH + h;
             float dsv = SP[idx] * (DP[idx] - d);
-            if constexpr (G16) { dsv *= 1.f / S3Q_DPS; ds_amax = fmaxf(ds_amax, fabsf(dsv)); dsv = f16_clamp(dsv); }
+            if constexpr (G16) { dsv *= dps_back; ds_amax = fmaxf(ds_amax, fabsf(dsv)); dsv = f16_clamp(dsv); }
             DP[idx] = dsv;
             if (i < a.ntok && !gst && !a.packed) a.ds[(((size_t)b * nq + (i - 1)) * J + j) * NH + h] = dsv;
         }
@@ -2262,6 +2322,13 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      
             f32x4 pm = {0.f, 0.f, 0.f, 0.f};
             pm = __builtin_amdgcn_mfma_f32_16x16x16f16(aw_hi, pf, pm, 0, 0, 0);
             pm = __builtin_amdgcn_mfma_f32_16x16x16f16(aw_lo, pf, pm, 0, 0, 0);
+            if constexpr (DROP) {                                                 // P'' of the lane's 4 heads: the 4 mask bytes of heads 4 kh .. + 3
+                if (ok && iq < a.ntok) {
+                    const uint32_t m4 = *reinterpret_cast<const uint32_t*>(a.keep + (((size_t)b * nq + (iq - 1)) * J + j) * NH + 4 * kh);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) pm[i] = s3m_kept(m4, i) ? pm[i] * a.drop_s : 0.f;
+                }
+            }
             if (ok && j == 0) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) PM0[wq * NH + 4 * kh + i] = iq < a.ntok ? pm[i] : 0.f;
@@ -2294,6 +2361,8 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      
             const float pv[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
             const float dsv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
             uint32_t pw[8];
+            [[maybe_unused]] uint2 km = make_uint2(0u, 0u);
+            if constexpr (DROP) { if (iq < a.ntok) km = s3m_keep8(a.keep, ((size_t)b * nq + (iq - 1)) * J + j); }
 #pragma unroll
             for (int g = 0; g < 8; ++g) {
                 const float4 w0 = *reinterpret_cast<const float4*>(wv + g * NH), w1 = *reinterpret_cast<const float4*>(wv + g * NH + 4);
@@ -2301,6 +2370,7 @@ __global__ __launch_bounds__(512, 4) void s3_bwd_q_mfma_kernel(S3Args a) {      
                 float sm = 0.f;
 #pragma unroll
                 for (int hh = 0; hh < 8; ++hh) sm += wg[hh] * pv[hh];
+                if constexpr (DROP) sm = s3m_kept(km, g) ? sm * a.drop_s : 0.f;     // P''
                 if (j == 0) PM0[wq * NH + g] = iq < a.ntok ? sm : 0.f;
                 pw[g] = pack2_t<G16>(dsv[g], sm);                                 // low half: ds[head g], high half: P'[head g]  (G16: fp16 halves; ds was clamped in the ds pass)
             }
@@ -2801,15 +2871,15 @@ int s3_tile_rows(const amdnuwa_s3_geom* g) {
         if (g->dh > 0 && g->H % (g->dh * rws) == 0 && g->kf * (g->kh + rws - 1) <= S3T_MAXK) return rws;
     return 1;
 }
-template <bool F16>
-int s3_fwd_tile_launch(const S3Args& a, const amdnuwa_s3_geom* g, int tr, hipStream_t stream) {
+template <bool F16, bool DROP = false>
+int s3_fwd_tile_launch(const S3Args& a, const amdnuwa_s3_geom* g, int tr, hipStream_t stream, const uint8_t* keep = nullptr, float drop_s = 1.f) {
     const int J = g->kf * g->kh * g->kw + 1;
     const size_t lm = (size_t)tr * 16 * (J * 8 + 4) * sizeof(float) + 8 * 4096;
     const dim3 grid(g->B * g->F * (g->H / tr));
 #define S3T_LAUNCH(R_, B_)                                                                                        \
     do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3_fwd_tile_kernel<R_, F16, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); \
-        hipLaunchKernelGGL((s3_fwd_tile_kernel<R_, F16, B_>), grid, dim3(512), lm, stream, a);                    \
+        (void)hipFuncSetAttribute((const void*)s3_fwd_tile_kernel<R_, F16, B_, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); \
+        hipLaunchKernelGGL((s3_fwd_tile_kernel<R_, F16, B_, DROP>), grid, dim3(512), lm, stream, s3_kargs<DROP>(a, keep, drop_s)); \
     } while (0)
     if (tr == 4) { if (a.bias) S3T_LAUNCH(4, true); else S3T_LAUNCH(4, false); }
     else { if (a.bias) S3T_LAUNCH(2, true); else S3T_LAUNCH(2, false); }
@@ -2818,9 +2888,24 @@ int s3_fwd_tile_launch(const S3Args& a, const amdnuwa_s3_geom* g, int tr, hipStr
     return AMDNUWA_OK;
 }
 
+// the band forward (two-row tiles where H splits, else the one-row kernel); `a` is complete
+template <bool F16, bool DROP = false>
+int s3_fwd_band_launch(const S3Args& a, const amdnuwa_s3_geom* g, hipStream_t stream, const uint8_t* keep = nullptr, float drop_s = 1.f) {
+    const int tr = s3_tile_rows(g);
+    if (tr > 1) return s3_fwd_tile_launch<F16, DROP>(a, g, tr, stream, keep, drop_s);
+    const int J = g->kf * g->kh * g->kw + 1;
+    const size_t lm = (size_t)16 * (J * 8 + 4) * sizeof(float) + 8 * 4096;
+    (void)hipFuncSetAttribute((const void*)s3_fwd_mfma_kernel<F16, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm);
+    hipLaunchKernelGGL((s3_fwd_mfma_kernel<F16, DROP>), dim3(g->B * g->F * g->H), dim3(512), lm, stream, s3_kargs<DROP>(a, keep, drop_s));
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+// the band kernels read the 8 mask bytes of a (query, slot) item as one 8-byte word
+bool keep_aligned(const uint8_t* keep) { return (reinterpret_cast<uintptr_t>(keep) & 7u) == 0; }
+
 }  // namespace
 
-// the masked (attention dropout) forms: the causal window on the VALU kernels of either geometry (row / column tiles) and operand form
+// the masked (attention dropout) forms: the causal window on the kernels amdnuwa_sparse3dna_fwd / _bwd pick for the geometry and operand form
 static int drop_geom(const amdnuwa_s3_geom* g, bool lo) {
     const int rc = check_geom(g);
     if (rc) return rc;
@@ -2829,7 +2914,8 @@ static int drop_geom(const amdnuwa_s3_geom* g, bool lo) {
 }
 static bool drop_args_ok(const uint8_t* keep, float drop_scale) { return keep && std::isfinite(drop_scale) && drop_scale >= 1.f; }
 
-// keep == NULL: amdnuwa_sparse3dna_fwd.  keep != NULL: amdnuwa_sparse3dna_fwd_drop (the DROP forms of the VALU kernels, never the MFMA ones)
+// keep == NULL: amdnuwa_sparse3dna_fwd.  keep != NULL: amdnuwa_sparse3dna_fwd_drop (the DROP form of the kernel the unmasked call picks;
+// tuning key 26 = 1 keeps a masked call on the VALU kernels at band geometry too)
 static int s3_fwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
                       const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
                       const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, const uint8_t* keep, float drop_s, hipStream_t stream) {
@@ -2843,7 +2929,6 @@ static int s3_fwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_
     a.q = q; a.k = k; a.v = v; a.ql = q_lo; a.kl = k_lo; a.vl = v_lo; a.ld = ld;
     a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th;
     self_kv(a);
-    const int J = g->kf * g->kh * g->kw + 1;
     if ((k_lo != nullptr) && (!q_lo || !v_lo)) return AMDNUWA_ERR_ARG;
     // tuning key 3: 0 = one key row per staging round (measured faster: 4 resident workgroups per CU),
     //               1 = stage the kh rows of a tap frame at once (needs kh <= KHMAX)
@@ -2858,16 +2943,12 @@ static int s3_fwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_
     } while (0)
     const bool lo_mode = k_lo != nullptr;
     // MFMA forward (tuning key 3: 1 = keep the dot2 kernel): bf16 operands, 16 queries per grid row, 8 heads x 64
-    if (!keep && !lo_mode && !g->noncausal && !(g_amdnuwa_tuning[3] & 1) && g->W == 16 && g->heads == 8 && g->dim_head == 64 && g->kw <= S3M_KW &&
-        g->kf * g->kh <= S3M_PLANES && ld % 8 == 0 && ldo % 4 == 0) {
+    if (!(keep && g_amdnuwa_tuning[26] == 1) && !lo_mode && !g->noncausal && !(g_amdnuwa_tuning[3] & 1) && g->W == 16 && g->heads == 8 && g->dim_head == 64 &&
+        g->kw <= S3M_KW && g->kf * g->kh <= S3M_PLANES && ld % 8 == 0 && ldo % 4 == 0) {
         a.dbg = g_amdnuwa_tuning[9];
-        const int tr = s3_tile_rows(g);
-        if (tr > 1) return s3_fwd_tile_launch<false>(a, g, tr, stream);
-        const size_t lm = (size_t)16 * (J * 8 + 4) * sizeof(float) + 8 * 4096;
-        (void)hipFuncSetAttribute((const void*)s3_fwd_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm);
-        hipLaunchKernelGGL(s3_fwd_mfma_kernel<false>, grid, dim3(512), lm, stream, a);
-        LAUNCH_CHECK();
-        return AMDNUWA_OK;
+        if (!keep) return s3_fwd_band_launch<false>(a, g, stream);
+        if (!keep_aligned(keep)) return AMDNUWA_ERR_ARG;
+        return s3_fwd_band_launch<false, true>(a, g, stream, keep, drop_s);
     }
     if (keep) {
         if (g->dim_head == 64) { if (lo_mode) S3F(64, true, true); else S3F(64, false, true); }
@@ -2903,8 +2984,10 @@ static bool s3_mfma_geom(const amdnuwa_s3_geom* g) {
 }
 extern "C" int amdnuwa_s3_f16_supported(const amdnuwa_s3_geom* g) { return check_geom(g) == AMDNUWA_OK && s3_mfma_geom(g) ? 1 : 0; }
 
-extern "C" int amdnuwa_sparse3dna_fwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
-                                          int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, hipStream_t stream) {
+// keep == NULL: amdnuwa_sparse3dna_fwd_f16.  keep != NULL: amdnuwa_sparse3dna_fwd_f16_drop
+static int s3_fwd_f16_run(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
+                          int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, const uint8_t* keep, float drop_s,
+                          hipStream_t stream) {
     int rc = check_geom(g);
     if (rc) return rc;
     if (!s3_mfma_geom(g)) return AMDNUWA_ERR_UNSUPPORTED;
@@ -2917,16 +3000,21 @@ extern "C" int amdnuwa_sparse3dna_fwd_f16(const amdnuwa_s3_geom* g, const uint16
     a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0;
     a.dbg = g_amdnuwa_tuning[9];
     self_kv(a);
-    const int J = g->kf * g->kh * g->kw + 1;
-    {
-        const int tr = s3_tile_rows(g);
-        if (tr > 1) return s3_fwd_tile_launch<true>(a, g, tr, stream);
-    }
-    const size_t lm = (size_t)16 * (J * 8 + 4) * sizeof(float) + 8 * 4096;
-    (void)hipFuncSetAttribute((const void*)s3_fwd_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm);
-    hipLaunchKernelGGL(s3_fwd_mfma_kernel<true>, dim3(g->B * g->F * g->H), dim3(512), lm, stream, a);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    if (!keep) return s3_fwd_band_launch<true>(a, g, stream);
+    return s3_fwd_band_launch<true, true>(a, g, stream, keep, drop_s);
+}
+extern "C" int amdnuwa_sparse3dna_fwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
+                                          int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, hipStream_t stream) {
+    return s3_fwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, o, o_lo, ldo, o_lo_f16, nullptr, 1.f, stream);
+}
+extern "C" int amdnuwa_sparse3dna_fwd_f16_drop(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
+                                               int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16,
+                                               const uint8_t* keep, float drop_scale, hipStream_t stream) {
+    const int rc = check_geom(g);
+    if (rc) return rc;
+    if (!s3_mfma_geom(g)) return AMDNUWA_ERR_UNSUPPORTED;
+    if (!drop_args_ok(keep, drop_scale) || !keep_aligned(keep)) return AMDNUWA_ERR_ARG;
+    return s3_fwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, o, o_lo, ldo, o_lo_f16, keep, drop_scale, stream);
 }
 
 extern "C" int amdnuwa_s3_supported(const amdnuwa_s3_geom* g, int lo_operands) {
@@ -2943,8 +3031,8 @@ extern "C" size_t amdnuwa_sparse3dna_bwd_workspace_bytes(const amdnuwa_s3_geom* 
            amdnuwa_colsum_workspace_bytes((long long)g->B * nq, (int)(J * g->heads));
 }
 
-// keep == NULL: amdnuwa_sparse3dna_bwd.  keep != NULL: amdnuwa_sparse3dna_bwd_drop (the DROP form of the VALU query side; the key side is the
-// same kernel, it reads P'' where it read P')
+// keep == NULL: amdnuwa_sparse3dna_bwd.  keep != NULL: amdnuwa_sparse3dna_bwd_drop (the DROP form of the query side the unmasked call picks --
+// tuning key 26 = 1: of the VALU one at band geometry too; the key side is the same kernel, it reads P'' where it read P')
 static int s3_bwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
                       const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
                       const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo,
@@ -2981,12 +3069,14 @@ static int s3_bwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_
     const size_t lds_q = l.bq, lds_kv = l.bkv;
     dim3 grid((unsigned)rows), block(block_threads(g));
     // MFMA query-side kernel (tuning key 4: 1 = keep the dot2 kernel): bf16 operands, 16 queries per grid row, 8 heads x 64
-    const bool q_mfma = !keep && !has_lo && !dO_lo && !g->noncausal && g_amdnuwa_tuning[4] != 1 && g->W == 16 && g->heads == 8 && g->dim_head == 64 &&
+    const bool q_mfma = !(keep && g_amdnuwa_tuning[26] == 1) && !has_lo && !dO_lo && !g->noncausal && g_amdnuwa_tuning[4] != 1 && g->W == 16 && g->heads == 8 && g->dim_head == 64 &&
                         g->kw <= S3M_KW && g->kf * g->kh <= S3M_PLANES && ld % 8 == 0 && lddo % 8 == 0 && ldd % 4 == 0;
     // recomputing key side (tuning key 4 = 4; OFF by default: it removes the 3.9 GB workspace round trip -- backward traffic 2.85x ->
     // 1.5x algorithmic -- but runs 15-22 % slower: its per-plane head exchange serialises the eight waves and its 180 registers allow one
-    // workgroup per CU).  Needs the MFMA query side; d(rel_bias) is a column sum of the ds workspace.
-    const bool kv_rc = q_mfma && g_amdnuwa_tuning[4] == 4 && !g->d_rel_bias;
+    // workgroup per CU).  Needs the MFMA query side; d(rel_bias) is a column sum of the ds workspace.  It rebuilds P' from
+    // the statistics and knows no mask: a masked call takes the workspace key side whatever the key says.
+    if (q_mfma && keep && !keep_aligned(keep)) return AMDNUWA_ERR_ARG;
+    const bool kv_rc = q_mfma && g_amdnuwa_tuning[4] == 4 && !g->d_rel_bias && !keep;
     a.stats = kv_rc ? a.ds : nullptr;                                              // (lives where the workspace would: B*nq*NH*4 floats <= B*nq*J*NH)
     // packed (bf16 ds | bf16 P') workspace: MFMA query side + MFMA key side, no d(rel_bias) column sum over ds (tuning key 24 = 1: the fp32 pair)
     a.packed = (q_mfma && g_amdnuwa_tuning[4] != 2 && !g->d_rel_bias && g_amdnuwa_tuning[24] != 1 && !a.sep_passes) ? 1 : 0;
@@ -2995,11 +3085,11 @@ static int s3_bwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_
 #define S3B(DH_, LO_, DR_)                                                                                        \
     do {                                                                                                          \
         if (q_mfma && a.bias) {                                                                                   \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm); \
-            hipLaunchKernelGGL(s3_bwd_q_mfma_kernel<true>, grid, dim3(512), lds_qm, stream, a);                   \
+            (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<true, false, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm); \
+            hipLaunchKernelGGL((s3_bwd_q_mfma_kernel<true, false, DR_>), grid, dim3(512), lds_qm, stream, s3_kargs<DR_>(a, keep, drop_s)); \
         } else if (q_mfma) {                                                                                      \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm); \
-            hipLaunchKernelGGL(s3_bwd_q_mfma_kernel<false>, grid, dim3(512), lds_qm, stream, a);                  \
+            (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<false, false, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm); \
+            hipLaunchKernelGGL((s3_bwd_q_mfma_kernel<false, false, DR_>), grid, dim3(512), lds_qm, stream, s3_kargs<DR_>(a, keep, drop_s)); \
         } else {                                                                                                  \
             (void)hipFuncSetAttribute((const void*)s3_bwd_q_kernel<DH_, LO_, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q); \
             hipLaunchKernelGGL((s3_bwd_q_kernel<DH_, LO_, DR_>), grid, block, lds_q, stream, s3_kargs<DR_>(a, keep, drop_s)); \
@@ -3072,10 +3162,11 @@ extern "C" int amdnuwa_sparse3dna_bwd_drop(const amdnuwa_s3_geom* g, const uint1
 extern "C" int amdnuwa_sparse3dna_bwd_f16_supported(const amdnuwa_s3_geom* g) {
     return check_geom(g) == AMDNUWA_OK && s3_mfma_geom(g) && !g->rel_bias && !g->d_rel_bias ? 1 : 0;
 }
-extern "C" int amdnuwa_sparse3dna_bwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16, int ld,
-                                          const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16,
-                                          uint16_t* dv_f16, int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace,
-                                          size_t workspace_bytes, hipStream_t stream) {
+// keep == NULL: amdnuwa_sparse3dna_bwd_f16.  keep != NULL: amdnuwa_sparse3dna_bwd_f16_drop
+static int s3_bwd_f16_run(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16, int ld,
+                          const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16,
+                          uint16_t* dv_f16, int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace,
+                          size_t workspace_bytes, const uint8_t* keep, float drop_s, hipStream_t stream) {
     int rc = check_geom(g);
     if (rc) return rc;
     if (!amdnuwa_sparse3dna_bwd_f16_supported(g)) return AMDNUWA_ERR_UNSUPPORTED;
@@ -3103,8 +3194,13 @@ extern "C" int amdnuwa_sparse3dna_bwd_f16(const amdnuwa_s3_geom* g, const uint16
     const size_t nspm = (size_t)g->W * (J * g->heads + 4);
     const size_t lds_qm = (nspm * 4 > 8 * 4096 ? nspm * 4 : 8 * 4096) + nspm * 4 + (8 * 64 + 16 * 8) * 4 + 8 * 2048;
     const dim3 grid((unsigned)rows);
-    (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm);
-    hipLaunchKernelGGL((s3_bwd_q_mfma_kernel<false, true>), grid, dim3(512), lds_qm, stream, a);
+    if (keep) {
+        (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm);
+        hipLaunchKernelGGL((s3_bwd_q_mfma_kernel<false, true, true>), grid, dim3(512), lds_qm, stream, s3_kargs<true>(a, keep, drop_s));
+    } else {
+        (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm);
+        hipLaunchKernelGGL((s3_bwd_q_mfma_kernel<false, true>), grid, dim3(512), lds_qm, stream, a);
+    }
     LAUNCH_CHECK();
     (void)hipFuncSetAttribute((const void*)s3_bwd_kv_mfma_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 8192);
     hipLaunchKernelGGL((s3_bwd_kv_mfma_kernel<true, true>), grid, dim3(512), 8 * 8192, stream, a);
@@ -3112,6 +3208,24 @@ extern "C" int amdnuwa_sparse3dna_bwd_f16(const amdnuwa_s3_geom* g, const uint16
     hipLaunchKernelGGL(s3_bwd_fin_kernel, dim3(g->B * (((int)inner + 63) / 64) + (g->heads * g->heads + 15) / 16), dim3(1024), 0, stream, a, g->dim_head);
     LAUNCH_CHECK();
     return AMDNUWA_OK;
+}
+extern "C" int amdnuwa_sparse3dna_bwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16, int ld,
+                                          const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16,
+                                          uint16_t* dv_f16, int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace,
+                                          size_t workspace_bytes, hipStream_t stream) {
+    return s3_bwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, dO_f16, lddo, dq_f16, dk_f16, dv_f16, ldd, dw_th, accumulate, scale2, workspace,
+                          workspace_bytes, nullptr, 1.f, stream);
+}
+extern "C" int amdnuwa_sparse3dna_bwd_f16_drop(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16, int ld,
+                                               const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16,
+                                               uint16_t* dv_f16, int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace,
+                                               size_t workspace_bytes, const uint8_t* keep, float drop_scale, hipStream_t stream) {
+    const int rc = check_geom(g);
+    if (rc) return rc;
+    if (!amdnuwa_sparse3dna_bwd_f16_supported(g)) return AMDNUWA_ERR_UNSUPPORTED;
+    if (!drop_args_ok(keep, drop_scale) || !keep_aligned(keep)) return AMDNUWA_ERR_ARG;
+    return s3_bwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, dO_f16, lddo, dq_f16, dk_f16, dv_f16, ldd, dw_th, accumulate, scale2, workspace,
+                          workspace_bytes, keep, drop_scale, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1095,16 +1095,14 @@ def _s3_keep(g, keep, drop_scale):
 def sparse3dna_fwd(g, qkv, wth, rel_bias=None, o_f16=False, keep=None, drop_scale=1.0):
     """qkv: BF [B*ntok, 3*inner] (q | k | v);  returns o BF [B*ntok, inner].  rel_bias: fp32 [J, heads] or None.
     o_f16 (fp16 operand form only): o = BF(bf16 copy, None, fp16 copy) -- the operand of the two-MFMA to_out product.
-    keep (attention dropout): bool / uint8 [B, ntok - 1, J, heads], nonzero = keep, with drop_scale = 1 / (1 - p): the masked forms of the
-    VALU kernels (bf16 or hi + lo operands; the fp16 operand form has none)"""
+    keep (attention dropout): bool / uint8 [B, ntok - 1, J, heads], nonzero = keep, with drop_scale = 1 / (1 - p): the masked form of the
+    kernel the same call takes without a mask (band kernels in the bf16 and fp16 operand forms at their geometry, VALU kernels elsewhere)"""
     L = _lib.lib()
     g.rel_bias, g.d_rel_bias = _p(rel_bias), None
     inner = g.heads * g.dim_head
     R = g.B * g.ntok
-    if keep is not None:
-        if qkv.f16 is not None or qkv.hi is None:
-            raise RuntimeError('sparse3dna_fwd: the masked window kernels take bf16 or hi + lo operands, not the fp16 form')
-        k8 = _s3_keep(g, keep, drop_scale)
+    k8 = _s3_keep(g, keep, drop_scale) if keep is not None else None
+    if keep is not None and qkv.f16 is None:
         o = empty_bf((R, inner), qkv.hi.device, lo=qkv.lo is not None)
         q, k, v = (view(qkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
         check(L.amdnuwa_sparse3dna_fwd_drop(C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
@@ -1121,6 +1119,11 @@ def sparse3dna_fwd(g, qkv, wth, rel_bias=None, o_f16=False, keep=None, drop_scal
                    torch.empty((R, inner), dtype=torch.float16, device=dev))
         else:
             o = empty_bf((R, inner), dev, lo=True)
+        if keep is not None:
+            check(L.amdnuwa_sparse3dna_fwd_f16_drop(C.byref(g), _p(q16), _p(k16), _p(v16), qkv.f16.stride(0), _p(wth), _p(o.hi),
+                                                    _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _p(k8), float(drop_scale),
+                                                    _stream()), 'amdnuwa_sparse3dna_fwd_f16_drop')
+            return o
         check(L.amdnuwa_sparse3dna_fwd_f16(C.byref(g), _p(q16), _p(k16), _p(v16), qkv.f16.stride(0), _p(wth), _p(o.hi),
                                            _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _stream()), 'amdnuwa_sparse3dna_fwd_f16')
         return o
@@ -1136,9 +1139,9 @@ def s3_bwd16_supported(g):
 
 
 @_family('s3', _s3_work('bwd'))
-def sparse3dna_bwd16(g, qkv16, wth, dO16, s2):
+def sparse3dna_bwd16(g, qkv16, wth, dO16, s2, keep=None, drop_scale=1.0):
     """fp16-gradient form: qkv16 fp16 [R, 3*inner] (the forward's operands), dO16 = fp16(S dO) [R, inner], s2 = device {S, 1 / S};
-    returns (dqkv fp16 [R, 3*inner] = fp16(S dqkv), dw_th fp32 [h, h])"""
+    returns (dqkv fp16 [R, 3*inner] = fp16(S dqkv), dw_th fp32 [h, h]).  keep / drop_scale: the forward's (sparse3dna_fwd)"""
     L = _lib.lib()
     g.rel_bias, g.d_rel_bias = None, None
     inner = g.heads * g.dim_head
@@ -1150,6 +1153,12 @@ def sparse3dna_bwd16(g, qkv16, wth, dO16, s2):
     dq, dk, dv = (dqkv[:, i * inner:(i + 1) * inner] for i in range(3))
     nb = L.amdnuwa_sparse3dna_bwd_workspace_bytes(C.byref(g))
     ws = workspace(nb, dev)
+    if keep is not None:
+        k8 = _s3_keep(g, keep, drop_scale)
+        check(L.amdnuwa_sparse3dna_bwd_f16_drop(C.byref(g), _p(q), _p(k), _p(v), qkv16.stride(0), _p(wth), _p(dO16), dO16.stride(0),
+                                                _p(dq), _p(dk), _p(dv), dqkv.stride(0), _p(dwth), 0, _p(s2), _p(ws), nb, _p(k8),
+                                                float(drop_scale), _stream()), 'amdnuwa_sparse3dna_bwd_f16_drop')
+        return dqkv, dwth
     check(L.amdnuwa_sparse3dna_bwd_f16(C.byref(g), _p(q), _p(k), _p(v), qkv16.stride(0), _p(wth), _p(dO16), dO16.stride(0),
                                        _p(dq), _p(dk), _p(dv), dqkv.stride(0), _p(dwth), 0, _p(s2), _p(ws), nb, _stream()),
           'amdnuwa_sparse3dna_bwd_f16')

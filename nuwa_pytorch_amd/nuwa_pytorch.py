@@ -512,8 +512,8 @@ class Sparse3DNA(nn.Module):
         # the same per-head bias is applied to every sample)
         self.rel_pos_bias = AxialPositionalEmbedding(heads, shape=self.kernel_size) if rel_pos_bias else None
         self.video_shape = video_shape
-        max_frames, fmap_size, _ = video_shape
-        self.max_num_tokens = max_frames * fmap_size * fmap_size
+        max_frames, fmap_size, fmap_width = video_shape
+        self.max_num_tokens = max_frames * fmap_size * fmap_width        # (the reference squares fmap_size: the same number on its square maps)
         self.query_num_frames_chunk = default(query_num_frames_chunk, max_frames)
         if causal:
             self.register_buffer('mask', causal_neighbor_mask(video_shape, self.kernel_size, self.dilation))

@@ -210,7 +210,8 @@ def _attn_keep_mask(B, nq, J, heads, p, device):
 
 class S3Inner:
     """to_q/to_kv -> Sparse3DNA core -> to_out (np.py:481-613).  params: to_q.w, to_kv.w, talking_heads.w,
-    to_out.w, to_out.b.  meta['drop_p'] (attention dropout in training): the masked window kernels; the mask is saved for the backward"""
+    to_out.w, to_out.b.  meta['drop_p'] (attention dropout in training): the masked form of whatever core the plan picks; the mask is saved
+    for the backward (so RngReplay's recomputed forward and the backward read the same one)"""
     nparams = 5
 
     @staticmethod
@@ -246,9 +247,10 @@ class S3Inner:
         's'): that, the two-MFMA to_out, no relative-position bias, and the band kernels and the five backward products take the shapes"""
         wq, wkv, wo = S3Inner.guarded(p)
         g, inner = meta['geom'], wq.shape[0]
-        if meta.get('drop_p'):
-            # live attention dropout: the masked core is the VALU window kernels on bf16 hi[/lo] operands -- no fp16 core (and so no fp16
-            # projections around it), no band kernels (the entry points never pick them under a mask), no fp16-gradient backward
+        if meta.get('drop_p') and not K.s3_f16_supported(g):
+            # live attention dropout off the band geometry: the masked core is the VALU window kernels on bf16 hi[/lo] operands -- no fp16
+            # core (and so no fp16 projections around it), no fp16-gradient backward.  At band geometry the band kernels have masked forms in
+            # every operand form, and the block gets the plan it gets without dropout.
             return Plan(guarded=(wq, wkv, wo))
         a16 = bool(meta.get('shift') is None and K.qkv_f16() and K.s3_f16_supported(g) and K.gemm_nt_f16ops_ok(R, 3 * inner, D, out_bf16=True) and
                    f16_weights_ok(wq, wkv))
@@ -267,12 +269,19 @@ class S3Inner:
         g = meta['geom']
         rel = p[5].detach().contiguous() if len(p) > 5 else None          # [J, heads] relative-position bias (optional)
         pl = meta['plan']
+        # attn_dropout > 0 in training (np.py:558, 748): nn.Dropout on the mixed attention map, inside the core.  The mask rides behind the three
+        # saved tensors of every branch.
+        drop_p = float(meta.get('drop_p') or 0.0)
+        dev = h.f16.device if h.hi is None else h.hi.device
+        keep = _attn_keep_mask(g.B, g.ntok - 1, g.kf * g.kh * g.kw + 1, g.heads, drop_p, dev) if drop_p else None
+        dkw = dict(keep=keep, drop_scale=1.0 / (1.0 - drop_p)) if drop_p else {}
+        tail = (keep,) if drop_p else ()
         if pl.bwd16:
             # fp16-gradient backward: ONE (fp16) copy of h, of q / k / v and of the core's output
             qkv = K.BF(None, None, K.gemm_nt_f16ops(h.f16, W['qkv_16'], out_f16=True))
-            o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), o_f16='only')
+            o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), o_f16='only', **dkw)
             y = K.gemm_nt_f16x2(o.f16, W['out_16'], bias=bo.detach())
-            return y, (K.BF(None, None, h.f16), qkv, o)
+            return y, (K.BF(None, None, h.f16), qkv, o) + tail
         assert h.hi is not None, 'a bf16 backward needs the bf16 copy of the LayerNorm output'
         if pl.a16:
             h16 = h.f16 if h.f16 is not None else K.hilo_to_f16(h)
@@ -280,15 +289,10 @@ class S3Inner:
         else:       # core16: q / k / v leave the 3-MFMA projection as a bf16 copy (backward) + an fp16 copy, and the core runs single fp16 MFMAs
             h = _f16_to_pair(h)
             qkv = K.gemm_nt(h, W['qkv'], out_bf16=True, shift=meta.get('shift'), out_f16=pl.core16)
-        drop_p = float(meta.get('drop_p') or 0.0)
-        if drop_p:              # attn_dropout > 0 in training (np.py:558, 748): nn.Dropout on the mixed attention map, inside the core
-            keep = _attn_keep_mask(g.B, g.ntok - 1, g.kf * g.kh * g.kw + 1, g.heads, drop_p, qkv.hi.device)
-            o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel, keep=keep, drop_scale=1.0 / (1.0 - drop_p))
-            return K.gemm_nt(o, W['out'], bias=bo.detach(), out_bf16=_fast()), (*_sv(h, qkv, o), keep)
         # two-MFMA to_out (o16): the fp16 core hands its output over as a bf16 copy (backward) + an fp16 copy (this product's A operand)
-        o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel, o_f16=pl.o16)
+        o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel, o_f16=pl.o16, **dkw)
         y = K.gemm_nt_f16x2(o.f16, W['out_16'], bias=bo.detach()) if pl.o16 else K.gemm_nt(o, W['out'], bias=bo.detach(), out_bf16=_fast())
-        return y, _sv(h, qkv, o)
+        return y, tuple(_sv(h, qkv, o)) + tail
 
     @staticmethod
     def bwd(saved, dy, p, meta, need_dbias=True, dy_f32=None):
@@ -305,7 +309,8 @@ class S3Inner:
             d_o = K.gemm_nt_f16ops(dy.t, W['outT_16'], out_f16=True)
             dwo = torch.empty_like(wo)
             K.gemm_tn16(dy.t, o.f16, dwo, s2)
-            dqkv, dwth = K.sparse3dna_bwd16(g, qkv.f16, wth.detach().reshape(g.heads, g.heads).contiguous(), d_o, s2)
+            dqkv, dwth = K.sparse3dna_bwd16(g, qkv.f16, wth.detach().reshape(g.heads, g.heads).contiguous(), d_o, s2, keep=keep,
+                                            drop_scale=1.0 / (1.0 - float(meta['drop_p'])) if keep is not None else 1.0)
             dh = K.G16(K.gemm_nt_f16ops(dqkv, W['qkvT_16'], out_f16=True), s2)
             dwqkv = torch.empty((3 * inner, wq.shape[1]), dtype=torch.float32, device=wq.device)
             K.gemm_tn16(dqkv, h.f16, dwqkv, s2)
