@@ -1,6 +1,7 @@
 // Argument block and the lane-level helpers shared by the Sparse3DNA window kernels: the row kernels and the MFMA band kernels of
 // sparse3dna.hip, the column-tiled kernels of sparse3dna_wide.hip.  Everything here has internal linkage (one copy per translation unit).
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "../../include/amdnuwa.h"
 
@@ -68,6 +69,26 @@ inline S3Tile s3_tile(const amdnuwa_s3_geom* g) {
     if (halo > 65536) halo = 65536;                       // (far beyond any LDS: s3_lds_need refuses it, no kernel sees the clipped value)
     return {tw, nt, tw + (int)halo};
 }
+// key slots of a query: slot 0 (<bos>, or the null key of SparseCross2DNA) + the kf*kh*kw window taps
+inline size_t s3_slots(const amdnuwa_s3_geom* g) { return (size_t)g->kf * g->kh * g->kw + 1; }
+
+// One launch of a window kernel: its dynamic-LDS allowance (set on every launch), the launch, the launch check.
+template <class A>
+int s3_launch(void (*kernel)(A), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A& args) {
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args);
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+// Run-time choices as compile-time parameters: f(std::true_type{}) or f(std::false_type{}); s3_dispatch() hands f the template parameters
+// <DH, LO, DROP> of the VALU kernels as (std::integral_constant<int, 64 or 32>, bool constant, bool constant).
+template <class F> int s3_if(bool c, F&& f) { return c ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> int s3_dispatch(int dim_head, bool lo, bool drop, F&& f) {
+    return s3_if(dim_head == 64, [&](auto d64) { return s3_if(lo, [&](auto lo_c) { return s3_if(drop, [&](auto dr) {
+        return f(std::integral_constant<int, d64() ? 64 : 32>{}, lo_c, dr);
+    }); }); });
+}
+
 // launchers of the column-tiled kernels (sparse3dna_wide.hip); `a` is complete, a.NT > 1.  lds_* = dynamic LDS bytes of the launch.
 // keep != NULL launches the masked (DROP) forms of the forward and of the query-side backward
 int s3w_fwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds, const uint8_t* keep, float drop_s, hipStream_t stream);

@@ -713,7 +713,7 @@ constexpr size_t S3_LDS_MAX = 160 * 1024 - 2048;        // leaves room for the k
 struct S3Lds { size_t fwd, bq, bkv; };                  // dynamic LDS bytes of the forward, the query-side and the key-side backward
 S3Lds s3_lds(const amdnuwa_s3_geom* g, bool lo) {
     const S3Tile tl = s3_tile(g);
-    const size_t J = (size_t)g->kf * g->kh * g->kw + 1, inner = (size_t)g->heads * g->dim_head, tw = (size_t)tl.tw, sw = (size_t)tl.sw;
+    const size_t J = s3_slots(g), inner = (size_t)g->heads * g->dim_head, tw = (size_t)tl.tw, sw = (size_t)tl.sw;
     const size_t stage = sw * inner * (lo ? 4 : 2), nsp = tw * J * g->heads;
     // bwd_q: stage (hi + lo) + SP + DP + RED(8*64); the <bos> partial reduction reuses SP + DP: needs tw*inner <= 2*nsp floats
     size_t spdp = 2 * nsp;
@@ -2843,10 +2843,67 @@ __global__ __launch_bounds__(512, 2) void s3_bwd_kv_rc_mfma_kernel(S3Args a) {
     }
 }
 
-void fill_geom(S3Args& a, const amdnuwa_s3_geom* g) {
+// ------------------------------------------------------------------------------------------------
+// Host side.  s3_route() names the kernels of a call, s3_ws() lays the backward workspace out, s3_fwd_launch() / s3_bwd_launch() launch what
+// the route names; the entry points below them check their arguments (in the order of their return codes) and fill S3Args.
+// ------------------------------------------------------------------------------------------------
+
+// the geometry of the MFMA band kernels: the causal decoder window on a 16-wide grid, 8 heads x 64
+bool s3_mfma_geom(const amdnuwa_s3_geom* g) {
+    return !g->noncausal && g->W == 16 && g->heads == 8 && g->dim_head == 64 && g->kw <= S3M_KW && g->kf * g->kh <= S3M_PLANES;
+}
+// query rows per workgroup of the band forward (`want`: 0 = auto, 1 / 2 / 4 = forced where the geometry allows it): a tile is
+// ROWS rows of one residue class of y modulo the dilation, so H must split into dh * ROWS
+int s3_tile_rows(const amdnuwa_s3_geom* g, int want) {
+    if (want == 0) want = S3T_AUTO_ROWS;
+    for (int rws = want >= 4 ? 4 : (want >= 2 ? 2 : 1); rws > 1; rws >>= 1)
+        if (g->dh > 0 && g->H % (g->dh * rws) == 0 && g->kf * (g->kh + rws - 1) <= S3T_MAXK) return rws;
+    return 1;
+}
+
+// The route of a call: which kernels run.  The only reader of the Sparse3DNA tuning keys (include/amdnuwa.h), by these names:
+enum : int { S3K_FWD = 3,            // bit 0: forward on the VALU (dot2) kernel; bit 1: band workgroups in the old (f, y) order
+             S3K_BWD = 4,            // 1 = VALU kernels, 2 = band query side + VALU key side, 4 = band query side + recomputing band key side
+             S3K_TILE_ROWS = 16,     // query rows per workgroup of the band forward (s3_tile_rows)
+             S3K_SEP_PASSES = 19,    // 1 = the band query side runs its three item passes separately
+             S3K_WS_FP32 = 24,       // 1 = the band backward keeps the two fp32 workspace arrays instead of the packed words
+             S3K_DROP_VALU = 26 };   // 1 = a masked call stays on the VALU kernels at band geometry too
+enum S3Form { S3_BF16, S3_HILO, S3_F16 };                                    // operand form: bf16, hi + lo pairs, fp16
+enum S3KvSide { S3KV_VALU, S3KV_BAND_F32, S3KV_BAND_PACKED, S3KV_BAND_RC };  // key side: VALU, band on the fp32 pair / the packed words, recomputing band
+struct S3Route {
+    bool f16;                          // the fp16 forms of the band kernels
+    bool fwd_band; int tile_rows;      // forward: band kernel (tile_rows > 1: the tiled one) or VALU (row kernel; column tiles where NT > 1)
+    bool q_band; S3KvSide kv;          // backward: query side (band or VALU, as the forward) and key side
+    int packed, sep_passes, ymajor;    // the S3Args fields of those names
+};
+// masked = a keep mask is present; cross = SparseCross2DNA (the band kernels know no context grid).  d(rel_bias) is a column sum over the fp32
+// ds workspace, so a call that wants it takes neither the packed words nor the recomputing key side; that key side rebuilds P' from the
+// statistics and knows no mask either (OFF by default: no 3.9 GB workspace round trip, but 15-22 % slower).
+S3Route s3_route(const amdnuwa_s3_geom* g, S3Form form, bool masked, bool cross = false) {
+    const int* t = g_amdnuwa_tuning;
+    S3Route r{};
+    r.tile_rows = 1;
+    r.ymajor = (t[S3K_FWD] & 2) ? 0 : 1;
+    if (cross) return r;
+    if (form == S3_F16) {              // band kernels + packed workspace only (the entry points refuse every other geometry)
+        r.f16 = r.fwd_band = r.q_band = true; r.kv = S3KV_BAND_PACKED; r.packed = 1;
+    } else {
+        const bool band = form == S3_BF16 && s3_mfma_geom(g) && !(masked && t[S3K_DROP_VALU] == 1);
+        r.fwd_band = band && !(t[S3K_FWD] & 1);
+        r.q_band = band && t[S3K_BWD] != 1;
+        const bool kv_band = r.q_band && t[S3K_BWD] != 2;
+        r.sep_passes = t[S3K_SEP_PASSES] == 1;
+        r.packed = (kv_band && !g->d_rel_bias && t[S3K_WS_FP32] != 1 && !r.sep_passes) ? 1 : 0;
+        r.kv = !kv_band ? S3KV_VALU : (t[S3K_BWD] == 4 && !g->d_rel_bias && !masked) ? S3KV_BAND_RC : r.packed ? S3KV_BAND_PACKED : S3KV_BAND_F32;
+    }
+    if (r.fwd_band) r.tile_rows = s3_tile_rows(g, t[S3K_TILE_ROWS]);
+    return r;
+}
+
+void fill_geom(S3Args& a, const amdnuwa_s3_geom* g, const S3Route& r) {
     a.B = g->B; a.ntok = g->ntok; a.F = g->F; a.H = g->H; a.W = g->W; a.kf = g->kf; a.kh = g->kh; a.kw = g->kw;
     a.df = g->df; a.dh = g->dh; a.dw = g->dw; a.NH = g->heads; a.scale = g->scale; a.bias = g->rel_bias;
-    a.ymajor = (g_amdnuwa_tuning[3] & 2) ? 0 : 1;
+    a.ymajor = r.ymajor;
     // causal: every tap at or before the query (np.py:427); symmetric 'same' window otherwise (np.py:429)
     a.of = g->noncausal ? (g->kf - 1) / 2 : g->kf - 1;
     a.oh = g->noncausal ? (g->kh - 1) / 2 : g->kh - 1;
@@ -2862,276 +2919,212 @@ void self_kv(S3Args& a) {
 }
 int block_threads(const amdnuwa_s3_geom* g) { return ((g->W * g->heads * 4 + 63) / 64) * 64; }
 
-// query rows per workgroup of the MFMA kernels (tuning key 16: 0 = auto, 1 / 2 / 4 = forced where the geometry allows it): a tile is
-// ROWS rows of one residue class of y modulo the dilation, so H must split into dh * ROWS
-int s3_tile_rows(const amdnuwa_s3_geom* g) {
-    int want = g_amdnuwa_tuning[16];
-    if (want == 0) want = S3T_AUTO_ROWS;
-    for (int rws = want >= 4 ? 4 : (want >= 2 ? 2 : 1); rws > 1; rws >>= 1)
-        if (g->dh > 0 && g->H % (g->dh * rws) == 0 && g->kf * (g->kh + rws - 1) <= S3T_MAXK) return rws;
-    return 1;
+// The backward workspace, in floats from its start: ds and P' [B][nq][J][heads] (the recomputing key side keeps its statistics where ds would
+// be: B*nq*heads*4 floats), the per-workgroup partials of dW_th and of the <bos> / null dk and dv -- one per (query row, column tile) -- and
+// the column-sum scratch of d(rel_bias).  `bytes` is what amdnuwa_sparse3dna_bwd_workspace_bytes() reports.
+struct S3Ws { size_t ds, pm, part_th, part_k0, part_v0, colsum, bytes; };
+S3Ws s3_ws(const amdnuwa_s3_geom* g) {
+    const size_t nq = g->ntok - 1, items = (size_t)g->B * nq * s3_slots(g) * g->heads;
+    const size_t parts = (size_t)g->B * g->F * g->H * s3_tile(g).nt, inner = (size_t)g->heads * g->dim_head;
+    S3Ws w{};
+    w.pm = items; w.part_th = 2 * items; w.part_k0 = w.part_th + parts * g->heads * g->heads; w.part_v0 = w.part_k0 + parts * inner;
+    w.colsum = w.part_v0 + parts * inner;
+    w.bytes = w.colsum * sizeof(float) + 256 + amdnuwa_colsum_workspace_bytes((long long)g->B * nq, (int)(s3_slots(g) * g->heads));
+    return w;
 }
-template <bool F16, bool DROP = false>
-int s3_fwd_tile_launch(const S3Args& a, const amdnuwa_s3_geom* g, int tr, hipStream_t stream, const uint8_t* keep = nullptr, float drop_s = 1.f) {
-    const int J = g->kf * g->kh * g->kw + 1;
-    const size_t lm = (size_t)tr * 16 * (J * 8 + 4) * sizeof(float) + 8 * 4096;
-    const dim3 grid(g->B * g->F * (g->H / tr));
-#define S3T_LAUNCH(R_, B_)                                                                                        \
-    do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3_fwd_tile_kernel<R_, F16, B_, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm); \
-        hipLaunchKernelGGL((s3_fwd_tile_kernel<R_, F16, B_, DROP>), grid, dim3(512), lm, stream, s3_kargs<DROP>(a, keep, drop_s)); \
-    } while (0)
-    if (tr == 4) { if (a.bias) S3T_LAUNCH(4, true); else S3T_LAUNCH(4, false); }
-    else { if (a.bias) S3T_LAUNCH(2, true); else S3T_LAUNCH(2, false); }
-#undef S3T_LAUNCH
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+S3Ws bind_ws(S3Args& a, const amdnuwa_s3_geom* g, void* workspace) {
+    const S3Ws w = s3_ws(g);
+    float* ws = (float*)workspace;
+    a.ds = ws + w.ds; a.pm = ws + w.pm; a.part_th = ws + w.part_th; a.part_k0 = ws + w.part_k0; a.part_v0 = ws + w.part_v0;
+    return w;
 }
 
-// the band forward (two-row tiles where H splits, else the one-row kernel); `a` is complete
-template <bool F16, bool DROP = false>
-int s3_fwd_band_launch(const S3Args& a, const amdnuwa_s3_geom* g, hipStream_t stream, const uint8_t* keep = nullptr, float drop_s = 1.f) {
-    const int tr = s3_tile_rows(g);
-    if (tr > 1) return s3_fwd_tile_launch<F16, DROP>(a, g, tr, stream, keep, drop_s);
-    const int J = g->kf * g->kh * g->kw + 1;
-    const size_t lm = (size_t)16 * (J * 8 + 4) * sizeof(float) + 8 * 4096;
-    (void)hipFuncSetAttribute((const void*)s3_fwd_mfma_kernel<F16, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm);
-    hipLaunchKernelGGL((s3_fwd_mfma_kernel<F16, DROP>), dim3(g->B * g->F * g->H), dim3(512), lm, stream, s3_kargs<DROP>(a, keep, drop_s));
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
-}
+// the mask of a _drop entry point (the unmasked ones pass {}): on = 1 makes keep and drop_s arguments to check
+struct S3Mask { bool on; const uint8_t* keep; float s; };
 // the band kernels read the 8 mask bytes of a (query, slot) item as one 8-byte word
 bool keep_aligned(const uint8_t* keep) { return (reinterpret_cast<uintptr_t>(keep) & 7u) == 0; }
+bool mask_ok(const S3Mask& m, bool band) { return !m.on || (m.keep && std::isfinite(m.s) && m.s >= 1.f && (!band || keep_aligned(m.keep))); }
 
-}  // namespace
-
-// the masked (attention dropout) forms: the causal window on the kernels amdnuwa_sparse3dna_fwd / _bwd pick for the geometry and operand form
-static int drop_geom(const amdnuwa_s3_geom* g, bool lo) {
-    const int rc = check_geom(g);
-    if (rc) return rc;
-    if (s3_lds_need(g, lo) > S3_LDS_MAX || g->noncausal) return AMDNUWA_ERR_UNSUPPORTED;
-    return AMDNUWA_OK;
-}
-static bool drop_args_ok(const uint8_t* keep, float drop_scale) { return keep && std::isfinite(drop_scale) && drop_scale >= 1.f; }
-
-// keep == NULL: amdnuwa_sparse3dna_fwd.  keep != NULL: amdnuwa_sparse3dna_fwd_drop (the DROP form of the kernel the unmasked call picks;
-// tuning key 26 = 1 keeps a masked call on the VALU kernels at band geometry too)
-static int s3_fwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
-                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
-                      const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, const uint8_t* keep, float drop_s, hipStream_t stream) {
-    int rc = check_geom(g);
-    if (rc) return rc;
-    if (s3_lds_need(g, k_lo != nullptr) > S3_LDS_MAX) return AMDNUWA_ERR_UNSUPPORTED;
-    if (!q || !k || !v || !w_th || !o || ld % 8 || ldo % 8) return AMDNUWA_ERR_ARG;
-    if (g->B <= 0) return AMDNUWA_OK;
-    S3Args a{};
-    fill_geom(a, g);
-    a.q = q; a.k = k; a.v = v; a.ql = q_lo; a.kl = k_lo; a.vl = v_lo; a.ld = ld;
-    a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th;
-    self_kv(a);
-    if ((k_lo != nullptr) && (!q_lo || !v_lo)) return AMDNUWA_ERR_ARG;
-    // tuning key 3: 0 = one key row per staging round (measured faster: 4 resident workgroups per CU),
-    //               1 = stage the kh rows of a tap frame at once (needs kh <= KHMAX)
-    // (slab staging of a whole tap frame measured slower than row staging: retired)
-    const size_t lds = s3_lds(g, k_lo != nullptr).fwd;
-    if (a.NT > 1) return s3w_fwd_launch(a, g->dim_head, k_lo != nullptr, lds, keep, drop_s, stream);      // column tiles of a wide row
-    dim3 grid(g->B * g->F * g->H), block(block_threads(g));
-#define S3F(DH_, LO_, DR_)                                                                                        \
-    do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3_fwd_kernel<DH_, LO_, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((s3_fwd_kernel<DH_, LO_, DR_>), grid, block, lds, stream, s3_kargs<DR_>(a, keep, drop_s)); \
-    } while (0)
-    const bool lo_mode = k_lo != nullptr;
-    // MFMA forward (tuning key 3: 1 = keep the dot2 kernel): bf16 operands, 16 queries per grid row, 8 heads x 64
-    if (!(keep && g_amdnuwa_tuning[26] == 1) && !lo_mode && !g->noncausal && !(g_amdnuwa_tuning[3] & 1) && g->W == 16 && g->heads == 8 && g->dim_head == 64 &&
-        g->kw <= S3M_KW && g->kf * g->kh <= S3M_PLANES && ld % 8 == 0 && ldo % 4 == 0) {
-        a.dbg = g_amdnuwa_tuning[9];
-        if (!keep) return s3_fwd_band_launch<false>(a, g, stream);
-        if (!keep_aligned(keep)) return AMDNUWA_ERR_ARG;
-        return s3_fwd_band_launch<false, true>(a, g, stream, keep, drop_s);
+// the forward the route names; `a` is complete.  keep != NULL: its masked (DROP) form
+int s3_fwd_launch(const S3Args& a, const amdnuwa_s3_geom* g, const S3Route& r, bool lo, const uint8_t* keep, float drop_s, hipStream_t stream) {
+    if (!r.fwd_band) {
+        const size_t lds = s3_lds(g, lo).fwd;
+        if (a.NT > 1) return s3w_fwd_launch(a, g->dim_head, lo, lds, keep, drop_s, stream);              // column tiles of a wide row
+        return s3_dispatch(g->dim_head, lo, keep != nullptr, [&](auto dh, auto lo_c, auto dr) {
+            return s3_launch(s3_fwd_kernel<dh(), lo_c(), dr()>, dim3(g->B * g->F * g->H), dim3(block_threads(g)), lds, stream, s3_kargs<dr()>(a, keep, drop_s));
+        });
     }
-    if (keep) {
-        if (g->dim_head == 64) { if (lo_mode) S3F(64, true, true); else S3F(64, false, true); }
-        else { if (lo_mode) S3F(32, true, true); else S3F(32, false, true); }
-    } else if (g->dim_head == 64) { if (lo_mode) S3F(64, true, false); else S3F(64, false, false); }
-    else { if (lo_mode) S3F(32, true, false); else S3F(32, false, false); }
-#undef S3F
+    // band: tiles of tile_rows query rows where H splits, else the one-row kernel
+    const int tr = r.tile_rows;
+    const size_t lm = (size_t)tr * 16 * (s3_slots(g) * 8 + 4) * sizeof(float) + 8 * 4096;
+    const dim3 grid(g->B * g->F * (g->H / tr)), block(512);
+    return s3_if(r.f16, [&](auto f16) { return s3_if(keep != nullptr, [&](auto dr) {
+        const auto ka = s3_kargs<dr()>(a, keep, drop_s);
+        if (tr == 1) return s3_launch(s3_fwd_mfma_kernel<f16(), dr()>, grid, block, lm, stream, ka);
+        return s3_if(a.bias != nullptr, [&](auto bias) {
+            return tr == 4 ? s3_launch(s3_fwd_tile_kernel<4, f16(), bias(), dr()>, grid, block, lm, stream, ka)
+                           : s3_launch(s3_fwd_tile_kernel<2, f16(), bias(), dr()>, grid, block, lm, stream, ka);
+        });
+    }); });
+}
+
+// the backward the route names: query side, key side, final sums; `a` is complete.  keep != NULL: the masked (DROP) form of the query side
+// (the key side is the same kernel, it reads P'' where it read P')
+int s3_bwd_launch(const S3Args& a, const amdnuwa_s3_geom* g, const S3Route& r, bool lo, const uint8_t* keep, float drop_s, hipStream_t stream) {
+    const S3Lds l = s3_lds(g, lo);
+    int rc;
+    if (a.NT > 1) {                                                 // column tiles of a wide row
+        rc = s3w_bwd_launch(a, g->dim_head, lo, l.bq, l.bkv, keep, drop_s, stream);
+    } else {
+        // one workgroup per query row, then one per key row (SparseCross2DNA: the FK = kf context frames)
+        const dim3 grid_q(g->B * g->F * g->H), grid_kv(g->B * a.FK * g->H), block(block_threads(g)), band(512);
+        if (r.q_band) {
+            const size_t nspm = (size_t)g->W * (s3_slots(g) * g->heads + 4);                              // the band kernels' padded tables (s3m_ts)
+            const size_t lds_qm = (nspm * 4 > 8 * 4096 ? nspm * 4 : 8 * 4096) + nspm * 4 + (8 * 64 + 16 * 8) * 4 + 8 * 2048;   // + the score staging tiles
+            rc = s3_if(keep != nullptr, [&](auto dr) {
+                const auto ka = s3_kargs<dr()>(a, keep, drop_s);
+                if (r.f16) return s3_launch(s3_bwd_q_mfma_kernel<false, true, dr()>, grid_q, band, lds_qm, stream, ka);    // (no bias in the fp16 form)
+                return s3_if(a.bias != nullptr, [&](auto bias) { return s3_launch(s3_bwd_q_mfma_kernel<bias(), false, dr()>, grid_q, band, lds_qm, stream, ka); });
+            });
+        } else {
+            rc = s3_dispatch(g->dim_head, lo, keep != nullptr, [&](auto dh, auto lo_c, auto dr) {
+                return s3_launch(s3_bwd_q_kernel<dh(), lo_c(), dr()>, grid_q, block, l.bq, stream, s3_kargs<dr()>(a, keep, drop_s));
+            });
+        }
+        if (rc) return rc;
+        switch (r.kv) {
+        case S3KV_BAND_RC: rc = s3_launch(s3_bwd_kv_rc_mfma_kernel, grid_q, band, 8 * 4096 + 16384, stream, a); break;
+        case S3KV_BAND_PACKED:
+            rc = r.f16 ? s3_launch(s3_bwd_kv_mfma_kernel<true, true>, grid_q, band, 8 * 8192, stream, a)
+                       : s3_launch(s3_bwd_kv_mfma_kernel<true>, grid_q, band, 8 * 8192, stream, a);
+            break;
+        case S3KV_BAND_F32: rc = s3_launch(s3_bwd_kv_mfma_kernel<false>, grid_q, band, 8 * 8192, stream, a); break;
+        case S3KV_VALU:
+            rc = s3_dispatch(g->dim_head, lo, false, [&](auto dh, auto lo_c, auto) {
+                return s3_launch(s3_bwd_kv_kernel<dh(), lo_c()>, grid_kv, block, l.bkv, stream, a);
+            });
+        }
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(s3_bwd_fin_kernel, dim3(g->B * ((g->heads * g->dim_head + 63) / 64) + (g->heads * g->heads + 15) / 16), dim3(1024), 0, stream, a, g->dim_head);
     LAUNCH_CHECK();
     return AMDNUWA_OK;
 }
 
-extern "C" int amdnuwa_sparse3dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
-                                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
-                                      const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, hipStream_t stream) {
-    return s3_fwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, o, o_lo, ldo, nullptr, 1.f, stream);
-}
-
-extern "C" int amdnuwa_s3_drop_supported(const amdnuwa_s3_geom* g, int lo_operands) { return drop_geom(g, lo_operands != 0) == AMDNUWA_OK ? 1 : 0; }
-
-extern "C" int amdnuwa_sparse3dna_fwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
-                                           const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
-                                           const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, const uint8_t* keep,
-                                           float drop_scale, hipStream_t stream) {
-    const int rc = drop_geom(g, k_lo != nullptr);
-    if (rc) return rc;
-    if (!drop_args_ok(keep, drop_scale)) return AMDNUWA_ERR_ARG;
-    return s3_fwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, o, o_lo, ldo, keep, drop_scale, stream);
-}
-
-// the geometry of the MFMA band kernels: the causal decoder window on a 16-wide grid, 8 heads x 64
-static bool s3_mfma_geom(const amdnuwa_s3_geom* g) {
-    return !g->noncausal && g->W == 16 && g->heads == 8 && g->dim_head == 64 && g->kw <= S3M_KW && g->kf * g->kh <= S3M_PLANES;
-}
-extern "C" int amdnuwa_s3_f16_supported(const amdnuwa_s3_geom* g) { return check_geom(g) == AMDNUWA_OK && s3_mfma_geom(g) ? 1 : 0; }
-
-// keep == NULL: amdnuwa_sparse3dna_fwd_f16.  keep != NULL: amdnuwa_sparse3dna_fwd_f16_drop
-static int s3_fwd_f16_run(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
-                          int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, const uint8_t* keep, float drop_s,
-                          hipStream_t stream) {
-    int rc = check_geom(g);
-    if (rc) return rc;
-    if (!s3_mfma_geom(g)) return AMDNUWA_ERR_UNSUPPORTED;
-    if (!q_f16 || !k_f16 || !v_f16 || !w_th || ld % 8 || ldo % 8) return AMDNUWA_ERR_ARG;
-    if (!o && !(o_lo && o_lo_f16)) return AMDNUWA_ERR_ARG;        // o == NULL: the fp16 copy is the only output
-    if (g->B <= 0) return AMDNUWA_OK;
-    S3Args a{};
-    fill_geom(a, g);
-    a.q = q_f16; a.k = k_f16; a.v = v_f16; a.ld = ld;
-    a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0;
-    a.dbg = g_amdnuwa_tuning[9];
-    self_kv(a);
-    if (!keep) return s3_fwd_band_launch<true>(a, g, stream);
-    return s3_fwd_band_launch<true, true>(a, g, stream, keep, drop_s);
-}
-extern "C" int amdnuwa_sparse3dna_fwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
-                                          int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, hipStream_t stream) {
-    return s3_fwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, o, o_lo, ldo, o_lo_f16, nullptr, 1.f, stream);
-}
-extern "C" int amdnuwa_sparse3dna_fwd_f16_drop(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
-                                               int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16,
-                                               const uint8_t* keep, float drop_scale, hipStream_t stream) {
-    const int rc = check_geom(g);
-    if (rc) return rc;
-    if (!s3_mfma_geom(g)) return AMDNUWA_ERR_UNSUPPORTED;
-    if (!drop_args_ok(keep, drop_scale) || !keep_aligned(keep)) return AMDNUWA_ERR_ARG;
-    return s3_fwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, o, o_lo, ldo, o_lo_f16, keep, drop_scale, stream);
-}
+}  // namespace
 
 extern "C" int amdnuwa_s3_supported(const amdnuwa_s3_geom* g, int lo_operands) {
     if (check_geom(g)) return 0;
     return s3_lds_need(g, lo_operands != 0) <= S3_LDS_MAX ? 1 : 0;
 }
+// the masked (attention dropout) forms: the causal window on the kernels amdnuwa_sparse3dna_fwd / _bwd pick for the geometry and operand form
+extern "C" int amdnuwa_s3_drop_supported(const amdnuwa_s3_geom* g, int lo_operands) { return amdnuwa_s3_supported(g, lo_operands) && !g->noncausal ? 1 : 0; }
+extern "C" int amdnuwa_s3_f16_supported(const amdnuwa_s3_geom* g) { return check_geom(g) == AMDNUWA_OK && s3_mfma_geom(g) ? 1 : 0; }
+// the fp16-gradient backward: band kernels + packed workspace only (the causal decoder window, no relative-position bias)
+extern "C" int amdnuwa_sparse3dna_bwd_f16_supported(const amdnuwa_s3_geom* g) {
+    return check_geom(g) == AMDNUWA_OK && s3_mfma_geom(g) && !g->rel_bias && !g->d_rel_bias ? 1 : 0;
+}
+extern "C" size_t amdnuwa_sparse3dna_bwd_workspace_bytes(const amdnuwa_s3_geom* g) { return check_geom(g) ? 0 : s3_ws(g).bytes; }
 
-extern "C" size_t amdnuwa_sparse3dna_bwd_workspace_bytes(const amdnuwa_s3_geom* g) {
-    if (check_geom(g)) return 0;
-    // ds + P' [B][nq][J][heads], then the per-workgroup partials (dW_th, <bos> / null dk and dv): one per (query row, column tile)
-    const size_t J = (size_t)g->kf * g->kh * g->kw + 1, nq = g->ntok - 1, rows = (size_t)g->B * g->F * g->H * s3_tile(g).nt;
-    const size_t inner = (size_t)g->heads * g->dim_head;
-    return (2 * (size_t)g->B * nq * J * g->heads + rows * g->heads * g->heads + 2 * rows * inner) * sizeof(float) + 256 +
-           amdnuwa_colsum_workspace_bytes((long long)g->B * nq, (int)(J * g->heads));
+// amdnuwa_sparse3dna_fwd (m = {}) and amdnuwa_sparse3dna_fwd_drop: the DROP form of the kernel the unmasked call picks
+static int s3_fwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                      const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, const S3Mask& m, hipStream_t stream) {
+    int rc = check_geom(g);
+    if (rc) return rc;
+    const bool lo = k_lo != nullptr;
+    if (s3_lds_need(g, lo) > S3_LDS_MAX || (m.on && g->noncausal)) return AMDNUWA_ERR_UNSUPPORTED;
+    if (!mask_ok(m, false) || !q || !k || !v || !w_th || !o || ld % 8 || ldo % 8) return AMDNUWA_ERR_ARG;
+    if (g->B <= 0) return AMDNUWA_OK;
+    if (lo && (!q_lo || !v_lo)) return AMDNUWA_ERR_ARG;
+    const S3Route r = s3_route(g, lo ? S3_HILO : S3_BF16, m.on);
+    if (r.fwd_band && !mask_ok(m, true)) return AMDNUWA_ERR_ARG;
+    S3Args a{};
+    fill_geom(a, g, r);
+    a.q = q; a.k = k; a.v = v; a.ql = q_lo; a.kl = k_lo; a.vl = v_lo; a.ld = ld;
+    a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th;
+    if (r.fwd_band) a.dbg = g_amdnuwa_tuning[9];
+    self_kv(a);
+    return s3_fwd_launch(a, g, r, lo, m.keep, m.s, stream);
+}
+extern "C" int amdnuwa_sparse3dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                      const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                                      const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, hipStream_t stream) {
+    return s3_fwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, o, o_lo, ldo, {}, stream);
+}
+extern "C" int amdnuwa_sparse3dna_fwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                           const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                                           const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, const uint8_t* keep,
+                                           float drop_scale, hipStream_t stream) {
+    return s3_fwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, o, o_lo, ldo, {true, keep, drop_scale}, stream);
 }
 
-// keep == NULL: amdnuwa_sparse3dna_bwd.  keep != NULL: amdnuwa_sparse3dna_bwd_drop (the DROP form of the query side the unmasked call picks --
-// tuning key 26 = 1: of the VALU one at band geometry too; the key side is the same kernel, it reads P'' where it read P')
+// amdnuwa_sparse3dna_fwd_f16 (m = {}) and amdnuwa_sparse3dna_fwd_f16_drop
+static int s3_fwd_f16_run(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
+                          int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, const S3Mask& m, hipStream_t stream) {
+    int rc = check_geom(g);
+    if (rc) return rc;
+    if (!s3_mfma_geom(g)) return AMDNUWA_ERR_UNSUPPORTED;
+    if (!mask_ok(m, true) || !q_f16 || !k_f16 || !v_f16 || !w_th || ld % 8 || ldo % 8) return AMDNUWA_ERR_ARG;
+    if (!o && !(o_lo && o_lo_f16)) return AMDNUWA_ERR_ARG;        // o == NULL: the fp16 copy is the only output
+    if (g->B <= 0) return AMDNUWA_OK;
+    const S3Route r = s3_route(g, S3_F16, m.on);
+    S3Args a{};
+    fill_geom(a, g, r);
+    a.q = q_f16; a.k = k_f16; a.v = v_f16; a.ld = ld;
+    a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0;
+    a.dbg = g_amdnuwa_tuning[9];
+    self_kv(a);
+    return s3_fwd_launch(a, g, r, false, m.keep, m.s, stream);
+}
+extern "C" int amdnuwa_sparse3dna_fwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
+                                          int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, hipStream_t stream) {
+    return s3_fwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, o, o_lo, ldo, o_lo_f16, {}, stream);
+}
+extern "C" int amdnuwa_sparse3dna_fwd_f16_drop(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16,
+                                               int ld, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16,
+                                               const uint8_t* keep, float drop_scale, hipStream_t stream) {
+    return s3_fwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, o, o_lo, ldo, o_lo_f16, {true, keep, drop_scale}, stream);
+}
+
+// amdnuwa_sparse3dna_bwd (m = {}) and amdnuwa_sparse3dna_bwd_drop
 static int s3_bwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
                       const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
                       const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo,
                       uint16_t* dq, uint16_t* dk, uint16_t* dv, uint16_t* dq_lo, uint16_t* dk_lo,
                       uint16_t* dv_lo, int ldd, float* dw_th, int accumulate, void* workspace,
-                      size_t workspace_bytes, const uint8_t* keep, float drop_s, hipStream_t stream) {
+                      size_t workspace_bytes, const S3Mask& m, hipStream_t stream) {
     int rc = check_geom(g);
     if (rc) return rc;
-    if (s3_lds_need(g, k_lo != nullptr) > S3_LDS_MAX) return AMDNUWA_ERR_UNSUPPORTED;
-    if (!q || !k || !v || !w_th || !dO || !dq || !dk || !dv || !dw_th || ld % 8 || lddo % 8 || ldd % 8) return AMDNUWA_ERR_ARG;
-    if (!workspace || workspace_bytes < amdnuwa_sparse3dna_bwd_workspace_bytes(g)) return AMDNUWA_ERR_WORKSPACE;
+    const bool has_lo = k_lo != nullptr, lo = has_lo || dO_lo != nullptr;
+    if (s3_lds_need(g, has_lo) > S3_LDS_MAX || (m.on && g->noncausal)) return AMDNUWA_ERR_UNSUPPORTED;
+    if (!mask_ok(m, false) || !q || !k || !v || !w_th || !dO || !dq || !dk || !dv || !dw_th || ld % 8 || lddo % 8 || ldd % 8) return AMDNUWA_ERR_ARG;
+    if (!workspace || workspace_bytes < s3_ws(g).bytes) return AMDNUWA_ERR_WORKSPACE;
     if (g->B <= 0) return AMDNUWA_OK;
+    if (has_lo && (!q_lo || !v_lo)) return AMDNUWA_ERR_ARG;
+    if (lo && (!has_lo || !dO_lo)) return AMDNUWA_ERR_ARG;          // parity mode needs lo parts for q/k/v AND dO
+    const S3Route r = s3_route(g, lo ? S3_HILO : S3_BF16, m.on);
+    if (r.q_band && !mask_ok(m, true)) return AMDNUWA_ERR_ARG;
     S3Args a{};
-    fill_geom(a, g);
+    fill_geom(a, g, r);
     a.q = q; a.k = k; a.v = v; a.ql = q_lo; a.kl = k_lo; a.vl = v_lo; a.ld = ld; a.wth = w_th;
     a.dO = dO; a.dOl = dO_lo; a.lddo = lddo;
     a.dq = dq; a.dk = dk; a.dv = dv; a.dql = dq_lo; a.dkl = dk_lo; a.dvl = dv_lo; a.ldd = ldd;
     a.dwth = dw_th; a.accumulate = accumulate;
     a.dbg = g_amdnuwa_tuning[17];
-    a.sep_passes = g_amdnuwa_tuning[19] == 1;
+    a.sep_passes = r.sep_passes; a.packed = r.packed;
     self_kv(a);
-    const size_t J = (size_t)g->kf * g->kh * g->kw + 1, nq = g->ntok - 1, rows = (size_t)g->B * g->F * g->H;
-    const size_t inner = (size_t)g->heads * g->dim_head;
-    float* ws = (float*)workspace;
-    a.ds = ws; ws += (size_t)g->B * nq * J * g->heads;
-    a.pm = ws; ws += (size_t)g->B * nq * J * g->heads;
-    const size_t parts = rows * a.NT;                                              // workgroups of the query side: (query row, column tile)
-    a.part_th = ws; ws += parts * g->heads * g->heads;
-    a.part_k0 = ws; ws += parts * inner;
-    a.part_v0 = ws;
-    const bool has_lo = k_lo != nullptr;
-    if (has_lo && (!q_lo || !v_lo)) return AMDNUWA_ERR_ARG;
-    const S3Lds l = s3_lds(g, has_lo);
-    const size_t lds_q = l.bq, lds_kv = l.bkv;
-    dim3 grid((unsigned)rows), block(block_threads(g));
-    // MFMA query-side kernel (tuning key 4: 1 = keep the dot2 kernel): bf16 operands, 16 queries per grid row, 8 heads x 64
-    const bool q_mfma = !(keep && g_amdnuwa_tuning[26] == 1) && !has_lo && !dO_lo && !g->noncausal && g_amdnuwa_tuning[4] != 1 && g->W == 16 && g->heads == 8 && g->dim_head == 64 &&
-                        g->kw <= S3M_KW && g->kf * g->kh <= S3M_PLANES && ld % 8 == 0 && lddo % 8 == 0 && ldd % 4 == 0;
-    // recomputing key side (tuning key 4 = 4; OFF by default: it removes the 3.9 GB workspace round trip -- backward traffic 2.85x ->
-    // 1.5x algorithmic -- but runs 15-22 % slower: its per-plane head exchange serialises the eight waves and its 180 registers allow one
-    // workgroup per CU).  Needs the MFMA query side; d(rel_bias) is a column sum of the ds workspace.  It rebuilds P' from
-    // the statistics and knows no mask: a masked call takes the workspace key side whatever the key says.
-    if (q_mfma && keep && !keep_aligned(keep)) return AMDNUWA_ERR_ARG;
-    const bool kv_rc = q_mfma && g_amdnuwa_tuning[4] == 4 && !g->d_rel_bias && !keep;
-    a.stats = kv_rc ? a.ds : nullptr;                                              // (lives where the workspace would: B*nq*NH*4 floats <= B*nq*J*NH)
-    // packed (bf16 ds | bf16 P') workspace: MFMA query side + MFMA key side, no d(rel_bias) column sum over ds (tuning key 24 = 1: the fp32 pair)
-    a.packed = (q_mfma && g_amdnuwa_tuning[4] != 2 && !g->d_rel_bias && g_amdnuwa_tuning[24] != 1 && !a.sep_passes) ? 1 : 0;
-    const size_t nspm = (size_t)g->W * (J * g->heads + 4);                          // the MFMA kernels' padded tables (s3m_ts)
-    const size_t lds_qm = (nspm * 4 > 8 * 4096 ? nspm * 4 : 8 * 4096) + nspm * 4 + (8 * 64 + 16 * 8) * 4 + 8 * 2048;   // + the score staging tiles
-#define S3B(DH_, LO_, DR_)                                                                                        \
-    do {                                                                                                          \
-        if (q_mfma && a.bias) {                                                                                   \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<true, false, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm); \
-            hipLaunchKernelGGL((s3_bwd_q_mfma_kernel<true, false, DR_>), grid, dim3(512), lds_qm, stream, s3_kargs<DR_>(a, keep, drop_s)); \
-        } else if (q_mfma) {                                                                                      \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<false, false, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm); \
-            hipLaunchKernelGGL((s3_bwd_q_mfma_kernel<false, false, DR_>), grid, dim3(512), lds_qm, stream, s3_kargs<DR_>(a, keep, drop_s)); \
-        } else {                                                                                                  \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_q_kernel<DH_, LO_, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q); \
-            hipLaunchKernelGGL((s3_bwd_q_kernel<DH_, LO_, DR_>), grid, block, lds_q, stream, s3_kargs<DR_>(a, keep, drop_s)); \
-        }                                                                                                         \
-        LAUNCH_CHECK();                                                                                           \
-        if (kv_rc) {                                                                                              \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_kv_rc_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4096 + 16384); \
-            hipLaunchKernelGGL(s3_bwd_kv_rc_mfma_kernel, grid, dim3(512), 8 * 4096 + 16384, stream, a);           \
-        } else if (q_mfma && g_amdnuwa_tuning[4] != 2 && a.packed) {                                              \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_kv_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 8192); \
-            hipLaunchKernelGGL(s3_bwd_kv_mfma_kernel<true>, grid, dim3(512), 8 * 8192, stream, a);                \
-        } else if (q_mfma && g_amdnuwa_tuning[4] != 2) {                                                          \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_kv_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 8192); \
-            hipLaunchKernelGGL(s3_bwd_kv_mfma_kernel<false>, grid, dim3(512), 8 * 8192, stream, a);               \
-        } else {                                                                                                  \
-            (void)hipFuncSetAttribute((const void*)s3_bwd_kv_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv); \
-            hipLaunchKernelGGL((s3_bwd_kv_kernel<DH_, LO_>), grid, block, lds_kv, stream, a);                     \
-        }                                                                                                         \
-    } while (0)
-    const bool lo_mode = has_lo || dO_lo != nullptr;
-    if (lo_mode && (!has_lo || !dO_lo)) return AMDNUWA_ERR_ARG;     // parity mode needs lo parts for q/k/v AND dO
-    if (a.NT > 1) {                                                 // column tiles of a wide row
-        const int rcw = s3w_bwd_launch(a, g->dim_head, lo_mode, lds_q, lds_kv, keep, drop_s, stream);
-        if (rcw) return rcw;
-    } else if (keep) {
-        if (g->dim_head == 64) { if (lo_mode) S3B(64, true, true); else S3B(64, false, true); }
-        else { if (lo_mode) S3B(32, true, true); else S3B(32, false, true); }
-    } else if (g->dim_head == 64) { if (lo_mode) S3B(64, true, false); else S3B(64, false, false); }
-    else { if (lo_mode) S3B(32, true, false); else S3B(32, false, false); }
-#undef S3B
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(s3_bwd_fin_kernel, dim3(g->B * (((int)inner + 63) / 64) + (g->heads * g->heads + 15) / 16), dim3(1024), 0, stream, a, g->dim_head);
-    LAUNCH_CHECK();
+    const S3Ws w = bind_ws(a, g, workspace);
+    a.stats = r.kv == S3KV_BAND_RC ? a.ds : nullptr;
+    rc = s3_bwd_launch(a, g, r, lo, m.keep, m.s, stream);
+    if (rc) return rc;
     if (g->d_rel_bias) {         // d(bias)[j][h] = sum over every (sample, query) of ds[.][j][h]: fixed-order column sums of the ds workspace
-        float* cws = a.part_v0 + parts * inner;
-        const int rc2 = amdnuwa_colsum(a.ds, g->d_rel_bias, (long long)g->B * nq, (int)(J * g->heads), 0, cws,
-                                       amdnuwa_colsum_workspace_bytes((long long)g->B * nq, (int)(J * g->heads)), stream);
-        if (rc2) return rc2;
+        const long long rows = (long long)g->B * (g->ntok - 1);
+        const int cols = (int)(s3_slots(g) * g->heads);
+        return amdnuwa_colsum(a.ds, g->d_rel_bias, rows, cols, 0, (float*)workspace + w.colsum, amdnuwa_colsum_workspace_bytes(rows, cols), stream);
     }
     return AMDNUWA_OK;
 }
-
 extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
                                       const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
                                       const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo,
@@ -3139,93 +3132,60 @@ extern "C" int amdnuwa_sparse3dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* 
                                       uint16_t* dv_lo, int ldd, float* dw_th, int accumulate, void* workspace,
                                       size_t workspace_bytes, hipStream_t stream) {
     return s3_bwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, dO, dO_lo, lddo, dq, dk, dv, dq_lo, dk_lo, dv_lo, ldd, dw_th, accumulate,
-                      workspace, workspace_bytes, nullptr, 1.f, stream);
+                      workspace, workspace_bytes, {}, stream);
 }
-
 extern "C" int amdnuwa_sparse3dna_bwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
                                            const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
                                            const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo,
                                            uint16_t* dq, uint16_t* dk, uint16_t* dv, uint16_t* dq_lo, uint16_t* dk_lo,
                                            uint16_t* dv_lo, int ldd, float* dw_th, int accumulate, void* workspace,
                                            size_t workspace_bytes, const uint8_t* keep, float drop_scale, hipStream_t stream) {
-    const int rc = drop_geom(g, k_lo != nullptr);
-    if (rc) return rc;
-    if (!drop_args_ok(keep, drop_scale)) return AMDNUWA_ERR_ARG;
     return s3_bwd_run(g, q, k, v, q_lo, k_lo, v_lo, ld, w_th, dO, dO_lo, lddo, dq, dk, dv, dq_lo, dk_lo, dv_lo, ldd, dw_th, accumulate,
-                      workspace, workspace_bytes, keep, drop_scale, stream);
+                      workspace, workspace_bytes, {true, keep, drop_scale}, stream);
 }
 
 // fp16-gradient form of the backward ('bf16x3-fwd' with block class 's' of AMDNUWA_BWD_F16): q / k / v are the fp16 copies the forward core
 // read (the ONLY 16-bit copies the block keeps), dO = fp16(S dO), dq / dk / dv leave as fp16(S gradient), dW_th as fp32 without the factor.
-// scale2 = device {S, 1 / S}.  MFMA band kernels + packed workspace only (the causal decoder window, no relative-position bias):
-// AMDNUWA_ERR_UNSUPPORTED otherwise (amdnuwa_sparse3dna_bwd_f16_supported).
-extern "C" int amdnuwa_sparse3dna_bwd_f16_supported(const amdnuwa_s3_geom* g) {
-    return check_geom(g) == AMDNUWA_OK && s3_mfma_geom(g) && !g->rel_bias && !g->d_rel_bias ? 1 : 0;
-}
-// keep == NULL: amdnuwa_sparse3dna_bwd_f16.  keep != NULL: amdnuwa_sparse3dna_bwd_f16_drop
+// scale2 = device {S, 1 / S}.  AMDNUWA_ERR_UNSUPPORTED outside amdnuwa_sparse3dna_bwd_f16_supported().
+// amdnuwa_sparse3dna_bwd_f16 (m = {}) and amdnuwa_sparse3dna_bwd_f16_drop
 static int s3_bwd_f16_run(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16, int ld,
                           const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16,
                           uint16_t* dv_f16, int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace,
-                          size_t workspace_bytes, const uint8_t* keep, float drop_s, hipStream_t stream) {
+                          size_t workspace_bytes, const S3Mask& m, hipStream_t stream) {
     int rc = check_geom(g);
     if (rc) return rc;
     if (!amdnuwa_sparse3dna_bwd_f16_supported(g)) return AMDNUWA_ERR_UNSUPPORTED;
-    if (!q_f16 || !k_f16 || !v_f16 || !w_th || !dO_f16 || !dq_f16 || !dk_f16 || !dv_f16 || !dw_th || !scale2 || ld % 8 || lddo % 8 || ldd % 8)
+    if (!mask_ok(m, true) || !q_f16 || !k_f16 || !v_f16 || !w_th || !dO_f16 || !dq_f16 || !dk_f16 || !dv_f16 || !dw_th || !scale2 || ld % 8 ||
+        lddo % 8 || ldd % 8)
         return AMDNUWA_ERR_ARG;
-    if (!workspace || workspace_bytes < amdnuwa_sparse3dna_bwd_workspace_bytes(g)) return AMDNUWA_ERR_WORKSPACE;
+    if (!workspace || workspace_bytes < s3_ws(g).bytes) return AMDNUWA_ERR_WORKSPACE;
     if (g->B <= 0) return AMDNUWA_OK;
+    const S3Route r = s3_route(g, S3_F16, m.on);
     S3Args a{};
-    fill_geom(a, g);
+    fill_geom(a, g, r);
     a.q = q_f16; a.k = k_f16; a.v = v_f16; a.ld = ld; a.wth = w_th;
     a.dO = dO_f16; a.lddo = lddo;
     a.dq = dq_f16; a.dk = dk_f16; a.dv = dv_f16; a.ldd = ldd;
     a.dwth = dw_th; a.accumulate = accumulate; a.gs2 = scale2;
     a.dbg = g_amdnuwa_tuning[17];
+    a.packed = r.packed;
     self_kv(a);
-    const size_t J = (size_t)g->kf * g->kh * g->kw + 1, nq = g->ntok - 1, rows = (size_t)g->B * g->F * g->H;
-    const size_t inner = (size_t)g->heads * g->dim_head;
-    float* ws = (float*)workspace;
-    a.ds = ws; ws += (size_t)g->B * nq * J * g->heads;
-    a.pm = ws; ws += (size_t)g->B * nq * J * g->heads;
-    a.part_th = ws; ws += rows * g->heads * g->heads;
-    a.part_k0 = ws; ws += rows * inner;
-    a.part_v0 = ws;
-    a.packed = 1;
-    const size_t nspm = (size_t)g->W * (J * g->heads + 4);
-    const size_t lds_qm = (nspm * 4 > 8 * 4096 ? nspm * 4 : 8 * 4096) + nspm * 4 + (8 * 64 + 16 * 8) * 4 + 8 * 2048;
-    const dim3 grid((unsigned)rows);
-    if (keep) {
-        (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm);
-        hipLaunchKernelGGL((s3_bwd_q_mfma_kernel<false, true, true>), grid, dim3(512), lds_qm, stream, s3_kargs<true>(a, keep, drop_s));
-    } else {
-        (void)hipFuncSetAttribute((const void*)s3_bwd_q_mfma_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_qm);
-        hipLaunchKernelGGL((s3_bwd_q_mfma_kernel<false, true>), grid, dim3(512), lds_qm, stream, a);
-    }
-    LAUNCH_CHECK();
-    (void)hipFuncSetAttribute((const void*)s3_bwd_kv_mfma_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 8192);
-    hipLaunchKernelGGL((s3_bwd_kv_mfma_kernel<true, true>), grid, dim3(512), 8 * 8192, stream, a);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(s3_bwd_fin_kernel, dim3(g->B * (((int)inner + 63) / 64) + (g->heads * g->heads + 15) / 16), dim3(1024), 0, stream, a, g->dim_head);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    bind_ws(a, g, workspace);
+    return s3_bwd_launch(a, g, r, false, m.keep, m.s, stream);
 }
 extern "C" int amdnuwa_sparse3dna_bwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16, int ld,
                                           const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16,
                                           uint16_t* dv_f16, int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace,
                                           size_t workspace_bytes, hipStream_t stream) {
     return s3_bwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, dO_f16, lddo, dq_f16, dk_f16, dv_f16, ldd, dw_th, accumulate, scale2, workspace,
-                          workspace_bytes, nullptr, 1.f, stream);
+                          workspace_bytes, {}, stream);
 }
 extern "C" int amdnuwa_sparse3dna_bwd_f16_drop(const amdnuwa_s3_geom* g, const uint16_t* q_f16, const uint16_t* k_f16, const uint16_t* v_f16, int ld,
                                                const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16,
                                                uint16_t* dv_f16, int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace,
                                                size_t workspace_bytes, const uint8_t* keep, float drop_scale, hipStream_t stream) {
-    const int rc = check_geom(g);
-    if (rc) return rc;
-    if (!amdnuwa_sparse3dna_bwd_f16_supported(g)) return AMDNUWA_ERR_UNSUPPORTED;
-    if (!drop_args_ok(keep, drop_scale) || !keep_aligned(keep)) return AMDNUWA_ERR_ARG;
     return s3_bwd_f16_run(g, q_f16, k_f16, v_f16, ld, w_th, dO_f16, lddo, dq_f16, dk_f16, dv_f16, ldd, dw_th, accumulate, scale2, workspace,
-                          workspace_bytes, keep, drop_scale, stream);
+                          workspace_bytes, {true, keep, drop_scale}, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3235,7 +3195,7 @@ extern "C" int amdnuwa_sparse3dna_bwd_f16_drop(const amdnuwa_s3_geom* g, const u
 // (<bos>, which attends to every context token without talking heads) is not touched here: the caller owns o[b*ntok] / dq[b*ntok].
 // ------------------------------------------------------------------------------------------------
 namespace {
-int cross_setup(S3Args& a, const amdnuwa_s3_geom* g, int ctx_rows, const uint16_t* k, const uint16_t* v, const uint16_t* k_lo,
+int cross_setup(S3Args& a, S3Route& r, const amdnuwa_s3_geom* g, int ctx_rows, const uint16_t* k, const uint16_t* v, const uint16_t* k_lo,
                 const uint16_t* v_lo, int ldkv, const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v,
                 const uint16_t* null_v_lo, const uint8_t* key_mask) {
     int rc = check_geom(g);
@@ -3245,7 +3205,8 @@ int cross_setup(S3Args& a, const amdnuwa_s3_geom* g, int ctx_rows, const uint16_
     if (g->rel_bias || ctx_rows != g->kf * g->H * g->W) return AMDNUWA_ERR_ARG;
     if ((k_lo != nullptr) != (v_lo != nullptr) || (k_lo != nullptr) != (null_k_lo != nullptr) || (k_lo != nullptr) != (null_v_lo != nullptr))
         return AMDNUWA_ERR_ARG;
-    fill_geom(a, g);
+    r = s3_route(g, k_lo ? S3_HILO : S3_BF16, false, true);
+    fill_geom(a, g, r);
     a.xmode = 1; a.FK = g->kf; a.kvrows = ctx_rows; a.kvoff = 0; a.kmask = key_mask;
     a.of = 0; a.df = 1;                                            // frame tap a = context frame a
     a.oh = (g->kh - 1) / 2; a.ow = (g->kw - 1) / 2;                // 'same' padding on the feature map (np.py:789)
@@ -3261,25 +3222,13 @@ extern "C" int amdnuwa_cross2dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q
                                      const uint16_t* null_v_lo, const uint8_t* key_mask, const float* w_th, uint16_t* o,
                                      uint16_t* o_lo, int ldo, hipStream_t stream) {
     S3Args a{};
-    int rc = cross_setup(a, g, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask);
+    S3Route r{};
+    int rc = cross_setup(a, r, g, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask);
     if (rc) return rc;
     if (!q || !w_th || !o || ldq % 8 || ldo % 8 || (k_lo != nullptr) != (q_lo != nullptr)) return AMDNUWA_ERR_ARG;
     if (g->B <= 0) return AMDNUWA_OK;
     a.q = q; a.ql = q_lo; a.ld = ldq; a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th;
-    const bool lo_mode = k_lo != nullptr;
-    const size_t lds = s3_lds(g, lo_mode).fwd;
-    if (a.NT > 1) return s3w_fwd_launch(a, g->dim_head, lo_mode, lds, nullptr, 1.f, stream);
-    dim3 grid(g->B * g->F * g->H), block(block_threads(g));
-#define S3F(DH_, LO_)                                                                                             \
-    do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3_fwd_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((s3_fwd_kernel<DH_, LO_>), grid, block, lds, stream, a);                               \
-    } while (0)
-    if (g->dim_head == 64) { if (lo_mode) S3F(64, true); else S3F(64, false); }
-    else { if (lo_mode) S3F(32, true); else S3F(32, false); }
-#undef S3F
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return s3_fwd_launch(a, g, r, k_lo != nullptr, nullptr, 1.f, stream);
 }
 
 extern "C" size_t amdnuwa_cross2dna_bwd_workspace_bytes(const amdnuwa_s3_geom* g) { return amdnuwa_sparse3dna_bwd_workspace_bytes(g); }
@@ -3292,48 +3241,21 @@ extern "C" int amdnuwa_cross2dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q
                                      uint16_t* dv, uint16_t* dk_lo, uint16_t* dv_lo, int lddkv, float* d_null_k, float* d_null_v,
                                      float* dw_th, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     S3Args a{};
-    int rc = cross_setup(a, g, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask);
+    S3Route r{};
+    int rc = cross_setup(a, r, g, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask);
     if (rc) return rc;
     if (!q || !w_th || !dO || !dq || !dk || !dv || !d_null_k || !d_null_v || !dw_th || ldq % 8 || lddo % 8 || lddq % 8 || lddkv % 8)
         return AMDNUWA_ERR_ARG;
-    const bool lo_mode = k_lo != nullptr;
-    if (lo_mode != (q_lo != nullptr) || lo_mode != (dO_lo != nullptr)) return AMDNUWA_ERR_ARG;
-    if (!workspace || workspace_bytes < amdnuwa_cross2dna_bwd_workspace_bytes(g)) return AMDNUWA_ERR_WORKSPACE;
+    const bool lo = k_lo != nullptr;
+    if (lo != (q_lo != nullptr) || lo != (dO_lo != nullptr)) return AMDNUWA_ERR_ARG;
+    if (!workspace || workspace_bytes < s3_ws(g).bytes) return AMDNUWA_ERR_WORKSPACE;
     if (g->B <= 0) return AMDNUWA_OK;
     a.q = q; a.ql = q_lo; a.ld = ldq; a.wth = w_th;
     a.dO = dO; a.dOl = dO_lo; a.lddo = lddo;
     a.dq = dq; a.dql = dq_lo; a.ldd = lddq; a.dk = dk; a.dv = dv; a.dkl = dk_lo; a.dvl = dv_lo; a.lddk = lddkv;
     a.dwth = dw_th; a.accumulate = 0; a.dnull_k = d_null_k; a.dnull_v = d_null_v;
-    const size_t J = (size_t)g->kf * g->kh * g->kw + 1, nq = g->ntok - 1, rows = (size_t)g->B * g->F * g->H;
-    const size_t inner = (size_t)g->heads * g->dim_head;
-    float* ws = (float*)workspace;
-    a.ds = ws; ws += (size_t)g->B * nq * J * g->heads;
-    a.pm = ws; ws += (size_t)g->B * nq * J * g->heads;
-    const size_t parts = rows * a.NT;
-    a.part_th = ws; ws += parts * g->heads * g->heads;
-    a.part_k0 = ws; ws += parts * inner;
-    a.part_v0 = ws;
-    const S3Lds l = s3_lds(g, lo_mode);
-    const size_t lds_q = l.bq, lds_kv = l.bkv;
-    dim3 grid_q((unsigned)rows), grid_kv((unsigned)(g->B * g->kf * g->H)), block(block_threads(g));
-#define S3XB(DH_, LO_)                                                                                            \
-    do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3_bwd_q_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q); \
-        hipLaunchKernelGGL((s3_bwd_q_kernel<DH_, LO_>), grid_q, block, lds_q, stream, a);                         \
-        LAUNCH_CHECK();                                                                                           \
-        (void)hipFuncSetAttribute((const void*)s3_bwd_kv_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv); \
-        hipLaunchKernelGGL((s3_bwd_kv_kernel<DH_, LO_>), grid_kv, block, lds_kv, stream, a);                      \
-    } while (0)
-    if (a.NT > 1) {
-        const int rcw = s3w_bwd_launch(a, g->dim_head, lo_mode, lds_q, lds_kv, nullptr, 1.f, stream);
-        if (rcw) return rcw;
-    } else if (g->dim_head == 64) { if (lo_mode) S3XB(64, true); else S3XB(64, false); }
-    else { if (lo_mode) S3XB(32, true); else S3XB(32, false); }
-#undef S3XB
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(s3_bwd_fin_kernel, dim3(g->B * (((int)inner + 63) / 64) + (g->heads * g->heads + 15) / 16), dim3(1024), 0, stream, a, g->dim_head);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    bind_ws(a, g, workspace);
+    return s3_bwd_launch(a, g, r, lo, nullptr, 1.f, stream);
 }
 
 AMDNUWA_SAT_ACCESSOR(sparse3dna)

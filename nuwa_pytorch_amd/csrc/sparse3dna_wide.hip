@@ -536,38 +536,16 @@ int tile_threads(const S3Args& a) { return ((a.TW * a.NH * 4 + 63) / 64) * 64; }
 
 int s3w_fwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds, const uint8_t* keep, float drop_s, hipStream_t stream) {
     const dim3 grid((unsigned)((size_t)a.B * a.F * a.H * a.NT)), block(tile_threads(a));
-#define S3WF(DH_, LO_, DR_)                                                                                          \
-    do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3w_fwd_kernel<DH_, LO_, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((s3w_fwd_kernel<DH_, LO_, DR_>), grid, block, lds, stream, s3_kargs<DR_>(a, keep, drop_s)); \
-    } while (0)
-    if (keep) {
-        if (dim_head == 64) { if (lo) S3WF(64, true, true); else S3WF(64, false, true); }
-        else { if (lo) S3WF(32, true, true); else S3WF(32, false, true); }
-    } else if (dim_head == 64) { if (lo) S3WF(64, true, false); else S3WF(64, false, false); }
-    else { if (lo) S3WF(32, true, false); else S3WF(32, false, false); }
-#undef S3WF
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return s3_dispatch(dim_head, lo, keep != nullptr, [&](auto dh, auto lo_c, auto dr) {
+        return s3_launch(s3w_fwd_kernel<dh(), lo_c(), dr()>, grid, block, lds, stream, s3_kargs<dr()>(a, keep, drop_s));
+    });
 }
 
 // query side over the B*F*H*NT (query row, tile) workgroups, then the key side over the B*FK*H*NT (key row, tile) ones
 int s3w_bwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds_q, size_t lds_kv, const uint8_t* keep, float drop_s, hipStream_t stream) {
     const dim3 grid_q((unsigned)((size_t)a.B * a.F * a.H * a.NT)), grid_kv((unsigned)((size_t)a.B * a.FK * a.H * a.NT)), block(tile_threads(a));
-#define S3WB(DH_, LO_, DR_)                                                                                          \
-    do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)s3w_bwd_q_kernel<DH_, LO_, DR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q); \
-        hipLaunchKernelGGL((s3w_bwd_q_kernel<DH_, LO_, DR_>), grid_q, block, lds_q, stream, s3_kargs<DR_>(a, keep, drop_s)); \
-        LAUNCH_CHECK();                                                                                           \
-        (void)hipFuncSetAttribute((const void*)s3w_bwd_kv_kernel<DH_, LO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv); \
-        hipLaunchKernelGGL((s3w_bwd_kv_kernel<DH_, LO_>), grid_kv, block, lds_kv, stream, a);                     \
-    } while (0)
-    if (keep) {
-        if (dim_head == 64) { if (lo) S3WB(64, true, true); else S3WB(64, false, true); }
-        else { if (lo) S3WB(32, true, true); else S3WB(32, false, true); }
-    } else if (dim_head == 64) { if (lo) S3WB(64, true, false); else S3WB(64, false, false); }
-    else { if (lo) S3WB(32, true, false); else S3WB(32, false, false); }
-#undef S3WB
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return s3_dispatch(dim_head, lo, keep != nullptr, [&](auto dh, auto lo_c, auto dr) {
+        const int rc = s3_launch(s3w_bwd_q_kernel<dh(), lo_c(), dr()>, grid_q, block, lds_q, stream, s3_kargs<dr()>(a, keep, drop_s));
+        return rc ? rc : s3_launch(s3w_bwd_kv_kernel<dh(), lo_c()>, grid_kv, block, lds_kv, stream, a);
+    });
 }

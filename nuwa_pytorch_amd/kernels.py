@@ -1082,7 +1082,7 @@ def s3_drop_supported(g, lo=None):
     return bool(_lib.lib().amdnuwa_s3_drop_supported(C.byref(g), 1 if lo else 0))
 
 
-def _s3_keep(g, keep, drop_scale):
+def _s3_keep(g, keep):
     """the keep mask of sparse3dna_fwd / _bwd as the uint8 [B, ntok - 1, J, heads] array the kernels read"""
     J = g.kf * g.kh * g.kw + 1
     if tuple(keep.shape) != (g.B, g.ntok - 1, J, g.heads) or keep.dtype not in (torch.bool, torch.uint8):
@@ -1091,24 +1091,23 @@ def _s3_keep(g, keep, drop_scale):
     return keep.view(torch.uint8) if keep.dtype == torch.bool else keep
 
 
+def _s3_call(name, args, keep, drop_scale):
+    """entry point `name`, or with a mask its `_drop` form: the same arguments, then the mask and 1 / (1 - p), then the stream"""
+    if keep is not None:
+        name, args = name + '_drop', args + [_p(keep), float(drop_scale)]
+    check(getattr(_lib.lib(), name)(*args, _stream()), name)
+
+
 @_family('s3', _s3_work('fwd'))
 def sparse3dna_fwd(g, qkv, wth, rel_bias=None, o_f16=False, keep=None, drop_scale=1.0):
     """qkv: BF [B*ntok, 3*inner] (q | k | v);  returns o BF [B*ntok, inner].  rel_bias: fp32 [J, heads] or None.
     o_f16 (fp16 operand form only): o = BF(bf16 copy, None, fp16 copy) -- the operand of the two-MFMA to_out product.
     keep (attention dropout): bool / uint8 [B, ntok - 1, J, heads], nonzero = keep, with drop_scale = 1 / (1 - p): the masked form of the
     kernel the same call takes without a mask (band kernels in the bf16 and fp16 operand forms at their geometry, VALU kernels elsewhere)"""
-    L = _lib.lib()
     g.rel_bias, g.d_rel_bias = _p(rel_bias), None
     inner = g.heads * g.dim_head
     R = g.B * g.ntok
-    k8 = _s3_keep(g, keep, drop_scale) if keep is not None else None
-    if keep is not None and qkv.f16 is None:
-        o = empty_bf((R, inner), qkv.hi.device, lo=qkv.lo is not None)
-        q, k, v = (view(qkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
-        check(L.amdnuwa_sparse3dna_fwd_drop(C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
-                                            _p(wth), _p(o.hi), _p(o.lo), inner, _p(k8), float(drop_scale), _stream()),
-              'amdnuwa_sparse3dna_fwd_drop')
-        return o
+    k8 = _s3_keep(g, keep) if keep is not None else None
     if qkv.f16 is not None:            # fp16 operand form: single fp16 MFMAs; output hi + lo, or (o_f16) a bf16 copy + an fp16 copy
         q16, k16, v16 = (qkv.f16[:, i * inner:(i + 1) * inner] for i in range(3))
         dev = qkv.f16.device
@@ -1119,18 +1118,13 @@ def sparse3dna_fwd(g, qkv, wth, rel_bias=None, o_f16=False, keep=None, drop_scal
                    torch.empty((R, inner), dtype=torch.float16, device=dev))
         else:
             o = empty_bf((R, inner), dev, lo=True)
-        if keep is not None:
-            check(L.amdnuwa_sparse3dna_fwd_f16_drop(C.byref(g), _p(q16), _p(k16), _p(v16), qkv.f16.stride(0), _p(wth), _p(o.hi),
-                                                    _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _p(k8), float(drop_scale),
-                                                    _stream()), 'amdnuwa_sparse3dna_fwd_f16_drop')
-            return o
-        check(L.amdnuwa_sparse3dna_fwd_f16(C.byref(g), _p(q16), _p(k16), _p(v16), qkv.f16.stride(0), _p(wth), _p(o.hi),
-                                           _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _stream()), 'amdnuwa_sparse3dna_fwd_f16')
+        _s3_call('amdnuwa_sparse3dna_fwd_f16', [C.byref(g), _p(q16), _p(k16), _p(v16), qkv.f16.stride(0), _p(wth), _p(o.hi),
+                                                _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0], k8, drop_scale)
         return o
     o = empty_bf((R, inner), qkv.hi.device, lo=qkv.lo is not None)
     q, k, v = (view(qkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
-    check(L.amdnuwa_sparse3dna_fwd(C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
-                                   _p(wth), _p(o.hi), _p(o.lo), inner, _stream()), 'amdnuwa_sparse3dna_fwd')
+    _s3_call('amdnuwa_sparse3dna_fwd', [C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
+                                        _p(wth), _p(o.hi), _p(o.lo), inner], k8, drop_scale)
     return o
 
 
@@ -1153,15 +1147,9 @@ def sparse3dna_bwd16(g, qkv16, wth, dO16, s2, keep=None, drop_scale=1.0):
     dq, dk, dv = (dqkv[:, i * inner:(i + 1) * inner] for i in range(3))
     nb = L.amdnuwa_sparse3dna_bwd_workspace_bytes(C.byref(g))
     ws = workspace(nb, dev)
-    if keep is not None:
-        k8 = _s3_keep(g, keep, drop_scale)
-        check(L.amdnuwa_sparse3dna_bwd_f16_drop(C.byref(g), _p(q), _p(k), _p(v), qkv16.stride(0), _p(wth), _p(dO16), dO16.stride(0),
-                                                _p(dq), _p(dk), _p(dv), dqkv.stride(0), _p(dwth), 0, _p(s2), _p(ws), nb, _p(k8),
-                                                float(drop_scale), _stream()), 'amdnuwa_sparse3dna_bwd_f16_drop')
-        return dqkv, dwth
-    check(L.amdnuwa_sparse3dna_bwd_f16(C.byref(g), _p(q), _p(k), _p(v), qkv16.stride(0), _p(wth), _p(dO16), dO16.stride(0),
-                                       _p(dq), _p(dk), _p(dv), dqkv.stride(0), _p(dwth), 0, _p(s2), _p(ws), nb, _stream()),
-          'amdnuwa_sparse3dna_bwd_f16')
+    k8 = _s3_keep(g, keep) if keep is not None else None
+    _s3_call('amdnuwa_sparse3dna_bwd_f16', [C.byref(g), _p(q), _p(k), _p(v), qkv16.stride(0), _p(wth), _p(dO16), dO16.stride(0),
+                                            _p(dq), _p(dk), _p(dv), dqkv.stride(0), _p(dwth), 0, _p(s2), _p(ws), nb], k8, drop_scale)
     return dqkv, dwth
 
 
@@ -1181,17 +1169,10 @@ def sparse3dna_bwd(g, qkv, wth, dO, rel_bias=None, keep=None, drop_scale=1.0):
     dq, dk, dv = (view(dqkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
     nb = L.amdnuwa_sparse3dna_bwd_workspace_bytes(C.byref(g))
     ws = workspace(nb, dev)
-    if keep is not None:
-        k8 = _s3_keep(g, keep, drop_scale)
-        check(L.amdnuwa_sparse3dna_bwd_drop(C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
-                                            _p(wth), _p(dO.hi), _p(dO.lo), dO.hi.stride(0), _p(dq.hi), _p(dk.hi), _p(dv.hi),
-                                            _p(dq.lo), _p(dk.lo), _p(dv.lo), dqkv.hi.stride(0), _p(dwth), 0, _p(ws), nb, _p(k8),
-                                            float(drop_scale), _stream()), 'amdnuwa_sparse3dna_bwd_drop')
-    else:
-        check(L.amdnuwa_sparse3dna_bwd(C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
-                                       _p(wth), _p(dO.hi), _p(dO.lo), dO.hi.stride(0), _p(dq.hi), _p(dk.hi), _p(dv.hi),
-                                       _p(dq.lo), _p(dk.lo), _p(dv.lo), dqkv.hi.stride(0), _p(dwth), 0, _p(ws), nb, _stream()),
-              'amdnuwa_sparse3dna_bwd')
+    k8 = _s3_keep(g, keep) if keep is not None else None
+    _s3_call('amdnuwa_sparse3dna_bwd', [C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
+                                        _p(wth), _p(dO.hi), _p(dO.lo), dO.hi.stride(0), _p(dq.hi), _p(dk.hi), _p(dv.hi),
+                                        _p(dq.lo), _p(dk.lo), _p(dv.lo), dqkv.hi.stride(0), _p(dwth), 0, _p(ws), nb], k8, drop_scale)
     g.d_rel_bias = None
     return dqkv, dwth, drel
 
