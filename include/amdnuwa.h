@@ -48,7 +48,9 @@ const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
  *          11 its K-step 64 form with staggered wave rows, 12 the four-wave long-K kernel for every K % 64 == 0
- *          (1, 3, 4, 6, 8, 9, 10: A/B variants of rounds 2-4, removed in round 6 -- 1 runs as 2, 10 as 0, the others as 7)
+ *          (1, 3, 4, 6, 8, 9, 10: A/B variants of rounds 2-4, removed in round 6 -- 1 runs as 2, 10 as 5, the others as 7; hi + lo operands
+ *          reach their 256x256 ring under 0 and 7 only and take the 128x128 kernel under every other value; fp16 operands are accepted under
+ *          0, 7, 11, 6 and 10, the last two on the persistent or plain ring)
  *   key 1  TN split-K workgroup slots        key 2  TN minimum token rows per split
  *   key 3  Sparse3DNA forward: 1 = keep the VALU (dot2) kernel        key 13 hi + lo NT GEMM: 1 = first-generation 128x128 kernel
  *   key 4  Sparse3DNA backward: 1 = VALU kernels, 2 = MFMA query side + VALU key side, 4 = MFMA query side + RECOMPUTING MFMA key side
@@ -69,7 +71,7 @@ const char* amdnuwa_error_string(int code);
  *   key 20 NT 256x256 ring as a PERSISTENT kernel (one workgroup per CU walks the tile list, the DMA ring runs on across tile borders):
  *          0 = auto (more tiles than CUs and K <= 1024), 1 = never, 2 = always
  *   key 22 NT long-K kernel (four waves of 128x128, K-step 64, hand-placed main loop: gemm_nt_w4k_kernel): 0 = auto (K >= 1024 and K % 64 == 0),
- *          1 = never (8-wave ring), 2 = for every K % 64 == 0        key 23 TN four-wave kernel (gemm_tn_w4k_kernel): 1 = keep the 8-wave ring
+ *          1 = never (8-wave ring), 2 = for every K % 32 == 0 from 96 up        key 23 TN four-wave kernel (gemm_tn_w4k_kernel): 1 = keep the 8-wave ring
  *   key 24 Sparse3DNA MFMA backward workspace: 0 = ONE array of (bf16 ds | bf16 P') words (round 5), 1 = the two fp32 arrays (same dK / dV bits)
  *   key 25 batched narrow TN (N <= 64, 128 < M <= 384: the cross attention's dK / dV): 1 = 128-row tiles instead of one workgroup per batch element,
  *          2 = always through the split-K reduction (no direct store of a one-split result), 3 = the general whole-M kernel also where the lean

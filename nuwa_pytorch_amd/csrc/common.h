@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -26,6 +27,24 @@ extern int g_amdnuwa_tuning[32];
         hipError_t e__ = hipGetLastError();           \
         if (e__ != hipSuccess) return (int)e__;       \
     } while (0)
+
+// One kernel launch: its dynamic-LDS allowance (lds_attr; the launches that never asked for one -- at most 64 KiB of dynamic LDS -- pass
+// false), the launch, the launch check.
+template <class... P, class... A>
+int launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, bool lds_attr, hipStream_t stream, const A&... args) {
+    if (lds_attr) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    LAUNCH_CHECK();
+    return AMDNUWA_OK;
+}
+// Run-time choices as compile-time parameters: launch_if hands f std::true_type{} or std::false_type{}; launch_pick<V...> hands it
+// std::integral_constant<int, v> for the one v of the list that `value` equals (a value outside the list is an argument error).
+template <class F> int launch_if(bool c, F&& f) { return c ? f(std::true_type{}) : f(std::false_type{}); }
+template <int... V, class F> int launch_pick(int value, F&& f) {
+    int rc = AMDNUWA_ERR_ARG;
+    (void)((value == V ? (rc = f(std::integral_constant<int, V>{}), true) : false) || ...);
+    return rc;
+}
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 

@@ -2672,30 +2672,6 @@ extern "C" int amdnuwa_geglu_il_fwd(const uint16_t* u_hi, const uint16_t* u_lo, 
 extern "C" int amdnuwa_geglu_il_bwd(const uint16_t* u_hi, const uint16_t* u_lo, const uint16_t* d_hi, const uint16_t* d_lo,
                                     uint16_t* du_hi, uint16_t* du_lo, long long R, int FP, hipStream_t stream);
 
-// can the GEGLU gate ride in the epilogue of the kernel this product will run on (the 256x256 staggered ring, bf16 output)?
-static bool nt_geglu_fusable(const amdnuwa_gemm_desc* d) {
-    if (!d->c_is_bf16 || d->batch > 1) return false;
-    if (d->Alo) {                  // bf16x3 ring: the FORWARD gate only (hi + lo gate output), no token shift in the loader
-        if (!d->Blo || d->geglu_u || d->shift_ntok > 0 || g_amdnuwa_tuning[13] == 1) return false;
-    } else if (d->Clo || d->C2lo) return false;
-    if (d->K % 32 || d->N % 16 || d->ldc % 8 || d->ldc2 % 8) return false;
-    if (d->geglu_u && (d->geglu_u_lo || d->ld_u % 8)) return false;
-    const int v = g_amdnuwa_tuning[0];
-    if (v == 7) return true;
-    if (v != 0 || d->M <= 4 * ROWS_MR) return false;
-    return (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) >= 512;
-}
-
-// start-phase step for the first-generation workgroups (see gemm_nt_256_kernel).  Measured (r02, b = 64): a perfectly regular grid (qkv:
-// 3840 equal tiles = 15 per CU) stays phase-locked and gains 12 % in isolation (380 -> 335 us at step 12), ragged grids (ff1, dgrad ff2)
-// gain nothing, and inside the training step -- where the previous kernel's tail already staggers the CUs -- the whole effect is
-// below the noise (600.3 k vs 600.3 k tokens/s).  Off unless forced through tuning key 14 (> 0 = phase step in s_sleep(8) units).
-static int nt_skew(long long tiles) {
-    (void)tiles;
-    const int t = g_amdnuwa_tuning[14];
-    return t > 0 ? t : 0;
-}
-
 // ---- fused linear + cross entropy: row statistics -> lse, row loss, mean (fixed order) ------------------------------------------
 namespace {
 __global__ __launch_bounds__(256) void ce_combine_kernel(const float* __restrict__ stats, const float* __restrict__ tl, int nblk,
@@ -2725,6 +2701,26 @@ __global__ __launch_bounds__(1024) void ce_mean_kernel(const float* __restrict__
 }
 }  // namespace
 
+// =================================================================================================================================
+// Host side.  nt_route() / tn_route() name the ONE kernel a product takes; the support queries read the route, nt_args() builds the
+// argument block, nt_launch() / amdnuwa_gemm_tn() turn the route into a template instantiation and launch it (launch_kernel, common.h).
+// =================================================================================================================================
+
+// tuning keys (include/amdnuwa.h).  nt_route() and its helpers are the only readers of keys 0, 13, 20, 22; tn_route() of 1, 2, 6, 8, 23, 25.
+enum { NTK_VARIANT = 0, NTK_PROBE = 7, NTK_X3_128 = 13, NTK_SKEW = 14, NTK_PERSISTENT = 20, NTK_LONG_K = 22,
+       TNK_SLOTS = 1, TNK_MIN_ROWS = 2, TNK_VARIANT = 6, TNK_STAGGER = 8, TNK_W4K = 23, TNK_WHOLE_M = 25 };
+
+// start-phase step for the first-generation workgroups (see gemm_nt_256_kernel).  Measured (r02, b = 64): a perfectly regular grid (qkv:
+// 3840 equal tiles = 15 per CU) stays phase-locked and gains 12 % in isolation (380 -> 335 us at step 12), ragged grids (ff1, dgrad ff2)
+// gain nothing, and inside the training step -- where the previous kernel's tail already staggers the CUs -- the whole effect is
+// below the noise (600.3 k vs 600.3 k tokens/s).  Off unless forced through tuning key 14 (> 0 = phase step in s_sleep(8) units).
+static int nt_skew() {
+    const int t = g_amdnuwa_tuning[NTK_SKEW];
+    return t > 0 ? t : 0;
+}
+// the probe bits of tuning key 7 (GemmArgs.dbg of every NT launch; bit 1 -- no main loop -- also keeps a product off the two kernels below)
+static int nt_probe() { return g_amdnuwa_tuning[NTK_PROBE]; }
+
 // persistent form of the staggered 256x256 ring (gemm_nt_256p_kernel): taken when a CU owns more than one tile and the main loop is short
 // (K <= 1024); tuning key 20 = 1 keeps the one-tile-per-workgroup launch everywhere, = 2 forces the persistent kernel for any shape
 static int nt_persistent_grid() {
@@ -2736,20 +2732,262 @@ static int nt_persistent_grid() {
     }
     return cus;
 }
-// the four-wave K-step 64 kernel (gemm_nt_w4k_kernel): the long-K products (tuning key 22 = 1 keeps the 8-wave ring, = 2 takes it for
-// every K that is a multiple of 64)
-static bool nt_long_k(int K, int dbg) {
-    const int v = g_amdnuwa_tuning[22];
-    if (v == 1 || K % 32 || K < 96 || (dbg & 2)) return false;
-    // (K % 64 == 32 -- FF2's 1376 -- works, bit-identical, and ties the K-step 64 ring at 592-606 vs 575-662 us: only on request)
-    return v == 2 || (K >= 1024 && K % 64 == 0);
-}
-static bool nt_persistent(long long tiles, int K, int dbg) {
-    const int v = g_amdnuwa_tuning[20];
-    if (v == 1 || K % 32 || K / 32 < 3 || (dbg & 2)) return false;
+static bool nt_persistent(long long tiles, int K) {
+    const int v = g_amdnuwa_tuning[NTK_PERSISTENT];
+    if (v == 1 || K % 32 || K / 32 < 3 || (nt_probe() & 2)) return false;
     // measured at b = 128 (tools/gemm_persist_probe.py): K = 512 shapes -2...-9 %, K = 1536 a tie, K >= 2752 +2...+5 % (the ring fill is
     // nothing next to a long main loop there, and the one-tile launch lets the hardware balance the tail)
     return v == 2 || (tiles > nt_persistent_grid() && K <= 1024);
+}
+// the four-wave K-step 64 kernel (gemm_nt_w4k_kernel): the long-K products (tuning key 22 = 1 keeps the 8-wave ring, = 2 takes it for
+// every K that is a multiple of 32 from 96 up)
+static bool nt_long_k(int K) {
+    const int v = g_amdnuwa_tuning[NTK_LONG_K];
+    if (v == 1 || K % 32 || K < 96 || (nt_probe() & 2)) return false;
+    // (K % 64 == 32 -- FF2's 1376 -- works, bit-identical, and ties the K-step 64 ring at 592-606 vs 575-662 us: only on request)
+    return v == 2 || (K >= 1024 && K % 64 == 0);
+}
+
+enum NtFamily {
+    NT_NONE,                 // no kernel takes the product in this form (fp16 operands only)
+    NT_ROWS,                 // few rows: gemm_nt_rows_kernel streams the weight (the decode step of generate())
+    NT_128_REG,              // gemm_nt_kernel: 128x128 tiles, register-staged, any K % 8 == 0
+    NT_128_GLDS,             // gemm_nt_glds_kernel<32>: 128x128 tiles, direct-to-LDS
+    NT_RING,                 // gemm_nt_256_kernel<.., 4, 4, 1>: 256x256 tiles, 4-stage ring, staggered wave rows
+    NT_RING_K64,             // gemm_nt_256_kernel<.., 1, 4, 4>: its K-step 64 form, two 64 KiB stages
+    NT_RING_PERSISTENT,      // gemm_nt_256p_kernel: one workgroup per CU walks the tile list
+    NT_W4K,                  // gemm_nt_w4k_kernel: four waves of 128x128, K-step 64
+    NT_X3,                   // gemm_nt_256x3_kernel: hi + lo operands, three MFMAs per product
+    NT_X3_X2,                // gemm_nt_256x3_kernel<.., true>: fp16 A x fp16 (hi + lo) B, two MFMAs per product
+};
+struct NtRoute {
+    NtFamily family;
+    int epi;                 // EPI of the kernel: 0 fp32, 1 bf16 (+ second copy / gate), 2 / 3 the cross-entropy passes, 4 ONE fp16 output, 5 fp16 GEGLU backward
+    bool x3, shift, f16;     // its other template flags: hi + lo operands (few-row and 128 register-staged kernels), token shift, fp16 operands
+    int tile;                // rows and columns per unit of GemmArgs.tiles_m / tiles_n
+    int block;
+    size_t lds;              // dynamic LDS bytes
+    bool lds_attr;           // ... announced with hipFuncSetAttribute (every kernel but the direct-to-LDS 128 one, which stays below 64 KiB)
+    bool persistent;         // grid.x = nt_persistent_grid() instead of the tile count
+    bool skew;               // GemmArgs.skew = nt_skew() (else 0)
+    bool gate_fused;         // a GEGLU gate (d->C2) rides in this kernel's epilogue
+    bool decomposed;         // d->C2 given and not fused: the plain product, then the stand-alone gate kernel on the same layout
+    bool f16_copy;           // the hi + lo ring in the form amdnuwa_gemm_nt_f16_fused() reports: it can write the fp16 second copy
+};
+constexpr size_t NT_LDS_RING = (size_t)4 * 2 * 256 * 32 * 2, NT_LDS_K64 = (size_t)2 * 2 * 256 * 64 * 2, NT_LDS_X3 = (size_t)2 * 4 * 256 * 32 * 2,
+                 NT_LDS_X2 = (size_t)2 * 3 * 256 * 32 * 2, NT_LDS_GLDS = (size_t)2 * 2 * 128 * 32 * 2;
+
+static NtRoute nt_route_of(NtFamily f, int epi, size_t lds) {
+    NtRoute r{};
+    r.family = f; r.epi = epi; r.lds = lds;
+    r.tile = (f == NT_ROWS || f == NT_128_REG || f == NT_128_GLDS) ? 128 : 256;
+    r.block = (f == NT_RING || f == NT_RING_K64 || f == NT_RING_PERSISTENT || f == NT_X3 || f == NT_X3_X2) ? 512 : 256;
+    r.lds_attr = f != NT_128_GLDS;
+    r.persistent = f == NT_RING_PERSISTENT;
+    r.skew = r.tile == 256;          // (two plain launches below keep 0)
+    return r;
+}
+
+// bf16 and hi + lo operands.  Tuning key 0 -> family (the table that include/amdnuwa.h describes):
+//   0                auto: K % 32 != 0 -> 128 register-staged; fewer than 512 tiles of 256x256 (over the batch) -> 128 direct-to-LDS; else the
+//                    256x256 family; before all that, M <= 32 unbatched and unshifted -> the few-row kernel, which ANY non-zero key switches off
+//   7                the 256x256 family for every size
+//   11               as 7, with the K-step 64 ring wherever it applies (no shift, no gate)
+//   12               as 7, with the four-wave kernel for every K % 64 == 0 (no shift, gate, second output or bias on a bf16 output)
+//   3 4 6 8 9        removed probe variants: as 7
+//   2, 1             128 direct-to-LDS (1, the removed BK 64 form, runs as 2)
+//   5, 10, others    128 register-staged
+// The 256x256 family needs K % 32 == 0 and the direct-to-LDS kernel too: otherwise 128 register-staged.  hi + lo operands reach their 256x256
+// ring under keys 0 and 7 only (no shift, key 13 != 1); everywhere else they take the 128 register-staged kernel.
+static NtRoute nt_route_plain(const amdnuwa_gemm_desc* d) {
+    const int key = g_amdnuwa_tuning[NTK_VARIANT];
+    const bool x3 = d->Alo != nullptr, sh = d->shift_ntok > 0, k32 = d->K % 32 == 0;
+    const int epi = d->c_is_bf16 ? 1 : 0, K = d->K;
+    const int tm = (d->M + 255) / 256, tn = (d->N + 255) / 256;
+    enum { F128_REG, F128_GLDS, F256 } fam;
+    switch (key) {
+    case 0: fam = !k32 ? F128_REG : (long long)tm * tn * (d->batch > 0 ? d->batch : 1) >= 512 ? F256 : F128_GLDS; break;
+    case 7: case 11: case 12: case 3: case 4: case 6: case 8: case 9: fam = F256; break;
+    case 1: case 2: fam = F128_GLDS; break;
+    default: fam = F128_REG;
+    }
+    if (!k32) fam = F128_REG;
+    NtRoute r;
+    if (key == 0 && d->M <= 4 * ROWS_MR && d->batch <= 1 && !sh && (size_t)ROWS_MR * K * 4 <= 144 * 1024)
+        r = nt_route_of(NT_ROWS, epi, (size_t)ROWS_MR * K * sizeof(float));
+    else if (x3)
+        r = (fam == F256 && (key == 0 || key == 7) && !sh && g_amdnuwa_tuning[NTK_X3_128] != 1) ? nt_route_of(NT_X3, epi, NT_LDS_X3)
+                                                                                            : nt_route_of(NT_128_REG, epi, (size_t)2 * 4 * TILE_BYTES);
+    else if (fam == F256) {
+        if (key == 12 && !sh && K % 64 == 0 && !d->C2 && !d->Clo && !(epi && d->bias)) {
+            r = nt_route_of(NT_W4K, epi, NT_LDS_K64);
+            r.skew = false;                                                  // (the forced probe launch never carried the start-phase step)
+        } else if (!sh && !d->C2 && (key == 11 || (key == 0 && K >= 1024 && K < 2048 && !nt_long_k(K)))) {
+            // measured ahead of the K-step 32 ring on the K = 1376 / 1536 shapes only (FF2 -10 %, dgrad qkv -1.5 %; K = 512 shapes and K >= 2752 equal
+            // or slower: profiles/r04g_gemm_k64.txt), so `auto` takes it for 1024 <= K < 2048 where the long-K kernel does not: K = 1376 here, 1536 there
+            r = nt_route_of(NT_RING_K64, epi, NT_LDS_K64);
+            r.skew = false;                                                  // (nor did this one, with bf16 operands)
+        } else if (!sh && nt_long_k(K)) r = nt_route_of(NT_W4K, epi, NT_LDS_K64);
+        else if (!sh && nt_persistent(tm * tn, K)) r = nt_route_of(NT_RING_PERSISTENT, epi, NT_LDS_RING);
+        else r = nt_route_of(NT_RING, epi, NT_LDS_RING);
+    } else if (fam == F128_GLDS) r = nt_route_of(NT_128_GLDS, epi, NT_LDS_GLDS);
+    else r = nt_route_of(NT_128_REG, epi, (size_t)2 * 2 * TILE_BYTES);
+    r.x3 = x3; r.shift = sh;
+    // What the two queries below report.  They read key 0 more narrowly than the table: only 0 and 7 count (a forced probe variant that runs
+    // "as 7" still decomposes its gate and refuses the fp16 copy), and under 0 a product of at most 32 rows never counts, although the table
+    // sends it to the 256x256 family when it is batched into 512 tiles or its K is beyond the few-row kernel's LDS.
+    const bool asked = r.tile == 256 && (key == 7 || (key == 0 && d->M > 4 * ROWS_MR));
+    // the gate in the epilogue: a bf16 u, unbatched; the hi + lo ring has the FORWARD gate only (hi + lo gate output), the other rings one
+    // copy of u and of the gate (K % 32 == 0 and, for hi + lo operands, no shift and key 13 != 1 follow from the family)
+    r.gate_fused = asked && d->c_is_bf16 && d->batch <= 1 && (x3 ? d->Blo && !d->geglu_u : !d->Clo && !d->C2lo) &&
+                   d->N % 16 == 0 && d->ldc % 8 == 0 && d->ldc2 % 8 == 0 && (!d->geglu_u || (!d->geglu_u_lo && d->ld_u % 8 == 0));
+    r.decomposed = d->C2 && !r.gate_fused;
+    r.f16_copy = asked && r.family == NT_X3 && d->Blo;
+    return r;
+}
+
+// fp16 operands (d->ab_f16), one MFMA per product: the 256x256 rings only -- the FeedForward GEMMs of the 'bf16x3-fwd' forward and the
+// fp16-gradient backward.  (No tile-count threshold above M = 4 * ROWS_MR = 32 rows: the arithmetic of a FeedForward block must not depend on
+// the batch size -- a one-sample parity check (M = n = 2560) has to run the same fp16 products as the training batch, so small M takes the
+// 256x256 ring too.  M <= 32 -- the few-row steps of generate() -- stays on the hi + lo row kernel: more exact)
+static NtRoute nt_route_f16ops(const amdnuwa_gemm_desc* d) {
+    const NtRoute none{};
+    if (!d->A || !d->B || !d->C || d->Alo || d->Blo || d->shift_ntok > 0 || d->batch > 1) return none;
+    if (d->geglu_u && !(d->c_f16 && d->c_is_bf16 && d->C2 && !d->Clo && !d->C2lo && !d->geglu_u_lo && d->ld_u % 8 == 0)) return none;   // GEGLU backward: fp16 du only
+    if (d->c_f16 && (!d->c_is_bf16 || d->Clo || d->C2lo || (d->C2 && !d->geglu_u))) return none;     // fp16 output: one copy, no forward gate
+    if (d->Clo && (!d->c_is_bf16 || d->C2)) return none;              // Clo = fp16 copy of a bf16 output (no gate at the same time)
+    if (d->K % 32 || d->lda % 8 || d->ldb % 8 || d->M <= 4 * ROWS_MR) return none;
+    if (d->c_is_bf16 && (d->N % 16 || d->ldc % 8 || (d->C2 && d->ldc2 % 8))) return none;
+    if (!d->c_is_bf16 && (d->C2 || d->N % 4 || d->ldc % 4)) return none;
+    const int key = g_amdnuwa_tuning[NTK_VARIANT], K = d->K;
+    if (!(key == 0 || key == 7 || key == 11 || key == 6 || key == 10)) return none;     // (6 and 10, removed probe variants, are still admitted: they ride the persistent or plain ring)
+    // epilogue: 0 = fp32, 1 = bf16 (+ fp16 copy / forward gate), 4 = ONE fp16 output, 5 = the fp16 GEGLU backward (fp16-gradient backward);
+    // EPI 5 exists on the persistent and the plain ring only
+    const int epi = d->c_f16 ? (d->geglu_u ? 5 : 4) : (d->c_is_bf16 ? 1 : 0);
+    const long long tiles = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256);
+    NtRoute r;
+    // (here the K-step 64 ring (FF2: -9 %) is asked BEFORE the long-K kernel: K = 1536 runs it with fp16 operands and the four-wave kernel with bf16 ones)
+    if (epi != 5 && (key == 11 || (key == 0 && K >= 1024 && K < 2048))) r = nt_route_of(NT_RING_K64, epi, NT_LDS_K64);
+    else if (epi != 5 && nt_long_k(K) && (key == 0 || key == 7)) r = nt_route_of(NT_W4K, epi, NT_LDS_K64);
+    else if (nt_persistent(tiles, K)) r = nt_route_of(NT_RING_PERSISTENT, epi, NT_LDS_RING + (epi == 5 ? (size_t)8 * 4096 : 0));   // EPI 5: the waves' u tiles behind the ring (160 KiB in all)
+    else r = nt_route_of(NT_RING, epi, NT_LDS_RING);
+    r.f16 = true;
+    return r;
+}
+
+// fp16 A x fp16 (hi + lo) B, two MFMAs per product (d->ab_f16 with Blo): the hi + lo ring's X2 form.  As for the one-MFMA fp16 products
+// there is no tile-count threshold above M = 32 rows -- the arithmetic of a block must not depend on the batch size; the few-row decode
+// steps (M <= 4 * ROWS_MR) run the more exact hi + lo row kernel instead.
+static NtRoute nt_route_f16x2(const amdnuwa_gemm_desc* d) {
+    const NtRoute none{};
+    if (!d->A || !d->B || !d->Blo || !d->C || d->Alo || d->shift_ntok > 0 || d->batch > 1 || d->C2 || d->geglu_u) return none;
+    if (d->K % 32 || d->lda % 8 || d->ldb % 8 || d->M <= 4 * ROWS_MR) return none;
+    if (d->c_is_bf16 ? (d->N % 8 || d->ldc % 8) : d->Clo != nullptr) return none;
+    if (d->c_f16 && (!d->c_is_bf16 || d->Clo)) return none;          // one fp16 output: a 16-bit C, no second copy
+    const int key = g_amdnuwa_tuning[NTK_VARIANT];
+    if (key != 0 && key != 7) return none;
+    NtRoute r = nt_route_of(NT_X3_X2, d->c_is_bf16 ? 1 : 0, NT_LDS_X2);
+    r.f16 = true;
+    return r;
+}
+
+static NtRoute nt_route(const amdnuwa_gemm_desc* d) {
+    if (d->ab_f16) return d->Blo ? nt_route_f16x2(d) : nt_route_f16ops(d);
+    return nt_route_plain(d);
+}
+
+// the queries (include/amdnuwa.h).  The first two ask about the bf16 / hi + lo forms whatever d->ab_f16 says; the last two do not look at it.
+extern "C" int amdnuwa_gemm_nt_fused(const amdnuwa_gemm_desc* d) { return d && d->C2 && nt_route_plain(d).gate_fused ? 1 : 0; }
+extern "C" int amdnuwa_gemm_nt_f16_fused(const amdnuwa_gemm_desc* d) {
+    return d && d->c_is_bf16 && d->Clo && !d->C2 && nt_route_plain(d).f16_copy && d->N % 8 == 0 && d->ldc % 8 == 0 ? 1 : 0;
+}
+extern "C" int amdnuwa_gemm_nt_f16ops_supported(const amdnuwa_gemm_desc* d) { return d && nt_route_f16ops(d).family != NT_NONE ? 1 : 0; }
+extern "C" int amdnuwa_gemm_nt_f16x2_supported(const amdnuwa_gemm_desc* d) { return d && nt_route_f16x2(d).family != NT_NONE ? 1 : 0; }
+
+// the argument block of an NT launch on route r
+static GemmArgs nt_args(const amdnuwa_gemm_desc* d, const NtRoute& r) {
+    GemmArgs p{};
+    p.A = (const bf16_t*)d->A; p.Alo = (const bf16_t*)d->Alo; p.lda = d->lda;
+    p.B = (const bf16_t*)d->B; p.Blo = (const bf16_t*)d->Blo; p.ldb = d->ldb;
+    p.C = d->C; p.Clo = (bf16_t*)d->Clo; p.ldc = d->ldc;
+    p.bias = d->bias; p.alpha = d->alpha;
+    p.M = d->M; p.N = d->N; p.K = d->K; p.shift_dim = d->K;
+    p.tiles_m = (d->M + r.tile - 1) / r.tile; p.tiles_n = (d->N + r.tile - 1) / r.tile;      // in 128-row units on the 128 kernels, 256-row units on the rest
+    p.dbg = nt_probe();
+    p.skew = r.skew ? nt_skew() : 0;
+    if (!d->ab_f16) {                                        // (the fp16-operand forms are unbatched and unshifted: their fields stay zero)
+        p.sA = d->strideA; p.sB = d->strideB; p.sC = d->strideC;
+        p.batch_inner = d->batch_inner; p.sA_in = d->strideA_inner; p.sB_in = d->strideB_inner; p.sC_in = d->strideC_inner;
+        p.shift_ntok = d->shift_ntok; p.shift_fmap = d->shift_fmap;
+    }
+    if (d->C2) { p.C2 = (bf16_t*)d->C2; p.C2lo = (bf16_t*)d->C2lo; p.ldc2 = d->ldc2; }      // (C2lo: the hi + lo ring and the fp16 rings; NULL where the plain ring fuses)
+    if (d->geglu_u) { p.Uin = (const bf16_t*)d->geglu_u; p.ldu = d->ld_u; }
+    // the second copy of a bf16 output as its fp16 rendering (the next fp16 consumer's operand): always on the X2 form, on request on the hi + lo ring
+    p.lo_f16 = r.family == NT_X3_X2 ? d->Clo != nullptr : r.family == NT_X3 ? (d->c_is_bf16 && d->c_lo_f16 && d->Clo) : 0;
+    p.c_f16 = d->ab_f16 && d->c_f16;                         // C itself (or du) is the fp16 rendering and there is no other copy (fp16-gradient backward)
+    if (r.family == NT_ROWS) p.beta = (d->c_is_bf16 && !d->Clo) ? 1.f : 0.f;      // destination-type marker for the rows kernel (see its epilogue)
+    return p;
+}
+
+// route -> template instantiation -> launch.  `batch` is grid.y of the tiled kernels.
+static int nt_launch(const NtRoute& r, const GemmArgs& p, int batch, hipStream_t stream) {
+    const dim3 grid = r.family == NT_ROWS ? dim3((p.N + 4 * ROWS_CPW - 1) / (4 * ROWS_CPW), (p.M + ROWS_MR - 1) / ROWS_MR)
+                                          : dim3(r.persistent ? nt_persistent_grid() : p.tiles_m * p.tiles_n, batch);
+    const auto go = [&](auto kernel) { return launch_kernel(kernel, grid, dim3(r.block), r.lds, r.lds_attr, stream, p); };
+    switch (r.family) {
+    case NT_ROWS: return launch_if(r.x3, [&](auto lo) { return go(gemm_nt_rows_kernel<lo()>); });
+    case NT_128_REG:
+        return launch_if(r.x3, [&](auto x3) { return launch_if(r.shift, [&](auto sh) { return launch_pick<0, 1>(r.epi, [&](auto e) {
+            return go(gemm_nt_kernel<x3(), sh(), e()>); }); }); });
+    case NT_128_GLDS:
+        return launch_if(r.shift, [&](auto sh) { return launch_pick<0, 1>(r.epi, [&](auto e) { return go(gemm_nt_glds_kernel<32, sh(), e()>); }); });
+    case NT_RING:
+        if (r.f16) return launch_pick<0, 1, 3, 4, 5>(r.epi, [&](auto e) { return go(gemm_nt_256_kernel<false, e(), 4, 4, 1, true>); });
+        if (r.shift) return launch_pick<0, 1>(r.epi, [&](auto e) { return go(gemm_nt_256_kernel<true, e(), 4, 4, 1>); });
+        return launch_pick<0, 1, 2, 3>(r.epi, [&](auto e) { return go(gemm_nt_256_kernel<false, e(), 4, 4, 1>); });
+    case NT_RING_K64:
+        if (r.f16) return launch_pick<0, 1, 4>(r.epi, [&](auto e) { return go(gemm_nt_256_kernel<false, e(), 1, 4, 4, true>); });
+        return launch_pick<0, 1>(r.epi, [&](auto e) { return go(gemm_nt_256_kernel<false, e(), 1, 4, 4, false>); });
+    case NT_RING_PERSISTENT:
+        if (r.f16) return launch_pick<0, 1, 4, 5>(r.epi, [&](auto e) { return go(gemm_nt_256p_kernel<e(), true>); });
+        return launch_pick<0, 1>(r.epi, [&](auto e) { return go(gemm_nt_256p_kernel<e(), false>); });
+    case NT_W4K:
+        if (r.f16) return launch_pick<0, 1, 4>(r.epi, [&](auto e) { return go(gemm_nt_w4k_kernel<e(), true>); });
+        return launch_pick<0, 1>(r.epi, [&](auto e) { return go(gemm_nt_w4k_kernel<e(), false>); });
+    case NT_X3: return launch_pick<0, 1, 2, 3>(r.epi, [&](auto e) { return go(gemm_nt_256x3_kernel<e()>); });
+    case NT_X3_X2: return launch_pick<0, 1>(r.epi, [&](auto e) { return go(gemm_nt_256x3_kernel<e(), true>); });
+    default: return AMDNUWA_ERR_UNSUPPORTED;
+    }
+}
+
+extern "C" int amdnuwa_gemm_nt(const amdnuwa_gemm_desc* d, hipStream_t stream) {
+    if (!d || !d->A || !d->B || !d->C) return AMDNUWA_ERR_ARG;
+    if (d->M <= 0 || d->N <= 0) return AMDNUWA_OK;
+    if (d->geglu_u && !d->C2) return AMDNUWA_ERR_ARG;
+    const NtRoute r = nt_route(d);
+    if (r.decomposed) {                                     // plain product, then the stand-alone gate kernel on the same layout
+        if (!d->c_is_bf16 || d->ldc != d->N || d->batch > 1) return AMDNUWA_ERR_ARG;
+        amdnuwa_gemm_desc plain = *d;
+        plain.C2 = nullptr; plain.C2lo = nullptr; plain.geglu_u = nullptr; plain.geglu_u_lo = nullptr;
+        const int rc = amdnuwa_gemm_nt(&plain, stream);
+        if (rc) return rc;
+        if (d->geglu_u) {
+            if (d->N % 8 || d->ld_u != 2 * d->N || d->ldc2 != 2 * d->N) return AMDNUWA_ERR_ARG;
+            return amdnuwa_geglu_il_bwd(d->geglu_u, d->geglu_u_lo, (const uint16_t*)d->C, d->Clo, d->C2, d->C2lo, d->M, d->N, stream);
+        }
+        if (d->N % 16 || d->ldc2 != d->N / 2) return AMDNUWA_ERR_ARG;
+        return amdnuwa_geglu_il_fwd((const uint16_t*)d->C, d->Clo, d->C2, d->C2lo, d->M, d->N / 2, stream);
+    }
+    if (d->ab_f16) {                                        // the fp16-operand forms answer with their queries' verdict, before any other check
+        if (r.family == NT_NONE) return AMDNUWA_ERR_UNSUPPORTED;
+    } else {
+        if (d->K % 8 || d->lda % 8 || d->ldb % 8) return AMDNUWA_ERR_ARG;
+        if ((d->Alo == nullptr) != (d->Blo == nullptr)) return AMDNUWA_ERR_ARG;
+        if (d->shift_ntok > 0 && (d->shift_fmap <= 0 || d->K % 32)) return AMDNUWA_ERR_ARG;
+        if (d->c_lo_f16 && !amdnuwa_gemm_nt_f16_fused(d)) return AMDNUWA_ERR_UNSUPPORTED;
+        if (r.family == NT_ROWS && d->Clo && !d->c_is_bf16) return AMDNUWA_ERR_ARG;      // (the few-row kernel writes a second copy of a bf16 output only)
+    }
+    return nt_launch(r, nt_args(d, r), d->batch > 0 ? d->batch : 1, stream);
 }
 
 extern "C" size_t amdnuwa_linear_ce_workspace_bytes(long long R, int C) {
@@ -2774,43 +3012,27 @@ static int linear_ce_run(const uint16_t* h, const uint16_t* h_lo, const uint16_t
     float* tl = lse + R;
     hipError_t e = hipMemsetAsync(tl, 0xff, (size_t)R * sizeof(float), stream);          // NaN until a valid target column writes it
     if (e != hipSuccess) return (int)e;
-    GemmArgs p{};
-    p.A = (const bf16_t*)h; p.Alo = (const bf16_t*)h_lo; p.lda = ldh; p.B = (const bf16_t*)w; p.Blo = (const bf16_t*)w_lo; p.ldb = ldw;
-    p.C = dlogits; p.ldc = ld_dl; p.alpha = 1.f;
-    p.M = (int)R; p.N = C; p.K = K; p.shift_dim = K;
-    p.tiles_m = (int)((R + 255) / 256); p.tiles_n = (C + 255) / 256;
+    // both passes are NT products logits = h w^T on the plain or the hi + lo ring (EPI 2, then 3), C = dlogits
+    amdnuwa_gemm_desc d{};
+    d.A = h; d.Alo = h_lo; d.lda = ldh; d.B = w; d.Blo = w_lo; d.ldb = ldw; d.C = dlogits; d.ldc = ld_dl; d.alpha = 1.f;
+    d.M = (int)R; d.N = C; d.K = K;
+    NtRoute r = x3 ? nt_route_of(NT_X3, 2, NT_LDS_X3) : nt_route_of(NT_RING, 2, NT_LDS_RING);
+    GemmArgs p = nt_args(&d, r);
+    p.dbg = 0;                                                // (the probe bits of key 7 never reached these passes)
     p.ce_stats = stats; p.ce_tl = tl; p.ce_lse = lse; p.ce_tgt = targets; p.ce_scale = grad_scale; p.ce_nblk = nblk;
-    p.skew = nt_skew((long long)p.tiles_m * p.tiles_n);
-    dim3 grid(p.tiles_m * p.tiles_n, 1), block(512);
-    const size_t lds = x3 ? (size_t)2 * 4 * 256 * 32 * 2 : (size_t)4 * 2 * 256 * 32 * 2;
-    if (x3) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_256x3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((gemm_nt_256x3_kernel<2>), grid, block, lds, stream, p);
-    } else {
-        (void)hipFuncSetAttribute((const void*)gemm_nt_256_kernel<false, 2, 4, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((gemm_nt_256_kernel<false, 2, 4, 4, 1>), grid, block, lds, stream, p);
+    int rc = nt_launch(r, p, 1, stream);
+    if (rc) return rc;
+    rc = launch_kernel(ce_combine_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, false, stream, stats, tl, nblk, R, lse, row_loss);
+    if (rc) return rc;
+    rc = launch_kernel(ce_mean_kernel, dim3(1), dim3(1024), 0, false, stream, row_loss, R, loss);
+    if (rc || !dlogits) return rc;
+    r.epi = 3;
+    if (x3 && h16 && w16) {                                   // one fp16 MFMA per product against the exact lse
+        p.A = (const bf16_t*)h16; p.B = (const bf16_t*)w16; p.Alo = nullptr; p.Blo = nullptr;
+        r = nt_route_of(NT_RING, 3, NT_LDS_RING);
+        r.f16 = true;
     }
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_combine_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, stats, tl, nblk, R, lse, row_loss);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_mean_kernel, dim3(1), dim3(1024), 0, stream, row_loss, R, loss);
-    LAUNCH_CHECK();
-    if (dlogits) {
-        if (x3 && h16 && w16) {
-            p.A = (const bf16_t*)h16; p.B = (const bf16_t*)w16; p.Alo = nullptr; p.Blo = nullptr;
-            const size_t l16 = (size_t)4 * 2 * 256 * 32 * 2;
-            (void)hipFuncSetAttribute((const void*)gemm_nt_256_kernel<false, 3, 4, 4, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l16);
-            hipLaunchKernelGGL((gemm_nt_256_kernel<false, 3, 4, 4, 1, true>), grid, block, l16, stream, p);
-        } else if (x3) {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_256x3_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((gemm_nt_256x3_kernel<3>), grid, block, lds, stream, p);
-        } else {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_256_kernel<false, 3, 4, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((gemm_nt_256_kernel<false, 3, 4, 4, 1>), grid, block, lds, stream, p);
-        }
-        LAUNCH_CHECK();
-    }
-    return AMDNUWA_OK;
+    return nt_launch(r, p, 1, stream);
 }
 
 extern "C" int amdnuwa_linear_ce(const uint16_t* h, int ldh, const uint16_t* w, int ldw, const long long* targets, long long R, int C,
@@ -2829,478 +3051,125 @@ extern "C" int amdnuwa_linear_ce_x3(const uint16_t* h_hi, const uint16_t* h_lo, 
                          workspace_bytes, stream);
 }
 
-extern "C" int amdnuwa_gemm_nt_fused(const amdnuwa_gemm_desc* d) { return d && d->C2 && nt_geglu_fusable(d) ? 1 : 0; }
-
-// fp16 operands (d->ab_f16): the 256x256 ring only -- the FeedForward GEMMs of the 'bf16x3-fwd' forward
-extern "C" int amdnuwa_gemm_nt_f16ops_supported(const amdnuwa_gemm_desc* d) {
-    if (!d || !d->A || !d->B || !d->C || d->Alo || d->Blo || d->shift_ntok > 0 || d->batch > 1) return 0;
-    if (d->geglu_u && !(d->c_f16 && d->c_is_bf16 && d->C2 && !d->Clo && !d->C2lo && !d->geglu_u_lo && d->ld_u % 8 == 0)) return 0;   // GEGLU backward: fp16 du only
-    if (d->c_f16 && (!d->c_is_bf16 || d->Clo || d->C2lo || (d->C2 && !d->geglu_u))) return 0;     // fp16 output: one copy, no forward gate
-    if (d->Clo && (!d->c_is_bf16 || d->C2)) return 0;              // Clo = fp16 copy of a bf16 output (no gate at the same time)
-    if (d->K % 32 || d->lda % 8 || d->ldb % 8 || d->M <= 4 * ROWS_MR) return 0;
-    if (d->c_is_bf16 && (d->N % 16 || d->ldc % 8 || (d->C2 && d->ldc2 % 8))) return 0;
-    if (!d->c_is_bf16 && (d->C2 || d->N % 4 || d->ldc % 4)) return 0;
-    // (no tile-count threshold above M = 4 * ROWS_MR = 32 rows: the arithmetic of a FeedForward block must not depend on the batch size -- a
-    //  one-sample parity check (M = n = 2560) has to run the same fp16 products as the training batch, so small M takes the 256x256 ring too.
-    //  M <= 32 -- the few-row steps of generate() -- stays on the hi + lo row kernel: more exact, and documented in DESIGN.md section 3)
-    const int v = g_amdnuwa_tuning[0];
-    return (v == 0 || v == 7 || v == 6 || v == 10 || v == 11) ? 1 : 0;          // (6: the 256x128 two-workgroups-per-CU probe of the same ring; 10: the K-step 64 form)
-}
-
-// fp16 A x fp16 (hi + lo) B, two MFMAs per product (d->ab_f16 with Blo): the hi + lo ring's X2 form.  As for the one-MFMA fp16 products
-// there is no tile-count threshold above M = 32 rows -- the arithmetic of a block must not depend on the batch size; the few-row decode
-// steps (M <= 4 * ROWS_MR) run the more exact hi + lo row kernel instead.
-extern "C" int amdnuwa_gemm_nt_f16x2_supported(const amdnuwa_gemm_desc* d) {
-    if (!d || !d->A || !d->B || !d->Blo || !d->C || d->Alo || d->shift_ntok > 0 || d->batch > 1 || d->C2 || d->geglu_u) return 0;
-    if (d->K % 32 || d->lda % 8 || d->ldb % 8 || d->M <= 4 * ROWS_MR) return 0;
-    if (d->c_is_bf16 ? (d->N % 8 || d->ldc % 8) : d->Clo != nullptr) return 0;
-    if (d->c_f16 && (!d->c_is_bf16 || d->Clo)) return 0;          // one fp16 output: a 16-bit C, no second copy
-    const int v = g_amdnuwa_tuning[0];
-    return (v == 0 || v == 7) ? 1 : 0;
-}
-
-// does this product run on the bf16x3 256x256 ring (the only kernel that writes the fp16 second copy)?
-static bool nt_x3_ring(const amdnuwa_gemm_desc* d) {
-    if (!d->Alo || !d->Blo || d->shift_ntok > 0 || d->K % 32 || g_amdnuwa_tuning[13] == 1) return false;
-    const int v = g_amdnuwa_tuning[0];
-    if (v == 7) return true;
-    if (v != 0 || d->M <= 4 * ROWS_MR) return false;
-    return (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) * (d->batch > 0 ? d->batch : 1) >= 512;
-}
-extern "C" int amdnuwa_gemm_nt_f16_fused(const amdnuwa_gemm_desc* d) {
-    return d && d->c_is_bf16 && d->Clo && !d->C2 && nt_x3_ring(d) && d->N % 8 == 0 && d->ldc % 8 == 0 ? 1 : 0;
-}
-
-extern "C" int amdnuwa_gemm_nt(const amdnuwa_gemm_desc* d, hipStream_t stream) {
-    if (!d || !d->A || !d->B || !d->C) return AMDNUWA_ERR_ARG;
-    if (d->M <= 0 || d->N <= 0) return AMDNUWA_OK;
-    if (d->geglu_u && !d->C2) return AMDNUWA_ERR_ARG;
-    if (d->C2 && !d->ab_f16 && !nt_geglu_fusable(d)) {             // plain product, then the stand-alone gate kernel on the same layout
-        if (!d->c_is_bf16 || d->ldc != d->N || d->batch > 1) return AMDNUWA_ERR_ARG;
-        amdnuwa_gemm_desc plain = *d;
-        plain.C2 = nullptr; plain.C2lo = nullptr; plain.geglu_u = nullptr; plain.geglu_u_lo = nullptr;
-        const int rc = amdnuwa_gemm_nt(&plain, stream);
-        if (rc) return rc;
-        if (d->geglu_u) {
-            if (d->N % 8 || d->ld_u != 2 * d->N || d->ldc2 != 2 * d->N) return AMDNUWA_ERR_ARG;
-            return amdnuwa_geglu_il_bwd(d->geglu_u, d->geglu_u_lo, (const uint16_t*)d->C, d->Clo, d->C2, d->C2lo, d->M, d->N, stream);
-        }
-        if (d->N % 16 || d->ldc2 != d->N / 2) return AMDNUWA_ERR_ARG;
-        return amdnuwa_geglu_il_fwd((const uint16_t*)d->C, d->Clo, d->C2, d->C2lo, d->M, d->N / 2, stream);
-    }
-    if (d->ab_f16 && d->Blo) {                 // fp16 activation x fp16 (hi + lo) weight: two MFMAs per product on the hi + lo ring
-        if (!amdnuwa_gemm_nt_f16x2_supported(d)) return AMDNUWA_ERR_UNSUPPORTED;
-        GemmArgs q{};
-        q.A = (const bf16_t*)d->A; q.lda = d->lda; q.B = (const bf16_t*)d->B; q.Blo = (const bf16_t*)d->Blo; q.ldb = d->ldb;
-        q.C = d->C; q.Clo = (bf16_t*)d->Clo; q.ldc = d->ldc; q.bias = d->bias; q.alpha = d->alpha;
-        q.M = d->M; q.N = d->N; q.K = d->K; q.shift_dim = d->K;
-        q.tiles_m = (d->M + 255) / 256; q.tiles_n = (d->N + 255) / 256;
-        q.dbg = g_amdnuwa_tuning[7];
-        q.lo_f16 = d->Clo ? 1 : 0;             // the second copy of a bf16 output is its fp16 rendering (the next fp16 consumer's operand)
-        q.c_f16 = d->c_f16 ? 1 : 0;            // ... or C itself is the fp16 rendering and there is no other copy (fp16-gradient backward of the block)
-        q.skew = nt_skew((long long)q.tiles_m * q.tiles_n);
-        dim3 g3(q.tiles_m * q.tiles_n, 1), b3(512);
-        const size_t l3 = (size_t)2 * 3 * 256 * 32 * 2;
-        if (d->c_is_bf16) {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_256x3_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3);
-            hipLaunchKernelGGL((gemm_nt_256x3_kernel<1, true>), g3, b3, l3, stream, q);
-        } else {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_256x3_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3);
-            hipLaunchKernelGGL((gemm_nt_256x3_kernel<0, true>), g3, b3, l3, stream, q);
-        }
-        LAUNCH_CHECK();
-        return AMDNUWA_OK;
-    }
-    if (d->ab_f16) {
-        if (!amdnuwa_gemm_nt_f16ops_supported(d)) return AMDNUWA_ERR_UNSUPPORTED;
-        GemmArgs q{};
-        q.A = (const bf16_t*)d->A; q.lda = d->lda; q.B = (const bf16_t*)d->B; q.ldb = d->ldb;
-        q.C = d->C; q.Clo = (bf16_t*)d->Clo; q.ldc = d->ldc; q.bias = d->bias; q.alpha = d->alpha;
-        q.M = d->M; q.N = d->N; q.K = d->K; q.shift_dim = d->K;
-        q.tiles_m = (d->M + 255) / 256; q.tiles_n = (d->N + 255) / 256;
-        q.dbg = g_amdnuwa_tuning[7];
-        if (d->C2) { q.C2 = (bf16_t*)d->C2; q.C2lo = (bf16_t*)d->C2lo; q.ldc2 = d->ldc2; }
-        if (d->geglu_u) { q.Uin = (const bf16_t*)d->geglu_u; q.ldu = d->ld_u; }
-        q.c_f16 = d->c_f16 ? 1 : 0;
-        q.skew = nt_skew((long long)q.tiles_m * q.tiles_n);
-        // epilogue: 0 = fp32, 1 = bf16 (+ fp16 copy / forward gate), 4 = ONE fp16 output or the fp16 GEGLU backward (fp16-gradient backward)
-        const int epi = d->c_f16 ? (d->geglu_u ? 5 : 4) : (d->c_is_bf16 ? 1 : 0);
-#define F16_LAUNCH(KERNEL, GRID, BLOCK, LDS, ...)                                                                         \
-    do {                                                                                                                  \
-        if (epi == 4) {                                                                                                   \
-            (void)hipFuncSetAttribute((const void*)KERNEL<__VA_ARGS__ 4 F16_TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)); \
-            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ 4 F16_TAIL>), GRID, BLOCK, LDS, stream, q);                            \
-        } else if (epi == 5) {                                                                                            \
-            (void)hipFuncSetAttribute((const void*)KERNEL<__VA_ARGS__ EPI5 F16_TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)); \
-            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ EPI5 F16_TAIL>), GRID, BLOCK, LDS, stream, q);                         \
-        } else if (epi == 1) {                                                                                            \
-            (void)hipFuncSetAttribute((const void*)KERNEL<__VA_ARGS__ 1 F16_TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)); \
-            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ 1 F16_TAIL>), GRID, BLOCK, LDS, stream, q);                            \
-        } else {                                                                                                          \
-            (void)hipFuncSetAttribute((const void*)KERNEL<__VA_ARGS__ 0 F16_TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)); \
-            hipLaunchKernelGGL((KERNEL<__VA_ARGS__ 0 F16_TAIL>), GRID, BLOCK, LDS, stream, q);                            \
-        }                                                                                                                 \
-        LAUNCH_CHECK();                                                                                                   \
-        return AMDNUWA_OK;                                                                                                \
-    } while (0)
-        // (EPI5: the GEGLU-backward epilogue exists on the persistent ring and the plain ring only; elsewhere the name stands for EPI 4 and is never reached)
-#define EPI5 4
-        const size_t l64 = (size_t)2 * 2 * 256 * 64 * 2;
-        dim3 g2(q.tiles_m * q.tiles_n, 1), b2(512);
-        if (epi != 5 && (g_amdnuwa_tuning[0] == 11 || (g_amdnuwa_tuning[0] == 0 && d->K >= 1024 && d->K < 2048))) {     // K-step 64 form with staggered wave rows (FF2: -9 %)
-#define F16_TAIL , 1, 4, 4, true
-            F16_LAUNCH(gemm_nt_256_kernel, g2, b2, l64, false,);
-#undef F16_TAIL
-        }
-        const size_t l2 = (size_t)4 * 2 * 256 * 32 * 2;
-        if (epi != 5 && nt_long_k(d->K, q.dbg) && (g_amdnuwa_tuning[0] == 0 || g_amdnuwa_tuning[0] == 7)) { // long K: four waves of 128x128, K-step 64 (gemm_nt_w4k_kernel)
-            dim3 b4(256);
-#define F16_TAIL , true
-            F16_LAUNCH(gemm_nt_w4k_kernel, g2, b4, l64, );
-#undef F16_TAIL
-        }
-#undef EPI5
-#define EPI5 5
-        if (nt_persistent(q.tiles_m * q.tiles_n, d->K, q.dbg)) {               // one workgroup per CU walks the tile list (gemm_nt_256p_kernel)
-            dim3 gp(nt_persistent_grid(), 1);
-            const size_t l2p = l2 + (epi == 5 ? (size_t)8 * 4096 : 0);             // EPI 5: the waves' u tiles behind the ring (160 KiB in all)
-#define F16_TAIL , true
-            F16_LAUNCH(gemm_nt_256p_kernel, gp, b2, l2p, );
-#undef F16_TAIL
-        }
-#define F16_TAIL , 4, 4, 1, true
-        F16_LAUNCH(gemm_nt_256_kernel, g2, b2, l2, false,);
-#undef F16_TAIL
-#undef EPI5
-#undef F16_LAUNCH
-    }
-    if (d->K % 8 || d->lda % 8 || d->ldb % 8) return AMDNUWA_ERR_ARG;
-    if ((d->Alo == nullptr) != (d->Blo == nullptr)) return AMDNUWA_ERR_ARG;
-    if (d->shift_ntok > 0 && (d->shift_fmap <= 0 || d->K % 32)) return AMDNUWA_ERR_ARG;
-    if (d->c_lo_f16 && !amdnuwa_gemm_nt_f16_fused(d)) return AMDNUWA_ERR_UNSUPPORTED;
-    GemmArgs p;
-    p.A = (const bf16_t*)d->A; p.Alo = (const bf16_t*)d->Alo; p.sA = d->strideA; p.lda = d->lda;
-    p.B = (const bf16_t*)d->B; p.Blo = (const bf16_t*)d->Blo; p.sB = d->strideB; p.ldb = d->ldb;
-    p.C = d->C; p.Clo = (bf16_t*)d->Clo; p.sC = d->strideC; p.ldc = d->ldc;
-    p.bias = d->bias; p.alpha = d->alpha; p.beta = 0.f;
-    p.M = d->M; p.N = d->N; p.K = d->K;
-    p.shift_ntok = d->shift_ntok; p.shift_fmap = d->shift_fmap; p.shift_dim = d->K;
-    p.tiles_m = (d->M + BM - 1) / BM; p.tiles_n = (d->N + BN - 1) / BN;
-    p.ksplit_len = 0;
-    p.dbg = g_amdnuwa_tuning[7];
-    p.skew = 0;
-    p.C2 = nullptr; p.C2lo = nullptr; p.ldc2 = 0; p.Uin = nullptr; p.ldu = 0; p.lo_f16 = 0; p.c_f16 = 0;
-    p.batch_inner = d->batch_inner; p.sA_in = d->strideA_inner; p.sB_in = d->strideB_inner; p.sC_in = d->strideC_inner;
-    const bool x3 = d->Alo != nullptr, sh = d->shift_ntok > 0, ob = d->c_is_bf16 != 0;
-    // a handful of rows (the decode step of generate()): stream the weight instead of running MFMA tiles
-    if (g_amdnuwa_tuning[0] == 0 && d->M <= 4 * ROWS_MR && d->batch <= 1 && !sh && (size_t)ROWS_MR * d->K * 4 <= 144 * 1024) {
-        if (d->Clo && !ob) return AMDNUWA_ERR_ARG;
-        p.beta = (ob && !d->Clo) ? 1.f : 0.f;                  // destination-type marker for the rows kernel (see its epilogue)
-        const size_t lds = (size_t)ROWS_MR * d->K * sizeof(float);
-        dim3 g((d->N + 4 * ROWS_CPW - 1) / (4 * ROWS_CPW), (d->M + ROWS_MR - 1) / ROWS_MR);
-        if (x3) {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((gemm_nt_rows_kernel<true>), g, dim3(256), lds, stream, p);
-        } else {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((gemm_nt_rows_kernel<false>), g, dim3(256), lds, stream, p);
-        }
-        LAUNCH_CHECK();
-        return AMDNUWA_OK;
-    }
-    dim3 grid(p.tiles_m * p.tiles_n, d->batch > 0 ? d->batch : 1), block(256);
-    // direct-to-LDS variants (tuning key 0: 0 = register-staged, 1 = glds BK 64, 2 = glds BK 32)
-    // tuning key 0: 0 = auto, 1 = direct-to-LDS BK 64, 2 = direct-to-LDS BK 32, 3 / 4 = 256x256 tile with a 4- / 3-stage
-    // DMA ring, 5 = register-staged.  auto: 256x256 ring when it yields >= 2 full rounds of tiles on 256 CUs, else BK 32.
-    int variant = g_amdnuwa_tuning[0];
-    if (variant == 0) {
-        const long long t256 = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) * (d->batch > 0 ? d->batch : 1);
-        variant = (d->K % 32 == 0) ? (t256 >= 512 ? 7 : 2) : 5;
-    }
-    // bf16x3 on the 256x256 tile (2-stage ring of hi + lo images); tuning key 13 = 1 keeps the first-generation 128x128 kernel
-    if (x3 && !sh && variant == 7 && d->K % 32 == 0 && g_amdnuwa_tuning[13] != 1) {
-        p.tiles_m = (d->M + 255) / 256; p.tiles_n = (d->N + 255) / 256;
-        dim3 g3(p.tiles_m * p.tiles_n, d->batch > 0 ? d->batch : 1), b3(512);
-        const size_t l3 = (size_t)2 * 4 * 256 * 32 * 2;
-        if (d->C2) { p.C2 = (bf16_t*)d->C2; p.C2lo = (bf16_t*)d->C2lo; p.ldc2 = d->ldc2; }
-        p.lo_f16 = (ob && d->c_lo_f16 && d->Clo) ? 1 : 0;
-        p.skew = nt_skew((long long)p.tiles_m * p.tiles_n);
-        if (ob) {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_256x3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3);
-            hipLaunchKernelGGL((gemm_nt_256x3_kernel<1>), g3, b3, l3, stream, p);
-        } else {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_256x3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3);
-            hipLaunchKernelGGL((gemm_nt_256x3_kernel<0>), g3, b3, l3, stream, p);
-        }
-        LAUNCH_CHECK();
-        return AMDNUWA_OK;
-    }
-    if (!x3 && !sh && variant == 12 && d->K % 64 == 0 && !d->C2 && !d->Clo && !(ob && d->bias)) {   // 4 waves x 128x128, K-step 64, 1.5-iteration prefetch
-        p.tiles_m = (d->M + 255) / 256; p.tiles_n = (d->N + 255) / 256;
-        dim3 g4(p.tiles_m * p.tiles_n, d->batch > 0 ? d->batch : 1), b4(256);
-        const size_t l4 = (size_t)2 * 2 * 256 * 64 * 2;
-        if (ob) {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_w4k_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4);
-            hipLaunchKernelGGL((gemm_nt_w4k_kernel<1, false>), g4, b4, l4, stream, p);
-        } else {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_w4k_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4);
-            hipLaunchKernelGGL((gemm_nt_w4k_kernel<0, false>), g4, b4, l4, stream, p);
-        }
-        LAUNCH_CHECK();
-        return AMDNUWA_OK;
-    }
-    if (variant == 12 || variant == 9 || variant == 8 || variant == 6 || variant == 3 || variant == 4) variant = 7;   // (3 / 4 / 6 / 8 / 9: probe variants of rounds 2-4, removed in round 6)
-    if (variant == 1) variant = 2;
-    // K-step 64 form with staggered wave rows (two 64 KiB stages of full 128-byte row lines): measured ahead of the K-step 32 ring on the
-    // K = 1376 / 1536 shapes only (FF2 -10 %, dgrad qkv -1.5 %; K = 512 shapes and K >= 2752 equal or slower: profiles/r04g_gemm_k64.txt), so `auto`
-    // takes it for 1024 <= K < 2048; tuning key 0 = 11 forces it, 7 keeps the ring
-    if (!x3 && !sh && (variant == 11 || (g_amdnuwa_tuning[0] == 0 && variant == 7 && d->K >= 1024 && d->K < 2048 && !nt_long_k(d->K, p.dbg))) && d->K % 32 == 0 && !d->C2) {
-        p.tiles_m = (d->M + 255) / 256; p.tiles_n = (d->N + 255) / 256;
-        dim3 g2(p.tiles_m * p.tiles_n, d->batch > 0 ? d->batch : 1), b2(512);
-        const size_t l6 = (size_t)2 * 2 * 256 * 64 * 2;
-        if (ob) {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_256_kernel<false, 1, 1, 4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l6);
-            hipLaunchKernelGGL((gemm_nt_256_kernel<false, 1, 1, 4, 4, false>), g2, b2, l6, stream, p);
-        } else {
-            (void)hipFuncSetAttribute((const void*)gemm_nt_256_kernel<false, 0, 1, 4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l6);
-            hipLaunchKernelGGL((gemm_nt_256_kernel<false, 0, 1, 4, 4, false>), g2, b2, l6, stream, p);
-        }
-        LAUNCH_CHECK();
-        return AMDNUWA_OK;
-    }
-    if (variant == 11) variant = 7;
-    if (!x3 && variant == 7 && d->K % 32 == 0) {                           // 256x256 tile, 4-stage ring, staggered wave rows
-        p.tiles_m = (d->M + 255) / 256; p.tiles_n = (d->N + 255) / 256;
-        if (d->C2) { p.C2 = (bf16_t*)d->C2; p.ldc2 = d->ldc2; p.Uin = (const bf16_t*)d->geglu_u; p.ldu = d->ld_u; }
-        p.skew = nt_skew((long long)p.tiles_m * p.tiles_n);
-        dim3 g2(p.tiles_m * p.tiles_n, d->batch > 0 ? d->batch : 1), b2(512);
-        if (!sh && nt_long_k(d->K, p.dbg)) {                                   // long K: four waves of 128x128, K-step 64 (gemm_nt_w4k_kernel)
-            const size_t l4 = (size_t)2 * 2 * 256 * 64 * 2;
-            dim3 b4(256);
-            if (ob) {
-                (void)hipFuncSetAttribute((const void*)gemm_nt_w4k_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4);
-                hipLaunchKernelGGL((gemm_nt_w4k_kernel<1, false>), g2, b4, l4, stream, p);
-            } else {
-                (void)hipFuncSetAttribute((const void*)gemm_nt_w4k_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4);
-                hipLaunchKernelGGL((gemm_nt_w4k_kernel<0, false>), g2, b4, l4, stream, p);
-            }
-            LAUNCH_CHECK();
-            return AMDNUWA_OK;
-        }
-        if (!sh && nt_persistent(p.tiles_m * p.tiles_n, d->K, p.dbg)) {        // one workgroup per CU walks the tile list (gemm_nt_256p_kernel)
-            const size_t l2 = (size_t)4 * 2 * 256 * 32 * 2;
-            dim3 gp(nt_persistent_grid(), d->batch > 0 ? d->batch : 1);
-            if (ob) {
-                (void)hipFuncSetAttribute((const void*)gemm_nt_256p_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-                hipLaunchKernelGGL((gemm_nt_256p_kernel<1, false>), gp, b2, l2, stream, p);
-            } else {
-                (void)hipFuncSetAttribute((const void*)gemm_nt_256p_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-                hipLaunchKernelGGL((gemm_nt_256p_kernel<0, false>), gp, b2, l2, stream, p);
-            }
-            LAUNCH_CHECK();
-            return AMDNUWA_OK;
-        }
-#define GS(SH, EP)                                                                                                    \
-    do {                                                                                                              \
-        const size_t l2 = (size_t)4 * 2 * 256 * 32 * 2;                                                               \
-        (void)hipFuncSetAttribute((const void*)gemm_nt_256_kernel<SH, EP, 4, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2); \
-        hipLaunchKernelGGL((gemm_nt_256_kernel<SH, EP, 4, 4, 1>), g2, b2, l2, stream, p);                           \
-    } while (0)
-        if (sh) { if (ob) GS(true, 1); else GS(true, 0); } else { if (ob) GS(false, 1); else GS(false, 0); }
-#undef GS
-        LAUNCH_CHECK();
-        return AMDNUWA_OK;
-    }
-    if (!x3 && variant == 2 && d->K % 32 == 0) {
-        const size_t gl = (size_t)2 * 2 * 128 * 32 * 2;
-#define GL_LAUNCH(BK__, SH, EP) hipLaunchKernelGGL((gemm_nt_glds_kernel<BK__, SH, EP>), grid, block, gl, stream, p)
-        if (sh) { if (ob) GL_LAUNCH(32, true, 1); else GL_LAUNCH(32, true, 0); } else { if (ob) GL_LAUNCH(32, false, 1); else GL_LAUNCH(32, false, 0); }
-#undef GL_LAUNCH
-        LAUNCH_CHECK();
-        return AMDNUWA_OK;
-    }
-    const size_t lds = (size_t)2 * (x3 ? 4 : 2) * TILE_BYTES;
-#define NT_LAUNCH(X3, SH, EP)                                                                                      \
-    do {                                                                                                             \
-        (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<X3, SH, EP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((gemm_nt_kernel<X3, SH, EP>), grid, block, lds, stream, p);                               \
-    } while (0)
-    if (x3) { if (sh) { if (ob) NT_LAUNCH(true, true, 1); else NT_LAUNCH(true, true, 0); } else { if (ob) NT_LAUNCH(true, false, 1); else NT_LAUNCH(true, false, 0); } }
-    else    { if (sh) { if (ob) NT_LAUNCH(false, true, 1); else NT_LAUNCH(false, true, 0); } else { if (ob) NT_LAUNCH(false, false, 1); else NT_LAUNCH(false, false, 0); } }
-#undef NT_LAUNCH
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
-}
-
-// tuning key 6: 0 = auto (256x256 4-stage ring when both output dims >= 256, else direct-to-LDS 128x128),
-//               1 = register-staged 128x128, 2 = direct-to-LDS 128x128, 3 = 256x256 ring
-static int tn_variant(const amdnuwa_gemm_desc* d) {
-    const bool x3 = d->Alo != nullptr, big = (long long)d->K >= (1LL << 31);
-    if (x3 || big) return 1;
-    int v = g_amdnuwa_tuning[6];
-    if (v == 0) v = (d->M >= 256 && d->N >= 256) ? 3 : 2;
-    if (v == 3 && !(d->M >= 256 && d->N >= 256)) v = 2;
-    return v;
-}
-// the four-wave weight-gradient kernel (gemm_tn_w4k_kernel): plain bf16 operands, no token shift, token rows and column counts it can cover
-// without edge handling (tuning key 23 = 1 keeps the 8-wave ring)
-static bool tn_w4k_ok(const amdnuwa_gemm_desc* d) {
-    if (g_amdnuwa_tuning[23] == 1 || d->Alo || d->shift_ntok > 0) return false;
-    return d->K % 64 == 0 && d->K >= 128 && d->M >= 256 && d->N >= 256;
-}
-// the whole-M narrow kernel (gemm_tn_wm_kernel): batched, N <= 64, 128 < M <= 384 (tuning key 25 = 1 keeps the 128-row tiles).  Returns MT or 0.
-static int tn_whole_m(const amdnuwa_gemm_desc* d) {
-    if (g_amdnuwa_tuning[25] == 1 || d->Alo || d->shift_ntok > 0 || (long long)d->K >= (1LL << 31)) return 0;
-    const int v = g_amdnuwa_tuning[6];
-    if ((v != 0 && v != 2) || d->N > 64 || d->N < 1 || d->M <= 128 || d->M > 384 || d->batch < 2) return 0;
-    return (d->M + 127) / 128;
-}
-// split-K policy: fill the workgroup SLOTS of the chip exactly once (256 CUs x resident workgroups per CU);
-// never exceed them (a 257th workgroup would cost a whole extra round), keep >= minrows token rows per split.
-static int tn_splits(const amdnuwa_gemm_desc* d) {
-    const int v = tn_variant(d);
-    const int tl = v == 3 ? 256 : 128;
-    const bool wm = tn_whole_m(d) != 0;                      // one workgroup per batch element, one workgroup per CU
-    const int tiles = wm ? d->batch : ((d->M + tl - 1) / tl) * ((d->N + tl - 1) / tl) * (d->batch > 0 ? d->batch : 1);
-    const int slots = g_amdnuwa_tuning[1] > 0 ? g_amdnuwa_tuning[1] : (v == 3 || wm ? 256 : 1024);
-    const int minrows = g_amdnuwa_tuning[2] > 0 ? g_amdnuwa_tuning[2] : 256;
-    int splits = slots / tiles;                              // floor: stay within one round
+// ---- TN: C[N1 = M, N2 = N] (fp32) = beta * C + alpha * A[K rows, M]^T . B[K rows, N]; the token shift (if any) applies to B --------------
+struct TnRoute {
+    int variant;             // 1 register-staged 128x128 (gemm_tn_kernel), 2 direct-to-LDS 128x128 (gemm_tn_glds_kernel / whole-M), 3 the 256x256 family
+    bool w4k;                // variant 3: the four-wave kernel (gemm_tn_w4k_kernel) instead of the 8-wave ring (gemm_tn_256_kernel)
+    int mt;                  // != 0 (variant 2 only): the whole-M narrow kernel with MT = mt row tiles, one workgroup per batch element
+    bool lean; int mi;       // ... its lean form (gemm_tn_wmf_kernel) with MI row fragments per wave
+    bool direct;             // ... writing C itself: one split, beta = 0 -- no reduction launch
+    bool stagger;            // the 8-wave ring with staggered wave rows
+    int splits, ksplit_len;  // split-K: number of splits, token rows per split
+};
+// tuning key 6: 0 = auto (the 256x256 family when both output dims >= 256, else direct-to-LDS 128x128), 1 = register-staged 128x128,
+// 2 = direct-to-LDS 128x128, 3 = as auto; hi + lo operands and K >= 2^31 take the register-staged kernel whatever the key says
+static TnRoute tn_route(const amdnuwa_gemm_desc* d) {
+    TnRoute r{};
+    const bool x3 = d->Alo != nullptr, sh = d->shift_ntok > 0, big = (long long)d->K >= (1LL << 31), sq256 = d->M >= 256 && d->N >= 256;
+    const int key = g_amdnuwa_tuning[TNK_VARIANT], key_wm = g_amdnuwa_tuning[TNK_WHOLE_M];
+    r.variant = (x3 || big) ? 1 : (key == 0 || key == 3) ? (sq256 ? 3 : 2) : key;
+    // the four-wave weight-gradient kernel: plain bf16 / fp16 operands, no token shift, token rows and column counts it can cover without edge
+    // handling (tuning key 23 = 1 keeps the 8-wave ring)
+    r.w4k = r.variant == 3 && g_amdnuwa_tuning[TNK_W4K] != 1 && !sh && d->K % 64 == 0 && d->K >= 128;
+    // the whole-M narrow kernel: batched, N <= 64, 128 < M <= 384 -- the cross attention's dK / dV (tuning key 25 = 1 keeps the 128-row tiles).
+    // Its shapes are below 256 columns, so keys 0 and 2 both mean variant 2 here.
+    if (key_wm != 1 && !x3 && !sh && !big && (key == 0 || key == 2) && d->N >= 1 && d->N <= 64 && d->M > 128 && d->M <= 384 && d->batch >= 2)
+        r.mt = (d->M + 127) / 128;
+    // the lean form: whole K-steps in every split, 32-bit piece offsets (tuning key 25 = 3 keeps the general kernel)
+    r.lean = r.mt && key_wm != 3 && d->K % TK == 0 && (long long)((d->M + 31) / 32) * d->K * 64 < (1LL << 32) && 32LL * d->lda * 2 < (1LL << 31) &&
+             32LL * d->ldb * 2 < (1LL << 31);
+    r.mi = ((d->M + 15) / 16 + 3) / 4;
+    // tuning key 8: 0 = auto = lock-step, 1 = lock-step, 2 = staggered wave rows.  With the DMA pieces issued through asm (common.h:
+    // the compiler no longer drains the ring before the fragment reads) the lock-step loop gained 15-27 % and passed the staggered
+    // one on every weight-gradient shape of the step (r02: dW qkv 466 -> 340 us vs 424 staggered; dW ff1 787 -> 608 vs 773)
+    r.stagger = g_amdnuwa_tuning[TNK_STAGGER] == 2;
+    // split-K policy: fill the workgroup SLOTS of the chip exactly once (256 CUs x resident workgroups per CU);
+    // never exceed them (a 257th workgroup would cost a whole extra round), keep >= minrows token rows per split.
+    const int tl = r.variant == 3 ? 256 : 128;
+    const int tiles = r.mt ? d->batch : ((d->M + tl - 1) / tl) * ((d->N + tl - 1) / tl) * (d->batch > 0 ? d->batch : 1);   // whole-M: one workgroup per batch element
+    const int slots = g_amdnuwa_tuning[TNK_SLOTS] > 0 ? g_amdnuwa_tuning[TNK_SLOTS] : (r.variant == 3 || r.mt ? 256 : 1024);
+    const int minrows = g_amdnuwa_tuning[TNK_MIN_ROWS] > 0 ? g_amdnuwa_tuning[TNK_MIN_ROWS] : 256;
+    r.splits = tiles > 0 ? slots / tiles : 1;                // floor: stay within one round (an empty product has no tiles)
     const int maxs = (d->K + minrows - 1) / minrows;
-    if (splits > maxs) splits = maxs;
-    if (splits < 1) splits = 1;
-    return splits;
+    if (r.splits > maxs) r.splits = maxs;
+    if (r.splits < 1) r.splits = 1;
+    r.ksplit_len = ((d->K + r.splits - 1) / r.splits + TK - 1) / TK * TK;
+    if (r.w4k) r.ksplit_len = (r.ksplit_len + 63) / 64 * 64;                     // whole 64-row iterations per split
+    r.direct = r.mt && r.splits == 1 && d->beta == 0.f && key_wm != 2;           // (a device factor rides in the direct epilogue too)
+    return r;
 }
-
+static size_t tn_workspace(const amdnuwa_gemm_desc* d, const TnRoute& r) {
+    return (size_t)r.splits * (d->batch > 0 ? d->batch : 1) * (size_t)d->M * d->N * sizeof(float);
+}
 // A in planes of 32 columns (d->a_chunk32): the whole-M narrow kernel only
-extern "C" int amdnuwa_gemm_tn_chunked_a_supported(const amdnuwa_gemm_desc* d) {
-    if (!d || d->lda % 8 || d->ldb % 8) return 0;
-    return tn_variant(d) == 2 && tn_whole_m(d) != 0 ? 1 : 0;
-}
-
+static bool tn_chunked_a_ok(const amdnuwa_gemm_desc* d, const TnRoute& r) { return !(d->lda % 8 || d->ldb % 8) && r.mt != 0; }
 // fp16 operands (d->ab_f16): the four-wave kernel and the whole-M narrow kernel only
-extern "C" int amdnuwa_gemm_tn_f16_supported(const amdnuwa_gemm_desc* d) {
-    if (!d || d->Alo || d->Blo || d->shift_ntok > 0 || d->lda % 8 || d->ldb % 8) return 0;
-    if (tn_variant(d) == 2) return tn_whole_m(d) != 0 ? 1 : 0;
-    return tn_variant(d) == 3 && tn_w4k_ok(d) ? 1 : 0;
+static bool tn_f16_ok(const amdnuwa_gemm_desc* d, const TnRoute& r) {
+    if (d->Alo || d->Blo || d->shift_ntok > 0 || d->lda % 8 || d->ldb % 8) return false;
+    return r.variant == 2 ? r.mt != 0 : r.w4k;
 }
+extern "C" int amdnuwa_gemm_tn_chunked_a_supported(const amdnuwa_gemm_desc* d) { return d && tn_chunked_a_ok(d, tn_route(d)) ? 1 : 0; }
+extern "C" int amdnuwa_gemm_tn_f16_supported(const amdnuwa_gemm_desc* d) { return d && tn_f16_ok(d, tn_route(d)) ? 1 : 0; }
+extern "C" size_t amdnuwa_gemm_tn_workspace_bytes(const amdnuwa_gemm_desc* d) { return d ? tn_workspace(d, tn_route(d)) : 0; }
 
-extern "C" size_t amdnuwa_gemm_tn_workspace_bytes(const amdnuwa_gemm_desc* d) {
-    if (!d) return 0;
-    return (size_t)tn_splits(d) * (d->batch > 0 ? d->batch : 1) * (size_t)d->M * d->N * sizeof(float);
-}
-
-// C[N1=M, N2=N] (fp32) = beta*C + alpha * A[K rows, M]^T . B[K rows, N]; shift (if any) applies to B.
 extern "C" int amdnuwa_gemm_tn(const amdnuwa_gemm_desc* d, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     if (!d || !d->A || !d->B || !d->C || d->c_is_bf16) return AMDNUWA_ERR_ARG;
     if (d->M <= 0 || d->N <= 0) return AMDNUWA_OK;
     if (d->lda % 8 || d->ldb % 8) return AMDNUWA_ERR_ARG;   // operand rows must be readable up to the next multiple of 8 columns
     if ((d->Alo == nullptr) != (d->Blo == nullptr)) return AMDNUWA_ERR_ARG;
     if (d->shift_ntok > 0 && (d->shift_fmap <= 0 || d->N % 32)) return AMDNUWA_ERR_ARG;
-    if (workspace_bytes < amdnuwa_gemm_tn_workspace_bytes(d) || !workspace) return AMDNUWA_ERR_WORKSPACE;
-    if (d->ab_f16 && !amdnuwa_gemm_tn_f16_supported(d)) return AMDNUWA_ERR_UNSUPPORTED;
-    if (d->a_chunk32 && !amdnuwa_gemm_tn_chunked_a_supported(d)) return AMDNUWA_ERR_UNSUPPORTED;
-    GemmArgs p;
-    p.c_f16 = 0; p.a_chunk = d->a_chunk32 ? 1 : 0; p.alpha_dev = d->alpha_dev;
+    const TnRoute r = tn_route(d);
+    if (workspace_bytes < tn_workspace(d, r) || !workspace) return AMDNUWA_ERR_WORKSPACE;
+    if (d->ab_f16 && !tn_f16_ok(d, r)) return AMDNUWA_ERR_UNSUPPORTED;
+    if (d->a_chunk32 && !tn_chunked_a_ok(d, r)) return AMDNUWA_ERR_UNSUPPORTED;
+    const int tl = r.variant == 3 ? 256 : 128, batch = d->batch > 0 ? d->batch : 1, splits = r.splits;
+    const bool x3 = d->Alo != nullptr, sh = d->shift_ntok > 0;
+    GemmArgs p{};
+    p.a_chunk = d->a_chunk32 ? 1 : 0; p.alpha_dev = d->alpha_dev;
     p.A = (const bf16_t*)d->A; p.Alo = (const bf16_t*)d->Alo; p.sA = d->strideA; p.lda = d->lda;
     p.B = (const bf16_t*)d->B; p.Blo = (const bf16_t*)d->Blo; p.sB = d->strideB; p.ldb = d->ldb;
-    p.C = d->C; p.Clo = nullptr; p.sC = d->strideC; p.ldc = d->ldc;
-    p.bias = nullptr; p.alpha = d->alpha; p.beta = d->beta;
+    p.C = d->C; p.sC = d->strideC; p.ldc = d->ldc;
+    p.alpha = d->alpha; p.beta = d->beta;
     p.M = d->M; p.N = d->N; p.K = d->K;
     p.shift_ntok = d->shift_ntok; p.shift_fmap = d->shift_fmap; p.shift_dim = d->N;
-    p.tiles_m = (d->M + 127) / 128; p.tiles_n = (d->N + 127) / 128;
-    const int splits = tn_splits(d);
-    int len = (d->K + splits - 1) / splits;
-    len = (len + TK - 1) / TK * TK;
-    if (tn_variant(d) == 3 && d->shift_ntok <= 0 && tn_w4k_ok(d)) len = (len + 63) / 64 * 64;      // whole 64-row iterations per split
-    p.ksplit_len = len;
+    p.tiles_m = (d->M + tl - 1) / tl; p.tiles_n = (d->N + tl - 1) / tl;
+    p.ksplit_len = r.ksplit_len;
     p.batch_inner = d->batch_inner; p.sA_in = d->strideA_inner; p.sB_in = d->strideB_inner; p.sC_in = d->strideC_inner;
-    const int batch = d->batch > 0 ? d->batch : 1;
-    const bool x3 = d->Alo != nullptr, sh = d->shift_ntok > 0;
-    dim3 grid(p.tiles_m * p.tiles_n, batch, splits), block(256);
-    const size_t lds = (size_t)2 * (x3 ? 4 : 2) * TN_TILE_BYTES;
+    p.nsplit = r.variant == 3 ? splits : (r.mt && !r.direct) ? splits : 0;       // whole-M: 0 marks "wrote C itself"; the 128x128 kernels do not read it
     float* part = (float*)workspace;
-    const int tnv = tn_variant(d);
-    if (tnv == 3) {
-        p.tiles_m = (d->M + 255) / 256; p.tiles_n = (d->N + 255) / 256;
-        p.nsplit = splits;
-        dim3 g256(p.tiles_m * p.tiles_n * splits, batch, 1), b256(512);
-        const size_t l256 = (size_t)4 * 2 * 32 * 256 * 2;
-#define TN256(SH, ST)                                                                                                  \
-    do {                                                                                                              \
-        (void)hipFuncSetAttribute((const void*)gemm_tn_256_kernel<SH, 4, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l256); \
-        hipLaunchKernelGGL((gemm_tn_256_kernel<SH, 4, ST>), g256, b256, l256, stream, p, part);                        \
-    } while (0)
-        // tuning key 8: 0 = auto = lock-step, 1 = lock-step, 2 = staggered wave rows.  With the DMA pieces issued through asm (common.h:
-        // the compiler no longer drains the ring before the fragment reads) the lock-step loop gained 15-27 % and passed the staggered
-        // one on every weight-gradient shape of the step (r02: dW qkv 466 -> 340 us vs 424 staggered; dW ff1 787 -> 608 vs 773)
-        const bool stag = g_amdnuwa_tuning[8] == 2;
-        if (!sh && tn_w4k_ok(d)) {                                               // four waves, 64 token rows per iteration (gemm_tn_w4k_kernel)
-            dim3 b4(256);
-            const size_t l4 = (size_t)2 * 2 * 64 * 256 * 2;
-            if (d->ab_f16) {
-                (void)hipFuncSetAttribute((const void*)gemm_tn_w4k_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4);
-                hipLaunchKernelGGL(gemm_tn_w4k_kernel<true>, g256, b4, l4, stream, p, part);
-            } else {
-                (void)hipFuncSetAttribute((const void*)gemm_tn_w4k_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4);
-                hipLaunchKernelGGL(gemm_tn_w4k_kernel<false>, g256, b4, l4, stream, p, part);
-            }
-        } else
-        if (sh) { if (stag) TN256(true, true); else TN256(true, false); }
-        else    { if (stag) TN256(false, true); else TN256(false, false); }
-#undef TN256
-    } else
-    if (tnv == 2 && tn_whole_m(d) != 0) {
-        const int mt = tn_whole_m(d);
+    const dim3 grid(p.tiles_m * p.tiles_n, batch, splits);
+    const auto go = [&](auto kernel, dim3 g, int threads, size_t lds, bool lds_attr) {
+        return launch_kernel(kernel, g, dim3(threads), lds, lds_attr, stream, p, part);
+    };
+    int rc;
+    if (r.variant == 3) {
+        const dim3 g256(p.tiles_m * p.tiles_n * splits, batch, 1);               // the grid is flattened over (split, tile)
+        if (r.w4k) rc = launch_if(d->ab_f16 != 0, [&](auto f16) { return go(gemm_tn_w4k_kernel<f16()>, g256, 256, (size_t)2 * 2 * 64 * 256 * 2, true); });
+        else rc = launch_if(sh, [&](auto s) { return launch_if(r.stagger, [&](auto st) {
+            return go(gemm_tn_256_kernel<s(), 4, st()>, g256, 512, (size_t)4 * 2 * 32 * 256 * 2, true); }); });
+    } else if (r.mt) {
         const dim3 gw(batch, splits);
-        const bool direct = splits == 1 && d->beta == 0.f && g_amdnuwa_tuning[25] != 2;      // (a device factor rides in the direct epilogue too)
-        p.nsplit = direct ? 0 : splits;
-#define TNWM(MT_, F_)                                                                                                    \
-    do {                                                                                                                 \
-        const size_t l = (size_t)4 * (MT_ + 1) * TN_TILE_BYTES;                                                          \
-        (void)hipFuncSetAttribute((const void*)gemm_tn_wm_kernel<MT_, 4, F_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l); \
-        hipLaunchKernelGGL((gemm_tn_wm_kernel<MT_, 4, F_>), gw, block, l, stream, p, part);                               \
-    } while (0)
-#define TNWMF(MT_, MI_, F_)                                                                                              \
-    do {                                                                                                                 \
-        const size_t l = (size_t)4 * (MT_ + 1) * TN_TILE_BYTES;                                                          \
-        (void)hipFuncSetAttribute((const void*)gemm_tn_wmf_kernel<MT_, MI_, F_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l); \
-        hipLaunchKernelGGL((gemm_tn_wmf_kernel<MT_, MI_, F_>), gw, block, l, stream, p, part);                            \
-    } while (0)
-        // the lean form: whole K-steps in every split, 32-bit piece offsets (tuning key 25 = 3 keeps the general kernel)
-        const bool lean = g_amdnuwa_tuning[25] != 3 && d->K % TK == 0 && (long long)((d->M + 31) / 32) * d->K * 64 < (1LL << 32) &&
-                          32LL * d->lda * 2 < (1LL << 31) && 32LL * d->ldb * 2 < (1LL << 31);
-        const int mi = ((d->M + 15) / 16 + 3) / 4;                                // row fragments per wave
-        if (lean) {
-            if (mt == 3) { if (mi == 5) { if (d->ab_f16) TNWMF(3, 5, true); else TNWMF(3, 5, false); } else { if (d->ab_f16) TNWMF(3, 6, true); else TNWMF(3, 6, false); } }
-            else         { if (mi == 3) { if (d->ab_f16) TNWMF(2, 3, true); else TNWMF(2, 3, false); } else { if (d->ab_f16) TNWMF(2, 4, true); else TNWMF(2, 4, false); } }
-        } else
-        if (mt == 3) { if (d->ab_f16) TNWM(3, true); else TNWM(3, false); }
-        else         { if (d->ab_f16) TNWM(2, true); else TNWM(2, false); }
-#undef TNWMF
-#undef TNWM
-    } else
-    if (tnv == 2) {
+        const size_t l = (size_t)4 * (r.mt + 1) * TN_TILE_BYTES;
+        rc = launch_if(d->ab_f16 != 0, [&](auto f16) {
+            if (r.lean) return r.mt == 3 ? (r.mi == 5 ? go(gemm_tn_wmf_kernel<3, 5, f16()>, gw, 256, l, true) : go(gemm_tn_wmf_kernel<3, 6, f16()>, gw, 256, l, true))
+                                         : (r.mi == 3 ? go(gemm_tn_wmf_kernel<2, 3, f16()>, gw, 256, l, true) : go(gemm_tn_wmf_kernel<2, 4, f16()>, gw, 256, l, true));
+            return r.mt == 3 ? go(gemm_tn_wm_kernel<3, 4, f16()>, gw, 256, l, true) : go(gemm_tn_wm_kernel<2, 4, f16()>, gw, 256, l, true);
+        });
+    } else if (r.variant == 2) {
         const size_t gl = (size_t)2 * 2 * TN_TILE_BYTES;
-        if (sh) hipLaunchKernelGGL((gemm_tn_glds_kernel<true>), grid, block, gl, stream, p, part);
-        else if (d->N <= 64) {
-            const size_t gl4 = (size_t)4 * 2 * TN_TILE_BYTES;
-            (void)hipFuncSetAttribute((const void*)gemm_tn_glds_kernel<false, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gl4);
-            hipLaunchKernelGGL((gemm_tn_glds_kernel<false, true, 4>), dim3(grid.x * grid.y, 1, grid.z), block, gl4, stream, p, part);
-        }
-        else    hipLaunchKernelGGL((gemm_tn_glds_kernel<false>), grid, block, gl, stream, p, part);
-    } else
-    if (x3) { if (sh) hipLaunchKernelGGL((gemm_tn_kernel<true, true>), grid, block, lds, stream, p, part);
-              else    hipLaunchKernelGGL((gemm_tn_kernel<true, false>), grid, block, lds, stream, p, part); }
-    else    { if (sh) hipLaunchKernelGGL((gemm_tn_kernel<false, true>), grid, block, lds, stream, p, part);
-              else    hipLaunchKernelGGL((gemm_tn_kernel<false, false>), grid, block, lds, stream, p, part); }
-    LAUNCH_CHECK();
-    if (tnv == 2 && tn_whole_m(d) != 0 && p.nsplit == 0) return AMDNUWA_OK;      // (the whole-M kernel wrote C itself)
+        if (sh) rc = go(gemm_tn_glds_kernel<true>, grid, 256, gl, false);
+        else if (d->N <= 64) rc = go(gemm_tn_glds_kernel<false, true, 4>, dim3(grid.x * grid.y, 1, grid.z), 256, (size_t)4 * 2 * TN_TILE_BYTES, true);   // the narrow form: a flattened grid
+        else rc = go(gemm_tn_glds_kernel<false>, grid, 256, gl, false);
+    } else {
+        rc = launch_if(x3, [&](auto lo) { return launch_if(sh, [&](auto s) {
+            return go(gemm_tn_kernel<lo(), s()>, grid, 256, (size_t)2 * (lo() ? 4 : 2) * TN_TILE_BYTES, false); }); });
+    }
+    if (rc) return rc;
+    if (r.mt && p.nsplit == 0) return AMDNUWA_OK;                                 // (the whole-M kernel wrote C itself)
     const size_t per = (size_t)d->M * d->N;
     int rb = (int)((per + 255) / 256); if (rb > 2048) rb = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rb, batch), dim3(256), 0, stream, part, (float*)d->C, (long long)d->strideC,
-                       (long long)d->strideC_inner, d->batch_inner, d->ldc, d->M, d->N, splits, d->alpha, d->beta, d->alpha_dev);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return launch_kernel(splitk_reduce_kernel, dim3(rb, batch), dim3(256), 0, false, stream, part, (float*)d->C, (long long)d->strideC,
+                         (long long)d->strideC_inner, d->batch_inner, d->ldc, d->M, d->N, splits, d->alpha, d->beta, d->alpha_dev);
 }
 
 AMDNUWA_SAT_ACCESSOR(gemm)

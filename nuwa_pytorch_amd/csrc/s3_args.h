@@ -72,17 +72,14 @@ inline S3Tile s3_tile(const amdnuwa_s3_geom* g) {
 // key slots of a query: slot 0 (<bos>, or the null key of SparseCross2DNA) + the kf*kh*kw window taps
 inline size_t s3_slots(const amdnuwa_s3_geom* g) { return (size_t)g->kf * g->kh * g->kw + 1; }
 
-// One launch of a window kernel: its dynamic-LDS allowance (set on every launch), the launch, the launch check.
+// One launch of a window kernel: launch_kernel() of common.h with the dynamic-LDS allowance set on every launch.
 template <class A>
 int s3_launch(void (*kernel)(A), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A& args) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return launch_kernel(kernel, grid, block, lds, true, stream, args);
 }
-// Run-time choices as compile-time parameters: f(std::true_type{}) or f(std::false_type{}); s3_dispatch() hands f the template parameters
+// Run-time choices as compile-time parameters (launch_if of common.h); s3_dispatch() hands f the template parameters
 // <DH, LO, DROP> of the VALU kernels as (std::integral_constant<int, 64 or 32>, bool constant, bool constant).
-template <class F> int s3_if(bool c, F&& f) { return c ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> int s3_if(bool c, F&& f) { return launch_if(c, f); }
 template <class F> int s3_dispatch(int dim_head, bool lo, bool drop, F&& f) {
     return s3_if(dim_head == 64, [&](auto d64) { return s3_if(lo, [&](auto lo_c) { return s3_if(drop, [&](auto dr) {
         return f(std::integral_constant<int, d64() ? 64 : 32>{}, lo_c, dr);

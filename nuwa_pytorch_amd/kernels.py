@@ -352,17 +352,25 @@ def gemm_nt(A, B, *, out=None, out_bf16=False, bias=None, alpha=1.0, shift=None,
             # u's lo part (a third of this GEMM's output bytes) is never needed, so it is not written
             out = BF(out.hi, None)
             d.Clo = None
-    st = _stream()
+    ob = (2 * (2 if out.lo is not None else 1)) if out_bf16 else 4
+    _nt_call(d, 'amdnuwa_gemm_nt', 2.0 * M * N * K, 3 if x3 else 1,
+             (2.0 * (M + N) * K) * (2 if x3 else 1) + float(M) * N * ob + (float(M) * N if geglu_out is not None else 0.))
+    return out
+
+
+def _nt_call(d, label, flops, issued_factor, nbytes):
+    """amdnuwa_gemm_nt on descriptor d, counted by the step timer: flops = the ALGORITHMIC 2 M N K (one product per (m, n, k) whatever the
+    operand form), issued_factor = MFMAs per product (3 for hi + lo pairs on both sides, 2 for the fp16 x fp16 hi + lo form), nbytes = the
+    operand and output bytes of the call"""
+    L, st = _lib.lib(), _stream()
     if _TIMER['on']:
-        _TIMER['flops'] += 2.0 * M * N * K                     # ALGORITHMIC: one product per (m, n, k) whatever the operand form
-        _TIMER['issued'] = _TIMER.get('issued', 0.) + 2.0 * M * N * K * (3 if x3 else 1)
-        ob = (2 * (2 if out.lo is not None else 1)) if out_bf16 else 4
-        _TIMER['bytes'] += (2.0 * (M + N) * K) * (2 if x3 else 1) + float(M) * N * ob + (float(M) * N if geglu_out is not None else 0.)
+        _TIMER['flops'] += flops
+        _TIMER['issued'] = _TIMER.get('issued', 0.) + flops * issued_factor
+        _TIMER['bytes'] += nbytes
         _TIMER['tags'].append('gemm_nt'); L.amdnuwa_timer_begin(st)
-    check(L.amdnuwa_gemm_nt(C.byref(d), st), 'amdnuwa_gemm_nt')
+    check(L.amdnuwa_gemm_nt(C.byref(d), st), label)
     if _TIMER['on']:
         L.amdnuwa_timer_end(st)
-    return out
 
 
 def _gemm_nt_f16(A, B, *, bias, alpha, shift, N, K):
@@ -385,15 +393,7 @@ def _gemm_nt_f16(A, B, *, bias, alpha, shift, N, K):
         # shapes outside the hi + lo ring (small M, token shift in the loader): plain hi + lo product, then one conversion pass
         full = gemm_nt(A, B, out_bf16=True, bias=bias, alpha=alpha, shift=shift, N=N, K=K)
         return BF(full.hi, None, hilo_to_f16(full))
-    st = _stream()
-    if _TIMER['on']:
-        _TIMER['flops'] += 2.0 * M * N * K
-        _TIMER['issued'] = _TIMER.get('issued', 0.) + 6.0 * M * N * K
-        _TIMER['bytes'] += 4.0 * (M + N) * K + 4.0 * M * N
-        _TIMER['tags'].append('gemm_nt'); L.amdnuwa_timer_begin(st)
-    check(L.amdnuwa_gemm_nt(C.byref(d), st), 'amdnuwa_gemm_nt(f16 copy)')
-    if _TIMER['on']:
-        L.amdnuwa_timer_end(st)
+    _nt_call(d, 'amdnuwa_gemm_nt(f16 copy)', 2.0 * M * N * K, 3, 4.0 * (M + N) * K + 4.0 * M * N)
     return BF(hi, None, f16)
 
 
@@ -422,22 +422,28 @@ def _f16ops_desc(A16, B16, M, N, Kd):
 def gemm_nt_f16ops_ok(M, N, Kd, *, out_bf16, gate=False, out_f16=False, geglu_bwd=False):
     """will amdnuwa_gemm_nt take this product with fp16 operands (the 256x256 ring at training sizes)?  out_f16: one fp16 output;
     geglu_bwd: the product is dgg [M, N] and the epilogue writes du fp16 [M, 2 N] from u [M, 2 N]"""
-    d = GemmDesc()
-    one = ctypes_dummy()
-    d.A, d.B, d.C = one, one, one
-    d.lda, d.ldb, d.ldc = Kd, Kd, N
+    d, one = _query_desc(M, N, Kd, Kd, Kd, N)
     d.c_is_bf16 = 1 if (out_bf16 or out_f16 or geglu_bwd) else 0
     d.c_f16 = 1 if (out_f16 or geglu_bwd) else 0
     if geglu_bwd:
         d.C2, d.ldc2, d.geglu_u, d.ld_u = one, 2 * N, one, 2 * N
     if gate:
         d.C2, d.ldc2 = one, N // 2
-    d.M, d.N, d.K, d.batch, d.ab_f16 = M, N, Kd, 1, 1
     return bool(_lib.lib().amdnuwa_gemm_nt_f16ops_supported(C.byref(d)))
 
 
 def ctypes_dummy():
     return 16          # any non-null, 16-byte aligned address: the query never dereferences
+
+
+def _query_desc(M, N, Kd, lda, ldb, ldc):
+    """descriptor of an unbatched fp16-operand product for a support query: dummy operand pointers (returned too), the given leading dimensions"""
+    d = GemmDesc()
+    one = ctypes_dummy()
+    d.A, d.B, d.C = one, one, one
+    d.lda, d.ldb, d.ldc = lda, ldb, ldc
+    d.M, d.N, d.K, d.batch, d.ab_f16 = M, N, Kd, 1, 1
+    return d, one
 
 
 _QKV_F16 = os.environ.get('AMDNUWA_F16_QKV', '1') != '0'
@@ -492,19 +498,15 @@ def f16_pair(w):
 
 
 def gemm_nt_f16x2_ok(M, N, Kd, *, out_bf16):
-    d = GemmDesc()
-    one = ctypes_dummy()
-    d.A, d.B, d.Blo, d.C = one, one, one, one
-    d.lda, d.ldb, d.ldc = Kd, Kd, N
+    d, one = _query_desc(M, N, Kd, Kd, Kd, N)
+    d.Blo = one
     d.c_is_bf16 = 1 if out_bf16 else 0
-    d.M, d.N, d.K, d.batch, d.ab_f16 = M, N, Kd, 1, 1
     return bool(_lib.lib().amdnuwa_gemm_nt_f16x2_supported(C.byref(d)))
 
 
 def gemm_nt_f16x2(A16, B16, *, out_bf16=False, bias=None, copy_f16=False, out_f16=False):
     """two-MFMA product: A16 fp16 [M, K] x (B16 = (hi, lo) fp16 [N, K] pair)^T.  out_bf16=False -> fp32 [M, N] (+ bias);
     out_bf16=True -> BF(bf16 copy, None, fp16 copy if copy_f16); out_f16=True -> ONE fp16 [M, N] tensor (saturating)"""
-    L = _lib.lib()
     M, Kd = A16.shape
     Bh, Bl = B16
     N = Bh.shape[0]
@@ -528,15 +530,8 @@ def gemm_nt_f16x2(A16, B16, *, out_bf16=False, bias=None, copy_f16=False, out_f1
     else:
         out = torch.empty((M, N), dtype=torch.float32, device=dev)
         d.C, d.ldc, d.c_is_bf16 = _p(out), N, 0
-    st = _stream()
-    if _TIMER['on']:
-        _TIMER['flops'] += 2.0 * M * N * Kd
-        _TIMER['issued'] = _TIMER.get('issued', 0.) + 4.0 * M * N * Kd
-        _TIMER['bytes'] += 2.0 * M * Kd + 4.0 * N * Kd + float(M) * N * ((4 if c16 is not None else 2) if out_bf16 else 4)
-        _TIMER['tags'].append('gemm_nt'); L.amdnuwa_timer_begin(st)
-    check(L.amdnuwa_gemm_nt(C.byref(d), st), 'amdnuwa_gemm_nt(f16 x f16 hi+lo)')
-    if _TIMER['on']:
-        L.amdnuwa_timer_end(st)
+    _nt_call(d, 'amdnuwa_gemm_nt(f16 x f16 hi+lo)', 2.0 * M * N * Kd, 2,
+             2.0 * M * Kd + 4.0 * N * Kd + float(M) * N * ((4 if c16 is not None else 2) if out_bf16 else 4))
     if out_f16:
         return out
     return BF(out, None, c16) if out_bf16 else out
@@ -547,7 +542,6 @@ def gemm_nt_f16ops(A16, B16, *, out_bf16=False, gate=False, copy_f16=False, gate
     out_bf16=False -> fp32 [M, N].  out_bf16=True -> u bf16 [M, N]; with gate=True also (gg16 fp16 [M, N/2], gg bf16 [M, N/2] or None when
     gate_bf16 is off) = a * gelu(gate) computed on the fp32 accumulators (u in the interleaved-by-8 layout); with copy_f16=True ->
     BF(bf16 copy, None, fp16 copy).  out_f16=True -> ONE fp16 [M, N] output, saturating (dgrad products of the fp16-gradient backward)."""
-    L = _lib.lib()
     M, Kd = A16.shape
     N = B16.shape[0]
     dev = A16.device
@@ -571,15 +565,8 @@ def gemm_nt_f16ops(A16, B16, *, out_bf16=False, gate=False, copy_f16=False, gate
     else:
         out = torch.empty((M, N), dtype=torch.float32, device=dev)
         d.C, d.ldc, d.c_is_bf16 = _p(out), N, 0
-    st = _stream()
-    if _TIMER['on']:
-        _TIMER['flops'] += 2.0 * M * N * Kd
-        _TIMER['issued'] = _TIMER.get('issued', 0.) + 2.0 * M * N * Kd
-        _TIMER['bytes'] += 2.0 * (M + N) * Kd + float(M) * N * (2 if (out_bf16 or out_f16) else 4) + ((2.0 if gate_bf16 else 1.0) * M * N if gate else 0.)
-        _TIMER['tags'].append('gemm_nt'); L.amdnuwa_timer_begin(st)
-    check(L.amdnuwa_gemm_nt(C.byref(d), st), 'amdnuwa_gemm_nt(fp16 operands)')
-    if _TIMER['on']:
-        L.amdnuwa_timer_end(st)
+    _nt_call(d, 'amdnuwa_gemm_nt(fp16 operands)', 2.0 * M * N * Kd, 1,
+             2.0 * (M + N) * Kd + float(M) * N * (2 if (out_bf16 or out_f16) else 4) + ((2.0 if gate_bf16 else 1.0) * M * N if gate else 0.))
     if copy_f16:
         return BF(out, None, c16)
     return (out, gg16, ggb) if gate else out
@@ -605,22 +592,13 @@ def gemm_nt_geglu_bwd(dy, w2T, u, FP):
     if not L.amdnuwa_gemm_nt_fused(C.byref(d)):
         dgg = empty_bf((M, FP), dev, lo=x3 or want_lo())
         d.C, d.Clo = _p(dgg.hi), _p(dgg.lo)
-    st = _stream()
-    if _TIMER['on']:
-        _TIMER['flops'] += 2.0 * M * FP * Kd
-        _TIMER['issued'] = _TIMER.get('issued', 0.) + 2.0 * M * FP * Kd * (3 if x3 else 1)
-        _TIMER['bytes'] += (2.0 * (M + FP) * Kd) * (2 if x3 else 1) + float(M) * FP * 8
-        _TIMER['tags'].append('gemm_nt'); L.amdnuwa_timer_begin(st)
-    check(L.amdnuwa_gemm_nt(C.byref(d), st), 'amdnuwa_gemm_nt(geglu backward)')
-    if _TIMER['on']:
-        L.amdnuwa_timer_end(st)
+    _nt_call(d, 'amdnuwa_gemm_nt(geglu backward)', 2.0 * M * FP * Kd, 3 if x3 else 1, (2.0 * (M + FP) * Kd) * (2 if x3 else 1) + float(M) * FP * 8)
     return du
 
 
 def gemm_nt_geglu_bwd16(dy16, w2T16, u, FP):
     """fp16-gradient form of gemm_nt_geglu_bwd: dy16 fp16 [M, D] (= S * dy), w2T16 fp16 [FP, D], u bf16 [M, 2 FP] (interleaved) ->
     du fp16 [M, 2 FP] (= S * du), the gate's backward in the GEMM epilogue"""
-    L = _lib.lib()
     M, Kd = dy16.shape
     du = torch.empty((M, 2 * FP), dtype=torch.float16, device=dy16.device)
     d = _f16ops_desc(dy16, w2T16, M, FP, Kd)
@@ -628,15 +606,7 @@ def gemm_nt_geglu_bwd16(dy16, w2T16, u, FP):
     d.C2, d.ldc2 = _p(du), 2 * FP
     d.geglu_u, d.ld_u = _p(u), _ld(u)
     d.C = _p(du)                                      # placeholder: the fused epilogue does not write C
-    st = _stream()
-    if _TIMER['on']:
-        _TIMER['flops'] += 2.0 * M * FP * Kd
-        _TIMER['issued'] = _TIMER.get('issued', 0.) + 2.0 * M * FP * Kd
-        _TIMER['bytes'] += 2.0 * (M + FP) * Kd + float(M) * FP * 8
-        _TIMER['tags'].append('gemm_nt'); L.amdnuwa_timer_begin(st)
-    check(L.amdnuwa_gemm_nt(C.byref(d), st), 'amdnuwa_gemm_nt(geglu backward, fp16)')
-    if _TIMER['on']:
-        L.amdnuwa_timer_end(st)
+    _nt_call(d, 'amdnuwa_gemm_nt(geglu backward, fp16)', 2.0 * M * FP * Kd, 1, 2.0 * (M + FP) * Kd + float(M) * FP * 8)
     return du
 
 
@@ -650,32 +620,24 @@ def _tn16_desc(A16, B16, out, N1, N2):
 
 def gemm_tn16_ok(R, N1, N2, lda=None, ldb=None):
     """does amdnuwa_gemm_tn take [R, N1]^T [R, N2] with fp16 operands (the four-wave kernel's shapes)?"""
-    d = GemmDesc()
-    one = ctypes_dummy()
-    d.A, d.B, d.C = one, one, one
-    d.lda, d.ldb, d.ldc = (N1 if lda is None else lda), (N2 if ldb is None else ldb), N2
-    d.M, d.N, d.K, d.batch, d.ab_f16 = N1, N2, R, 1, 1
+    d, _ = _query_desc(N1, N2, R, (N1 if lda is None else lda), (N2 if ldb is None else ldb), N2)
     return bool(_lib.lib().amdnuwa_gemm_tn_f16_supported(C.byref(d)))
 
 
 def gemm_tn16(A16, B16, out, s2, *, alpha=1.0, beta=0.0, N1=None, N2=None):
     """out[N1, N2] (fp32) = beta * out + alpha / S * A16[R, N1]^T @ B16[R, N2]: a weight gradient from an fp16 gradient (A16 = S * dY) and
     an fp16 activation copy; s2 = device {S, 1 / S} (None: no scale)"""
-    L = _lib.lib()
     N1 = A16.shape[1] if N1 is None else N1
     N2 = B16.shape[1] if N2 is None else N2
     d = _tn16_desc(A16, B16, out, N1, N2)
     d.alpha, d.beta = float(alpha), float(beta)
     d.alpha_dev = None if s2 is None else s2.data_ptr() + 4
-    nb = L.amdnuwa_gemm_tn_workspace_bytes(C.byref(d))
-    ws = workspace(nb, A16.device)
-    check(L.amdnuwa_gemm_tn(C.byref(d), _p(ws), nb, _stream()), 'amdnuwa_gemm_tn(fp16)')
+    _tn_call(d, A16.device, 'amdnuwa_gemm_tn(fp16)')
     return out
 
 
 def gemm_tn(A, B, out, *, alpha=1.0, beta=0.0, shift=None, N1=None, N2=None):
     """out[N1,N2] (fp32 view) = beta*out + alpha * A[R,N1]^T @ B[R,N2]; shift applies to B's loader."""
-    L = _lib.lib()
     R = A.hi.shape[0]
     N1 = A.hi.shape[1] if N1 is None else N1
     N2 = B.hi.shape[1] if N2 is None else N2
@@ -688,17 +650,20 @@ def gemm_tn(A, B, out, *, alpha=1.0, beta=0.0, shift=None, N1=None, N2=None):
     d.M, d.N, d.K, d.batch = N1, N2, R, 1
     if shift is not None:
         d.shift_ntok, d.shift_fmap = int(shift[0]), int(shift[1])
-    nb = L.amdnuwa_gemm_tn_workspace_bytes(C.byref(d))
-    ws = workspace(nb, A.hi.device)
-    check(L.amdnuwa_gemm_tn(C.byref(d), _p(ws), nb, _stream()), 'amdnuwa_gemm_tn')
+    _tn_call(d, A.hi.device, 'amdnuwa_gemm_tn')
     return out
 
 
 def gemm_tn_batched(desc, device):
+    _tn_call(desc, device, 'amdnuwa_gemm_tn(batched)')
+
+
+def _tn_call(d, device, label):
+    """amdnuwa_gemm_tn on descriptor d, with the split-K workspace the library asks for"""
     L = _lib.lib()
-    nb = L.amdnuwa_gemm_tn_workspace_bytes(C.byref(desc))
+    nb = L.amdnuwa_gemm_tn_workspace_bytes(C.byref(d))
     ws = workspace(nb, device)
-    check(L.amdnuwa_gemm_tn(C.byref(desc), _p(ws), nb, _stream()), 'amdnuwa_gemm_tn(batched)')
+    check(L.amdnuwa_gemm_tn(C.byref(d), _p(ws), nb, _stream()), label)
 
 
 # ------------------------------------------------------------------------------------------------
