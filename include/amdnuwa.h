@@ -658,6 +658,31 @@ int amdnuwa_cattn_bwd(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, c
                       const uint16_t* dO, int lddo, const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th,
                       const float* stats, uint16_t* dq, int lddq, uint16_t* dk, uint16_t* dv, int lddkv, float* dw_th, float* dnull_k,
                       float* dnull_v, void* workspace, size_t workspace_bytes, amdnuwa_stream stream);
+/* Attention dropout inside the cattn kernels (added at ABI 21, purely additive; np.py:370-374, `self.dropout(self.talking_heads(attn))`:
+ * the mask acts AFTER the talking-heads mix).  With M[g][i][j] in {0, 1} the keep bit of output head g, query i, key row j, M0[g][i] that
+ * of the null slot and s = drop_scale = 1 / (1 - p):
+ *   forward   A''[g] = M . s . A'[g] feeds the product with V (A' = the mixed probabilities), the null term takes M0 . s . A'0[g];
+ *   backward  dv = A''^T dO;  dA'[g] = M . s . (dO_g . V_g) and dA'0[g] = M0 . s . (dO_g . null_v_g) before anything reads them, so delta,
+ *             dq, dk, dW_th and dnull_k follow unchanged; dnull_v sums the masked A'0.  The statistics pass is untouched.
+ * The caller draws the mask and hands the SAME arrays to the forward and the backward; one byte per (query, key) pair, bit g set = head g kept:
+ *   keep   [B][n][KP], KP = 32 * ceil(T / 32)   read by the query-stationary sweeps (forward, delta, dq)
+ *   keep_t [B][T][NP], NP = 32 * ceil(n / 32)   the same bytes transposed, read by the key-stationary sweeps (dk, dv)
+ *   keep0  [B][n]                               the null slot
+ * uint8, every base 4-byte aligned (a lane's eight streamed rows are two aligned 32-bit loads per tile on either side).  Padding bytes, bits
+ * at or above `heads`, and the bytes of masked or causally hidden pairs never influence an output.  An all-ones mask with drop_scale = 1
+ * gives the bits of the unmasked calls.  Envelope = amdnuwa_cattn_supported (amdnuwa_cattn_drop_supported answers the same); a NULL or
+ * misaligned mask array, or a drop_scale that is not finite or below 1: AMDNUWA_ERR_ARG before anything is launched.  _bwd_drop runs on the
+ * workspace amdnuwa_cattn_bwd_workspace_bytes reports. */
+int amdnuwa_cattn_drop_supported(const amdnuwa_cattn_geom* g);
+int amdnuwa_cattn_fwd_drop(const amdnuwa_cattn_geom* g, const uint16_t* q16, int ldq, const uint16_t* k16, const uint16_t* v16, int ldkv,
+                           const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o, uint16_t* o_lo,
+                           int ldo, int o_lo_f16, float* stats, int f16, const uint8_t* keep, const uint8_t* keep0, float drop_scale,
+                           amdnuwa_stream stream);
+int amdnuwa_cattn_bwd_drop(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, const uint16_t* k, const uint16_t* v, int ldkv,
+                           const uint16_t* dO, int lddo, const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th,
+                           const float* stats, uint16_t* dq, int lddq, uint16_t* dk, uint16_t* dv, int lddkv, float* dw_th, float* dnull_k,
+                           float* dnull_v, void* workspace, size_t workspace_bytes, const uint8_t* keep, const uint8_t* keep_t,
+                           const uint8_t* keep0, float drop_scale, amdnuwa_stream stream);
 /* Text cross-attention (Attention.forward with context, np.py:339-378) for ONE query row per sample (g->n must be 1):
  * q [B, ldq] unscaled, keys / values as packed by amdnuwa_xattn_pack (Kp / Vp images and the valid map), o [B, ldo]. */
 int amdnuwa_xattn_decode(const amdnuwa_xattn_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq,

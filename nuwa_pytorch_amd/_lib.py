@@ -164,6 +164,9 @@ SIGNATURES = {
     'amdnuwa_cattn_fwd': (I, [CG, P, I, P, P, I, P, P, P, P, P, P, I, I, P, I, P]),
     'amdnuwa_cattn_bwd_workspace_bytes': (SZ, [CG]),
     'amdnuwa_cattn_bwd': (I, [CG, P, I, P, P, I, P, I, P, P, P, P, P, P, I, P, P, I, P, P, P, P, SZ, P]),
+    'amdnuwa_cattn_drop_supported': (I, [CG]),
+    'amdnuwa_cattn_fwd_drop': (I, [CG, P, I, P, P, I, P, P, P, P, P, P, I, I, P, I, P, P, F, P]),
+    'amdnuwa_cattn_bwd_drop': (I, [CG, P, I, P, P, I, P, I, P, P, P, P, P, P, I, P, P, I, P, P, P, P, SZ, P, P, P, F, P]),
     'amdnuwa_xattn2_bwd_rc_supported': (I, [XG]),
     'amdnuwa_xattn2_bwd_rc_stats_bytes': (SZ, [XG]),
     'amdnuwa_xattn2_bwd_rc': (I, [XG, P, I, P, I, XK, P, P, P, I, P, SZ, P, SZ, P, P, P]),

@@ -24,6 +24,8 @@
 // ones ceil(nk / 64) workgroups over ceil(n / 32) query tiles; row bases and ragged-tile predicates are per side (Item).
 // Causal: key tiles above the diagonal are never staged; a wave skips tiles that lie wholly above its own 16 rows; the predicate is per element.
 // No atomics: dW_th / dnull_k / dnull_v leave as per-workgroup partials reduced in a fixed order (amdnuwa_colsum).
+// Attention dropout (template parameter DROP, amdnuwa_cattn_fwd_drop / _bwd_drop): the keep mask multiplies the MIXED probabilities in the one
+// place each sweep holds them in registers -- see CDropArgs.  The unmasked instantiations keep their kernel argument and their code.
 #include "common.h"
 #include "../../include/amdnuwa.h"
 
@@ -57,6 +59,29 @@ struct CArgs {
     float c1, scale;                         // scale * log2(e), scale
 };
 
+// Attention dropout (the DROP forms; np.py:370-374, after the talking-heads mix): A''[g] = keep . s . A'[g] feeds the V product and dv,
+// dA'[g] = keep . s . dA''[g] everything of the backward.  One byte per (query, key) pair, bit g = output head g kept; the query-stationary
+// sweeps read keep [B][n][KP], the key-stationary ones the same bytes transposed, keep_t [B][nk][NP] (KP / NP = the key / query count
+// rounded up to 32), so a lane's eight streamed rows (yrow) are two aligned 32-bit loads per tile on either side; keep0 [B][n] is the null
+// slot.  Only the DROP instantiations take the extra words: the kernel argument of the unmasked ones stays CArgs itself.
+struct CDropArgs : CArgs { const uint8_t *keep, *keep_t, *keep0; int KP, NP; float drop_s; };
+template <bool DROP> struct CKArgsSel { using type = CArgs; };
+template <> struct CKArgsSel<true> { using type = CDropArgs; };
+template <bool DROP> using CKArgs = typename CKArgsSel<DROP>::type;
+// the mask of a dropout call (keep == NULL: an unmasked call)
+struct CMask { const uint8_t *keep, *keep_t, *keep0; float s; };
+template <bool DROP> inline CKArgs<DROP> c_kargs(const CArgs& a, const CMask& mk) {
+    if constexpr (DROP) {
+        CDropArgs d{};
+        static_cast<CArgs&>(d) = a;
+        d.keep = mk.keep; d.keep_t = mk.keep_t; d.keep0 = mk.keep0; d.drop_s = mk.s;
+        d.KP = (a.nk + YT - 1) / YT * YT; d.NP = (a.n + YT - 1) / YT * YT;
+        return d;
+    } else {
+        return a;
+    }
+}
+
 __device__ __forceinline__ bf16x8 lds16(const char* p) { return *reinterpret_cast<const bf16x8*>(p); }
 __device__ __forceinline__ bf16x8 ldfrag(const uint16_t* p, bool ok) {
     u32x4 z = {0u, 0u, 0u, 0u};
@@ -75,6 +100,20 @@ template <bool F16> __device__ __forceinline__ bf16x8 pack8(const float (&v)[8])
 __device__ __forceinline__ int slot_of(int y) { return 8 * ((y & 15) >> 2) + 4 * (y >> 4) + (y & 3); }
 // tile row of a lane's value e
 __device__ __forceinline__ int yrow(int g4, int e) { return (e < 4 ? 4 * g4 + e : 12 + 4 * g4 + e); }
+// DROP forms: the keep bytes of a lane's stationary row `row` (an in-range row of keep / keep_t, pitch bytes each) at its eight streamed rows
+// of the tile at y0 -- yrow: bytes y0 + 4 g4 .. + 3 and y0 + 16 + 4 g4 .. + 3, inside the pitch because it is a multiple of the tile
+__device__ __forceinline__ uint2 keep_words(const uint8_t* __restrict__ base, long row, int pitch, bool rin, int y0, int g4) {
+    uint2 kw = make_uint2(0u, 0u);
+    if (rin) {
+        const uint8_t* p = base + row * pitch + y0 + 4 * g4;
+        kw.x = *reinterpret_cast<const uint32_t*>(p); kw.y = *reinterpret_cast<const uint32_t*>(p + 16);
+    }
+    return kw;
+}
+// value e of head g under dropout: v . s where the mask keeps it, exactly 0 where it drops it
+__device__ __forceinline__ float keep_apply(const uint2& kw, int g, int e, float s, float v) {
+    return (((e < 4 ? kw.x : kw.y) >> (8 * (e & 3) + g)) & 1u) ? v * s : 0.f;
+}
 
 // 32 rows [row0, row0 + 32) x inner columns of the sample's 16-bit rows -> LDS: row-major copy (pitch bytes per row) and / or the
 // transposed copy [column][slot].  Rows beyond the sequence are zeros.  Four loads in flight per thread, then their LDS stores.
@@ -180,8 +219,8 @@ __device__ __forceinline__ float null_dot(const bf16x8 (&xf)[DH / 32], const flo
 }
 
 // ---- forward (KEYSIDE = false: statistics pass, then o = A V) and the dv sweep (KEYSIDE = true: dv = A^T dO) ----------------------
-template <int DH, bool F16, bool KEYSIDE>
-__global__ __launch_bounds__(256, 1) void cattn_apply_kernel(CArgs a) {
+template <int DH, bool F16, bool KEYSIDE, bool DROP = false>
+__global__ __launch_bounds__(256, 1) void cattn_apply_kernel(CKArgs<DROP> a) {
     constexpr int KS = DH / 32, DB = DH / 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, g4 = lane >> 4;
@@ -290,6 +329,8 @@ __global__ __launch_bounds__(256, 1) void cattn_apply_kernel(CArgs a) {
         __syncthreads();
         if (a.causal && (KEYSIDE ? (y0 + YT - 1 < xw) : (y0 > xw + 15))) continue;
         const unsigned vm = valid_bits<KEYSIDE>(a, x, xok, y0, g4, KEYSIDE ? 0u : *svb);
+        uint2 kw = make_uint2(0u, 0u);                   // DROP: in flight under the probabilities, read by the mix
+        if constexpr (DROP) kw = keep_words(KEYSIDE ? a.keep_t : a.keep, rowb + x, KEYSIDE ? a.NP : a.KP, xin, y0, g4);
         float p[NHM][8];
 #pragma unroll
         for (int h = 0; h < NHM; ++h) {
@@ -317,6 +358,7 @@ __global__ __launch_bounds__(256, 1) void cattn_apply_kernel(CArgs a) {
 #pragma unroll
                     for (int h = 0; h < NHM; ++h) v = fmaf(w[g][h], p[h][e], v);
                     am[e] = v;
+                    if constexpr (DROP) am[e] = keep_apply(kw, g, e, a.drop_s, v);
                 }
                 const bf16x8 bm = pack8<F16>(am);
 #pragma unroll
@@ -332,12 +374,15 @@ __global__ __launch_bounds__(256, 1) void cattn_apply_kernel(CArgs a) {
         float p0[NHM], amax = 0.f;
 #pragma unroll
         for (int h = 0; h < NHM; ++h) p0[h] = h < heads ? __builtin_amdgcn_exp2f(s0[h] - m[h]) * il[h] : 0.f;
+        unsigned k0 = 0;                                 // DROP: the null slot's keep byte of the lane's query
+        if constexpr (DROP) k0 = xin ? a.keep0[rowb + x] : 0u;
 #pragma unroll
         for (int g = 0; g < NHM; ++g) {
             if (g < heads) {
                 float a0 = 0.f;
 #pragma unroll
                 for (int h = 0; h < NHM; ++h) a0 = fmaf(w[g][h], p0[h], a0);
+                if constexpr (DROP) a0 = ((k0 >> g) & 1u) ? a0 * a.drop_s : 0.f;
 #pragma unroll
                 for (int db = 0; db < DB; ++db) {
                     const int d = 16 * db + 4 * g4;
@@ -374,8 +419,8 @@ __global__ __launch_bounds__(256, 1) void cattn_apply_kernel(CArgs a) {
 }
 
 // ---- backward sweeps on bf16 operands.  MODE 0 (query side): delta, dW_th partials, the null key's terms.  MODE 1: dq (query side) / dk (key side)
-template <int DH, bool KEYSIDE, int MODE>
-__global__ __launch_bounds__(256, 1) void cattn_grad_kernel(CArgs a) {
+template <int DH, bool KEYSIDE, int MODE, bool DROP = false>
+__global__ __launch_bounds__(256, 1) void cattn_grad_kernel(CKArgs<DROP> a) {
     constexpr int KS = DH / 32, DB = DH / 16;
     static_assert(MODE == 1 || !KEYSIDE, "the delta sweep is query-stationary");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -451,12 +496,21 @@ __global__ __launch_bounds__(256, 1) void cattn_grad_kernel(CArgs a) {
         __syncthreads();
         if (a.causal && (KEYSIDE ? (y0 + YT - 1 < xw) : (y0 > xw + 15))) continue;
         const unsigned vm = valid_bits<KEYSIDE>(a, x, xok, y0, g4, KEYSIDE ? 0u : *svb);
+        uint2 kw = make_uint2(0u, 0u);                   // DROP: read by the dA loop only, dead before the probabilities
+        if constexpr (DROP) kw = keep_words(KEYSIDE ? a.keep_t : a.keep, rowb + x, KEYSIDE ? a.NP : a.KP, xin, y0, g4);
         float dA[NHM][8];
 #pragma unroll
         for (int g = 0; g < NHM; ++g) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) dA[g][e] = 0.f;
-            if (g < heads) { score8<DH, false>(rm2, pitch, g, r16, g4, xf2[g], dA[g]); HEAD_FENCE(); }
+            if (g < heads) {
+                score8<DH, false>(rm2, pitch, g, r16, g4, xf2[g], dA[g]);
+                if constexpr (DROP) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) dA[g][e] = keep_apply(kw, g, e, a.drop_s, dA[g][e]);
+                }
+                HEAD_FENCE();
+            }
         }
 #pragma unroll
         for (int h = 0; h < NHM; ++h) {
@@ -501,6 +555,8 @@ __global__ __launch_bounds__(256, 1) void cattn_grad_kernel(CArgs a) {
         // the null key: dA0_g = dO_g . null_v_g, P0_h from the statistics; delta gets its term, then dS0 and the mixed A0 leave for the dq sweep
         // and for the null key / value gradients
         float p0[NHM], dA0[NHM];
+        unsigned k0 = 0;                                 // DROP: the null slot's keep byte of the lane's query
+        if constexpr (DROP) k0 = xin ? a.keep0[rowb + x] : 0u;
 #pragma unroll
         for (int h = 0; h < NHM; ++h) {
             p0[h] = 0.f; dA0[h] = 0.f;
@@ -508,6 +564,7 @@ __global__ __launch_bounds__(256, 1) void cattn_grad_kernel(CArgs a) {
                 const float s0 = a.c1 * null_dot<DH, false>(xf1[h], a.null_k, h, g4);
                 p0[h] = xin ? __builtin_amdgcn_exp2f(s0 - m[h]) * il[h] : 0.f;
                 dA0[h] = null_dot<DH, false>(xf2[h], a.null_v, h, g4);
+                if constexpr (DROP) dA0[h] = ((k0 >> h) & 1u) ? dA0[h] * a.drop_s : 0.f;
                 dl[h] += __shfl_xor(dl[h], 16, 64);
                 dl[h] += __shfl_xor(dl[h], 32, 64);
             }
@@ -518,6 +575,7 @@ __global__ __launch_bounds__(256, 1) void cattn_grad_kernel(CArgs a) {
                 float dP0 = 0.f, a0 = 0.f;
 #pragma unroll
                 for (int g = 0; g < NHM; ++g) { dP0 = fmaf(w[g][h], dA0[g], dP0); a0 = fmaf(w[h][g], p0[g], a0); }
+                if constexpr (DROP) a0 = ((k0 >> h) & 1u) ? a0 * a.drop_s : 0.f;
                 dl[h] = fmaf(p0[h], dP0, dl[h]);
                 if (g4 == 0) {
 #pragma unroll
@@ -595,8 +653,8 @@ size_t lds_grad(const amdnuwa_cattn_geom* g, int mode) {
     const size_t inner = (size_t)g->heads * g->dim_head;
     return 2 * YT * (inner * 2 + 16) + (mode ? inner * TP : 256 * 65 * 4) + 3 * NHM * YT * 4 + 16 + 4 * 64 * 4;
 }
-template <typename Kern>
-void launch(Kern kern, int grid, size_t lds, hipStream_t stream, const CArgs& a) {
+template <typename Kern, typename KA>
+void launch(Kern kern, int grid, size_t lds, hipStream_t stream, const KA& a) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
 }
@@ -606,51 +664,59 @@ long long wgs_k(const amdnuwa_cattn_geom* g) { return (long long)g->B * ((keys_o
 long long null_chunks(const amdnuwa_cattn_geom* g) { return ((long long)g->B * g->n + 255) / 256; }
 size_t al(size_t v) { return (v + 255) / 256 * 256; }
 
-}  // namespace
 
-extern "C" int amdnuwa_cattn_supported(const amdnuwa_cattn_geom* g) { return check_c(g) == AMDNUWA_OK; }
+// the mask arguments of a dropout entry: every array present and 4-byte aligned (the kernels read 32-bit words of keep / keep_t), s = 1 / (1 - p) >= 1
+int check_mask(const CMask& mk, bool bwd) {
+    if (!mk.keep || !mk.keep0 || (bwd && !mk.keep_t)) return AMDNUWA_ERR_ARG;
+    if (((uintptr_t)mk.keep | (uintptr_t)mk.keep0 | (bwd ? (uintptr_t)mk.keep_t : 0)) & 3) return AMDNUWA_ERR_ARG;
+    if (!(mk.s >= 1.f) || mk.s > 3.0e38f) return AMDNUWA_ERR_ARG;                           // (NaN fails the first comparison)
+    return AMDNUWA_OK;
+}
 
-extern "C" int amdnuwa_cattn_fwd(const amdnuwa_cattn_geom* g, const uint16_t* q16, int ldq, const uint16_t* k16, const uint16_t* v16, int ldkv,
-                                 const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o, uint16_t* o_lo,
-                                 int ldo, int o_lo_f16, float* stats, int f16, hipStream_t stream) {
+// one body of amdnuwa_cattn_fwd and amdnuwa_cattn_fwd_drop (mk == NULL: the unmasked kernels)
+int cattn_fwd_run(const amdnuwa_cattn_geom* g, const uint16_t* q16, int ldq, const uint16_t* k16, const uint16_t* v16, int ldkv, const uint8_t* key_mask,
+                  const float* null_k, const float* null_v, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, float* stats, int f16,
+                  const CMask* mk, hipStream_t stream) {
     int rc = check_c(g);
     if (rc) return rc;
     if (!q16 || !k16 || !v16 || !null_k || !null_v || !w_th || !stats || ldq % 8 || ldkv % 8 || ldo % 4) return AMDNUWA_ERR_ARG;
     if (ldq < g->heads * g->dim_head || ldkv < g->heads * g->dim_head || ldo < g->heads * g->dim_head) return AMDNUWA_ERR_ARG;
     if (!o && !(o_lo && o_lo_f16)) return AMDNUWA_ERR_ARG;
+    if (mk && (rc = check_mask(*mk, false))) return rc;
     CArgs a{};
     a.q = q16; a.k = k16; a.v = v16; a.ldq = ldq; a.ldkv = ldkv; a.mask = key_mask;
     a.null_k = null_k; a.null_v = null_v; a.wth = w_th; a.o = o; a.ol = o_lo; a.ldo = ldo; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0; a.stats = stats;
     a.B = g->B; a.n = g->n; a.nk = keys_of(g); a.heads = g->heads; a.causal = g->causal ? 1 : 0; a.scale = g->scale; a.c1 = g->scale * 1.4426950408889634f;
     const int grid = (int)wgs(g);
     const size_t lds = lds_apply(g);
-    if (g->dim_head == 64) {
-        if (f16) launch(cattn_apply_kernel<64, true, false>, grid, lds, stream, a);
-        else launch(cattn_apply_kernel<64, false, false>, grid, lds, stream, a);
-    } else {
-        if (f16) launch(cattn_apply_kernel<32, true, false>, grid, lds, stream, a);
-        else launch(cattn_apply_kernel<32, false, false>, grid, lds, stream, a);
-    }
+    auto go = [&](auto drop) {
+        constexpr bool D = decltype(drop)::value;
+        const CKArgs<D> ka = c_kargs<D>(a, mk ? *mk : CMask{});
+        if (g->dim_head == 64) {
+            if (f16) launch(cattn_apply_kernel<64, true, false, D>, grid, lds, stream, ka);
+            else launch(cattn_apply_kernel<64, false, false, D>, grid, lds, stream, ka);
+        } else {
+            if (f16) launch(cattn_apply_kernel<32, true, false, D>, grid, lds, stream, ka);
+            else launch(cattn_apply_kernel<32, false, false, D>, grid, lds, stream, ka);
+        }
+    };
+    if (mk) go(std::true_type{});
+    else go(std::false_type{});
     LAUNCH_CHECK();
     return AMDNUWA_OK;
 }
 
-extern "C" size_t amdnuwa_cattn_bwd_workspace_bytes(const amdnuwa_cattn_geom* g) {
-    if (check_c(g)) return 0;
-    const size_t rows = (size_t)g->B * g->n, inner = (size_t)g->heads * g->dim_head;
-    return al(rows * g->heads * 4) + 2 * al(rows * NHM * 4) + al((size_t)wgs(g) * 64 * 4) + al((size_t)null_chunks(g) * 2 * inner * 4) + al(2 * inner * 4) +
-           al(amdnuwa_colsum_workspace_bytes(wgs(g), 64)) + al(amdnuwa_colsum_workspace_bytes(null_chunks(g), (int)(2 * inner)));
-}
-
-extern "C" int amdnuwa_cattn_bwd(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, const uint16_t* k, const uint16_t* v, int ldkv,
-                                 const uint16_t* dO, int lddo, const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th,
-                                 const float* stats, uint16_t* dq, int lddq, uint16_t* dk, uint16_t* dv, int lddkv, float* dw_th, float* dnull_k,
-                                 float* dnull_v, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// one body of amdnuwa_cattn_bwd and amdnuwa_cattn_bwd_drop (mk == NULL: the unmasked kernels); the workspace is the same
+int cattn_bwd_run(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, const uint16_t* k, const uint16_t* v, int ldkv, const uint16_t* dO, int lddo,
+                  const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, const float* stats, uint16_t* dq, int lddq,
+                  uint16_t* dk, uint16_t* dv, int lddkv, float* dw_th, float* dnull_k, float* dnull_v, void* workspace, size_t workspace_bytes,
+                  const CMask* mk, hipStream_t stream) {
     int rc = check_c(g);
     if (rc) return rc;
     if (!q || !k || !v || !dO || !null_k || !null_v || !w_th || !stats || !dq || !dk || !dv || !dw_th || !dnull_k || !dnull_v) return AMDNUWA_ERR_ARG;
     const int inner = g->heads * g->dim_head;
     if (ldq % 8 || ldkv % 8 || lddo % 8 || lddq % 4 || lddkv % 4 || ldq < inner || ldkv < inner || lddo < inner || lddq < inner || lddkv < inner) return AMDNUWA_ERR_ARG;
+    if (mk && (rc = check_mask(*mk, true))) return rc;
     if (!workspace || workspace_bytes < amdnuwa_cattn_bwd_workspace_bytes(g)) return AMDNUWA_ERR_WORKSPACE;
     const size_t rows = (size_t)g->B * g->n;
     char* wp = (char*)workspace;
@@ -671,20 +737,26 @@ extern "C" int amdnuwa_cattn_bwd(const amdnuwa_cattn_geom* g, const uint16_t* q,
     a.B = g->B; a.n = g->n; a.nk = keys_of(g); a.heads = g->heads; a.causal = g->causal ? 1 : 0; a.scale = g->scale; a.c1 = g->scale * 1.4426950408889634f;
     const int grid = (int)wgs(g), grid_k = (int)wgs_k(g);
     const bool d64 = g->dim_head == 64;
-    // 1. delta, the talking-heads partials and the null key's dS / A per query
-    if (d64) launch(cattn_grad_kernel<64, false, 0>, grid, lds_grad(g, 0), stream, a);
-    else launch(cattn_grad_kernel<32, false, 0>, grid, lds_grad(g, 0), stream, a);
-    LAUNCH_CHECK();
-    // 2. dq (query-stationary), dk and dv (key-stationary)
-    if (d64) launch(cattn_grad_kernel<64, false, 1>, grid, lds_grad(g, 1), stream, a);
-    else launch(cattn_grad_kernel<32, false, 1>, grid, lds_grad(g, 1), stream, a);
-    LAUNCH_CHECK();
-    if (d64) launch(cattn_grad_kernel<64, true, 1>, grid_k, lds_grad(g, 1), stream, a);
-    else launch(cattn_grad_kernel<32, true, 1>, grid_k, lds_grad(g, 1), stream, a);
-    LAUNCH_CHECK();
-    if (d64) launch(cattn_apply_kernel<64, false, true>, grid_k, lds_apply(g), stream, a);
-    else launch(cattn_apply_kernel<32, false, true>, grid_k, lds_apply(g), stream, a);
-    LAUNCH_CHECK();
+    // 1. delta, the talking-heads partials and the null key's dS / A per query;  2. dq (query-stationary), dk and dv (key-stationary)
+    auto go = [&](auto drop) -> int {
+        constexpr bool D = decltype(drop)::value;
+        const CKArgs<D> ka = c_kargs<D>(a, mk ? *mk : CMask{});
+        if (d64) launch(cattn_grad_kernel<64, false, 0, D>, grid, lds_grad(g, 0), stream, ka);
+        else launch(cattn_grad_kernel<32, false, 0, D>, grid, lds_grad(g, 0), stream, ka);
+        LAUNCH_CHECK();
+        if (d64) launch(cattn_grad_kernel<64, false, 1, D>, grid, lds_grad(g, 1), stream, ka);
+        else launch(cattn_grad_kernel<32, false, 1, D>, grid, lds_grad(g, 1), stream, ka);
+        LAUNCH_CHECK();
+        if (d64) launch(cattn_grad_kernel<64, true, 1, D>, grid_k, lds_grad(g, 1), stream, ka);
+        else launch(cattn_grad_kernel<32, true, 1, D>, grid_k, lds_grad(g, 1), stream, ka);
+        LAUNCH_CHECK();
+        if (d64) launch(cattn_apply_kernel<64, false, true, D>, grid_k, lds_apply(g), stream, ka);
+        else launch(cattn_apply_kernel<32, false, true, D>, grid_k, lds_apply(g), stream, ka);
+        LAUNCH_CHECK();
+        return AMDNUWA_OK;
+    };
+    rc = mk ? go(std::true_type{}) : go(std::false_type{});
+    if (rc) return rc;
     // 3. the small gradients: fixed-order reductions of the partials
     hipLaunchKernelGGL(cattn_null_grads_kernel, dim3((unsigned)null_chunks(g)), dim3(256), 0, stream, q, ldq, dO, lddo, a.ds0, a.a0, part_null, (long)rows,
                        inner, g->dim_head);
@@ -696,6 +768,50 @@ extern "C" int amdnuwa_cattn_bwd(const amdnuwa_cattn_geom* g, const uint16_t* q,
     if (hipMemcpyAsync(dnull_k, dnull, (size_t)inner * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) return AMDNUWA_ERR_ARG;
     if (hipMemcpyAsync(dnull_v, dnull + inner, (size_t)inner * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) return AMDNUWA_ERR_ARG;
     return AMDNUWA_OK;
+}
+
+}  // namespace
+
+extern "C" int amdnuwa_cattn_supported(const amdnuwa_cattn_geom* g) { return check_c(g) == AMDNUWA_OK; }
+extern "C" int amdnuwa_cattn_drop_supported(const amdnuwa_cattn_geom* g) { return check_c(g) == AMDNUWA_OK; }
+
+extern "C" size_t amdnuwa_cattn_bwd_workspace_bytes(const amdnuwa_cattn_geom* g) {
+    if (check_c(g)) return 0;
+    const size_t rows = (size_t)g->B * g->n, inner = (size_t)g->heads * g->dim_head;
+    return al(rows * g->heads * 4) + 2 * al(rows * NHM * 4) + al((size_t)wgs(g) * 64 * 4) + al((size_t)null_chunks(g) * 2 * inner * 4) + al(2 * inner * 4) +
+           al(amdnuwa_colsum_workspace_bytes(wgs(g), 64)) + al(amdnuwa_colsum_workspace_bytes(null_chunks(g), (int)(2 * inner)));
+}
+
+extern "C" int amdnuwa_cattn_fwd(const amdnuwa_cattn_geom* g, const uint16_t* q16, int ldq, const uint16_t* k16, const uint16_t* v16, int ldkv,
+                                 const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o, uint16_t* o_lo,
+                                 int ldo, int o_lo_f16, float* stats, int f16, hipStream_t stream) {
+    return cattn_fwd_run(g, q16, ldq, k16, v16, ldkv, key_mask, null_k, null_v, w_th, o, o_lo, ldo, o_lo_f16, stats, f16, nullptr, stream);
+}
+
+extern "C" int amdnuwa_cattn_fwd_drop(const amdnuwa_cattn_geom* g, const uint16_t* q16, int ldq, const uint16_t* k16, const uint16_t* v16, int ldkv,
+                                      const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th, uint16_t* o, uint16_t* o_lo,
+                                      int ldo, int o_lo_f16, float* stats, int f16, const uint8_t* keep, const uint8_t* keep0, float drop_scale,
+                                      hipStream_t stream) {
+    const CMask mk{keep, nullptr, keep0, drop_scale};
+    return cattn_fwd_run(g, q16, ldq, k16, v16, ldkv, key_mask, null_k, null_v, w_th, o, o_lo, ldo, o_lo_f16, stats, f16, &mk, stream);
+}
+
+extern "C" int amdnuwa_cattn_bwd(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, const uint16_t* k, const uint16_t* v, int ldkv,
+                                 const uint16_t* dO, int lddo, const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th,
+                                 const float* stats, uint16_t* dq, int lddq, uint16_t* dk, uint16_t* dv, int lddkv, float* dw_th, float* dnull_k,
+                                 float* dnull_v, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return cattn_bwd_run(g, q, ldq, k, v, ldkv, dO, lddo, key_mask, null_k, null_v, w_th, stats, dq, lddq, dk, dv, lddkv, dw_th, dnull_k, dnull_v, workspace,
+                         workspace_bytes, nullptr, stream);
+}
+
+extern "C" int amdnuwa_cattn_bwd_drop(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, const uint16_t* k, const uint16_t* v, int ldkv,
+                                      const uint16_t* dO, int lddo, const uint8_t* key_mask, const float* null_k, const float* null_v, const float* w_th,
+                                      const float* stats, uint16_t* dq, int lddq, uint16_t* dk, uint16_t* dv, int lddkv, float* dw_th, float* dnull_k,
+                                      float* dnull_v, void* workspace, size_t workspace_bytes, const uint8_t* keep, const uint8_t* keep_t,
+                                      const uint8_t* keep0, float drop_scale, hipStream_t stream) {
+    const CMask mk{keep, keep_t, keep0, drop_scale};
+    return cattn_bwd_run(g, q, ldq, k, v, ldkv, dO, lddo, key_mask, null_k, null_v, w_th, stats, dq, lddq, dk, dv, lddkv, dw_th, dnull_k, dnull_v, workspace,
+                         workspace_bytes, &mk, stream);
 }
 
 AMDNUWA_SAT_ACCESSOR(cattn)

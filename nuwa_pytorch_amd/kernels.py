@@ -1592,6 +1592,26 @@ def cattn_supported(g):
     return bool(_lib.lib().amdnuwa_cattn_supported(C.byref(g)))
 
 
+def cattn_drop_supported(g):
+    """the masked (attention dropout) forms of the cattn cores take the geometry: the envelope of cattn_supported"""
+    return bool(_lib.lib().amdnuwa_cattn_drop_supported(C.byref(g)))
+
+
+def cattn_keep_shapes(g):
+    """shapes of the uint8 keep arrays of the masked cattn calls: keep [B, n, KP], keep_t [B, T, NP], keep0 [B, n] (KP / NP: T / n rounded up to 32)"""
+    T = cattn_keys(g)
+    return (g.B, g.n, -(-T // 32) * 32), (g.B, T, -(-g.n // 32) * 32), (g.B, g.n)
+
+
+def _chk_keep(g, keep, bwd):
+    """keep = (keep, keep_t, keep0) of a masked cattn call: contiguous uint8 arrays of cattn_keep_shapes (the forward reads keep and keep0 only)"""
+    assert len(keep) == 3
+    for t, shape, need in zip(keep, cattn_keep_shapes(g), (True, bwd, True)):
+        if need or t is not None:
+            assert t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == shape, (None if t is None else tuple(t.shape), shape)
+    return keep
+
+
 def _c_work(kind):
     """algorithmic MFMA work of the cattn cores over the VISIBLE (query, key) pairs only -- the causal half plus the null key, or all
     n x (T + 1) pairs of the non-causal form (U = one 2 pairs d product): forward QK^T + A V + head mix; backward S, dA, dq, dk, dv + two mixes"""
@@ -1612,10 +1632,12 @@ def _rows16(t, inner):
 
 
 @_family('cattn', _c_work('fwd'))
-def cattn_fwd(g, q16, k16, v16, null_k, null_v, wth, mask_u8=None, o_f16=False, lo=True):
+def cattn_fwd(g, q16, k16, v16, null_k, null_v, wth, mask_u8=None, o_f16=False, lo=True, keep=None, drop_scale=1.0):
     """the cattn forward core on 16-bit rows q16 [B*n, inner], k16 / v16 [B*T, inner] (T = the geometry's key count; views with a row stride; k16 and v16 share theirs: the two
     halves of to_kv's output).  fp16 rows: every MFMA the fp16 one; else bf16.  Returns o BF [B*n, inner] (hi + lo pair; with o_f16 a bf16
-    copy + an fp16 copy; lo=False: the bf16 copy alone) and the softmax statistics [B, heads, n, 2]"""
+    copy + an fp16 copy; lo=False: the bf16 copy alone) and the softmax statistics [B, heads, n, 2].
+    keep = (keep, keep_t, keep0) uint8 arrays of cattn_keep_shapes (bit g = output head g kept) with drop_scale = 1 / (1 - p): attention dropout
+    on the mixed probabilities inside the kernel (amdnuwa_cattn_fwd_drop)"""
     L = _lib.lib()
     inner = g.heads * g.dim_head
     f16 = q16.dtype == torch.float16
@@ -1630,17 +1652,22 @@ def cattn_fwd(g, q16, k16, v16, null_k, null_v, wth, mask_u8=None, o_f16=False, 
     else:
         o = empty_bf((g.B * g.n, inner), dev, lo=lo)
     stats = torch.empty((g.B, g.heads, g.n, 2), dtype=torch.float32, device=dev)
-    check(L.amdnuwa_cattn_fwd(C.byref(g), _p(q16), q16.stride(0), _p(k16), _p(v16), k16.stride(0), _p(mask_u8), _p(null_k), _p(null_v), _p(wth),
-                              _p(o.hi), _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _p(stats), 1 if f16 else 0, _stream()),
-          'amdnuwa_cattn_fwd')
+    args = (C.byref(g), _p(q16), q16.stride(0), _p(k16), _p(v16), k16.stride(0), _p(mask_u8), _p(null_k), _p(null_v), _p(wth),
+            _p(o.hi), _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _p(stats), 1 if f16 else 0)
+    if keep is not None:
+        kp, _, k0 = _chk_keep(g, keep, False)
+        _chk_dev(q16, kp, k0)
+        check(L.amdnuwa_cattn_fwd_drop(*args, _p(kp), _p(k0), float(drop_scale), _stream()), 'amdnuwa_cattn_fwd_drop')
+    else:
+        check(L.amdnuwa_cattn_fwd(*args, _stream()), 'amdnuwa_cattn_fwd')
     return o, stats
 
 
 @_family('cattn', _c_work('bwd'))
-def cattn_bwd(g, q, k, v, dO, null_k, null_v, wth, stats, mask_u8=None):
+def cattn_bwd(g, q, k, v, dO, null_k, null_v, wth, stats, mask_u8=None, keep=None, drop_scale=1.0):
     """the recomputing cattn backward on bf16 rows (q / dO [B*n, inner], k / v [B*T, inner] views) and the forward's statistics.  Returns dq BF
     [B*n, inner], dkv BF [B*T, 2 inner] (dk | dv: the layout of to_kv's output), dw_th [heads, heads], dnull_k and dnull_v [heads, dim_head]
-    fp32.  No n x T array: the workspace is O(B n heads) floats"""
+    fp32.  No n x T array: the workspace is O(B n heads) floats.  keep / drop_scale: the forward's mask arrays (amdnuwa_cattn_bwd_drop)"""
     L = _lib.lib()
     inner = g.heads * g.dim_head
     for t in (q, k, v, dO):
@@ -1655,9 +1682,15 @@ def cattn_bwd(g, q, k, v, dO, null_k, null_v, wth, stats, mask_u8=None):
     small = torch.empty(64 + 2 * inner, dtype=torch.float32, device=dev)
     nb = L.amdnuwa_cattn_bwd_workspace_bytes(C.byref(g))
     ws = workspace(nb, dev)
-    check(L.amdnuwa_cattn_bwd(C.byref(g), _p(q), q.stride(0), _p(k), _p(v), k.stride(0), _p(dO), dO.stride(0), _p(mask_u8), _p(null_k), _p(null_v),
-                              _p(wth), _p(stats), _p(dq), inner, _p(dkv), dkv.data_ptr() + 2 * inner, 2 * inner, _p(small), small.data_ptr() + 4 * 64,
-                              small.data_ptr() + 4 * (64 + inner), _p(ws), nb, _stream()), 'amdnuwa_cattn_bwd')
+    args = (C.byref(g), _p(q), q.stride(0), _p(k), _p(v), k.stride(0), _p(dO), dO.stride(0), _p(mask_u8), _p(null_k), _p(null_v),
+            _p(wth), _p(stats), _p(dq), inner, _p(dkv), dkv.data_ptr() + 2 * inner, 2 * inner, _p(small), small.data_ptr() + 4 * 64,
+            small.data_ptr() + 4 * (64 + inner), _p(ws), nb)
+    if keep is not None:
+        kp, kt, k0 = _chk_keep(g, keep, True)
+        _chk_dev(q, kp, kt, k0)
+        check(L.amdnuwa_cattn_bwd_drop(*args, _p(kp), _p(kt), _p(k0), float(drop_scale), _stream()), 'amdnuwa_cattn_bwd_drop')
+    else:
+        check(L.amdnuwa_cattn_bwd(*args, _stream()), 'amdnuwa_cattn_bwd')
     dwth = small[:64].reshape(8, 8)[:g.heads, :g.heads].contiguous()
     return BF(dq, None), BF(dkv, None), dwth, small[64:64 + inner].reshape(g.heads, g.dim_head), small[64 + inner:].reshape(g.heads, g.dim_head)
 

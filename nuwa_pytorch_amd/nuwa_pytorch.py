@@ -188,6 +188,8 @@ class SandwichNorm(nn.Module):
                 return fn, shift
         if isinstance(fn, FeedForward) or (isinstance(fn, Sparse3DNA) and fn._hip_ok()):      # (a FeedForward with live dropout too: its meta carries drop_p)
             return fn, shift
+        if isinstance(fn, Attention) and (context is not None or seq_len is not None) and fn._drop_hip_ok(context is not None):
+            return fn, shift                      # live attention dropout sent to the masked cattn kernels (Attention.dropout_on_kernels)
         if isinstance(fn, Attention) and context is not None and fn._hip_ok(context.shape[1]):
             return fn, shift
         if isinstance(fn, Attention) and context is None and seq_len is not None and fn._hip_ok(seq_len):
@@ -366,8 +368,16 @@ class Attention(nn.Module):
     the linear-memory cattn kernels at any length (`_causal_hip_ok`; precision modes 'bf16x3-fwd' and 'bf16'), and so does non-causal
     attention over more than 287 keys, its own rows or a context's (`_long_hip_ok`: the kernels' rectangular form, n queries x T keys)
     wherever the shape is large enough for them to be the faster route (`long_pairs_min`, `long_wgs_min`; 0 routes every such shape).
-    What still runs the PyTorch-ROCm forward below: more than 8 heads, dim_head not 32 / 64, attention dropout > 0 in training, causal
-    attention with a context, and the 'bf16x3' parity mode wherever the cattn kernels would serve."""
+    What still runs the PyTorch-ROCm forward below: more than 8 heads, dim_head not 32 / 64, attention dropout > 0 in training (by default),
+    causal attention with a context, and the 'bf16x3' parity mode wherever the cattn kernels would serve.
+    Attention dropout in training (np.py:370-374) is opt-in on the kernels: with the class (or instance) attribute `dropout_on_kernels = True`
+    a module with `dropout.p > 0` in training mode runs the masked forms of the cattn kernels at ANY key count -- causal self-attention,
+    non-causal self-attention, a context -- within heads <= 8, dim_head 32 / 64 and the modes 'bf16x3-fwd' / 'bf16' (`_drop_hip_ok`;
+    `long_pairs_min` / `long_wgs_min` do not gate it).  ops.CInner draws the keep mask from torch's RNG stream, one byte per (query, key)
+    pair kept from the forward to the backward, so this route is not strictly linear in memory.  The default, False, keeps the torch-op
+    forward for live dropout."""
+
+    dropout_on_kernels = False
 
     def __init__(self, *, dim, heads=8, dim_head=64, causal=False, dropout=0.):
         super().__init__()
@@ -395,6 +405,11 @@ class Attention(nn.Module):
         return (not self.causal) and self.dim_head in (32, 64) and self.heads <= 8 and n_keys + 1 <= 288 and \
             not (self.training and self.dropout.p > 0)
 
+    def _drop_hip_ok(self, has_ctx):
+        """live attention dropout the user sent to the masked cattn kernels (dropout_on_kernels): any number of queries and keys"""
+        return bool(self.dropout_on_kernels) and self.training and self.dropout.p > 0 and self.dim_head in (32, 64) and self.heads <= 8 and \
+            not (self.causal and has_ctx) and (K.get_precision() == 'bf16' or K.cores_f16())
+
     def _causal_hip_ok(self, n):
         """causal self-attention the cattn kernels take: any length; 'bf16x3-fwd' (fp16 forward core, bf16 backward) and 'bf16'"""
         return self.causal and n >= 1 and self.dim_head in (32, 64) and self.heads <= 8 and not (self.training and self.dropout.p > 0) and \
@@ -420,20 +435,23 @@ class Attention(nn.Module):
             batch * min(-(-n_queries // 64), -(-n_keys // 64)) >= self.long_wgs_min
 
     def _meta(self, B, n, device, context=None, context_mask=None, mask=None, rotary_pos_emb=None, **_):
-        assert not (self.training and self.dropout.p > 0)      # (_hip_ok routes attn_dropout > 0 in training to the torch-op forward)
+        drop = self._drop_hip_ok(context is not None)
+        # (without dropout_on_kernels, _hip_ok routes attn_dropout > 0 in training to the torch-op forward)
+        assert drop or not (self.training and self.dropout.p > 0)
+        dkw = dict(drop_p=float(self.dropout.p)) if drop else {}            # ops.CInner draws the keep mask and runs the masked kernels
         if self.causal:                               # plain causal self-attention: the cattn kernels (keys = the query rows, key mask = `mask`)
             assert context is None
             meta = dict(kind='cattn', cache=self._cache, cgeom=K.cattn_geom(B, n, self.heads, self.dim_head, causal=True),
-                        mask_u8=mask.to(torch.uint8).contiguous() if exists(mask) else None)
+                        mask_u8=mask.to(torch.uint8).contiguous() if exists(mask) else None, **dkw)
             if exists(rotary_pos_emb):
                 meta['rotary'] = rotary_pos_emb.detach().float()
             return meta
         self_kv = context is None
         T = n if self_kv else context.shape[1]
         key_mask = mask if self_kv else context_mask
-        if self._long_hip_ok(T, n, B):                # more keys than xattn6 takes: the cattn kernels, n query rows x T key rows
+        if drop or self._long_hip_ok(T, n, B):        # more keys than xattn6 takes, or live dropout: the cattn kernels, n query rows x T key rows
             meta = dict(kind='cattn', cache=self._cache, cgeom=K.cattn_geom(B, n, self.heads, self.dim_head, causal=False, n_keys=T),
-                        mask_u8=key_mask.to(torch.uint8).contiguous() if exists(key_mask) else None, has_ctx=not self_kv)
+                        mask_u8=key_mask.to(torch.uint8).contiguous() if exists(key_mask) else None, has_ctx=not self_kv, **dkw)
             if self_kv and exists(rotary_pos_emb):
                 meta['rotary'] = rotary_pos_emb.detach().float()
             return meta
@@ -448,7 +466,7 @@ class Attention(nn.Module):
 
     def forward(self, x, mask=None, context=None, context_mask=None, rotary_pos_emb=None):
         B, n, _ = x.shape
-        if x.is_cuda and self._hip_ok(context.shape[1] if exists(context) else n):
+        if x.is_cuda and (self._hip_ok(context.shape[1] if exists(context) else n) or self._drop_hip_ok(exists(context))):
             meta = self._meta(B, n, x.device, context, context_mask, mask=mask, rotary_pos_emb=rotary_pos_emb)
             return ops.InnerFn.apply(x, context, meta, *self._params())
         if x.is_cuda and not exists(context) and self._causal_hip_ok(n):

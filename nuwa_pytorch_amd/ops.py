@@ -496,11 +496,40 @@ class XInner:
         return dh, dctx, [dnk.reshape(nk.shape), dnv.reshape(nv.shape), dwth.reshape(wth.shape), dwq, dwkv, dwo]
 
 
+def cattn_pack_keep(keep_bhij):
+    """the mask arrays of the masked cattn kernels from a boolean keep mask [B, heads, n, T + 1] over (output head, query, key slot; slot 0 = the
+    null key): (keep [B, n, KP], keep_t [B, T, NP], keep0 [B, n]) uint8, bit g = head g kept, KP / NP = T / n rounded up to 32, padding zero"""
+    B, heads, n, J = keep_bhij.shape
+    T = J - 1
+    packed = torch.zeros((B, n, J), dtype=torch.uint8, device=keep_bhij.device)
+    for g in range(heads):
+        packed += keep_bhij[:, g].to(torch.uint8) * (1 << g)
+    keep = torch.zeros((B, n, -(-T // 32) * 32), dtype=torch.uint8, device=packed.device)
+    keep[:, :, :T] = packed[:, :, 1:]
+    keep_t = torch.zeros((B, T, -(-n // 32) * 32), dtype=torch.uint8, device=packed.device)
+    keep_t[:, :, :n] = packed[:, :, 1:].transpose(1, 2)
+    return keep, keep_t, packed[:, :, 0].contiguous()
+
+
+_CATTN_DRAW_MAX = 1 << 26          # most fp32 values of one transient draw of _cattn_keep_mask (256 MB)
+
+
+def _cattn_keep_mask(B, n, T, heads, p, device):
+    """keep mask of the nn.Dropout(p) on the mixed attention map [B, heads, n, T + 1] (np.py:370-374), as the mask arrays of the masked cattn
+    kernels (cattn_pack_keep).  Drawn from torch's RNG stream a batch chunk at a time, so the transient fp32 draw stays bounded; tests replace
+    this function by a fixed mask"""
+    bc = max(1, min(B, _CATTN_DRAW_MAX // max(1, heads * n * (T + 1))))
+    parts = [cattn_pack_keep(torch.rand((min(bc, B - b0), heads, n, T + 1), device=device) >= p) for b0 in range(0, B, bc)]
+    return tuple(torch.cat(ts, 0) if len(ts) > 1 else ts[0] for ts in zip(*parts))
+
+
 class CInner:
     """to_q(x), to_kv(x or context) -> plain attention core with linear memory (cattn: causal self-attention, or non-causal attention of the
     n rows over any number of keys -- their own or, with meta['has_ctx'], the T rows of meta['ctx_bf']) -> to_out (np.py:315-379).  params: null_k, null_v, talking_heads.w, to_q.w, to_kv.w, to_out.w  (the layout and weight cache of XInner).
     'bf16x3-fwd': hi + lo projections with an fp16 copy, the core on fp16 MFMAs, two-MFMA to_out; the backward on the bf16 hi parts.
-    'bf16': bf16 throughout.  ('bf16x3' keeps the torch-op formulation: Attention._causal_hip_ok.)"""
+    'bf16': bf16 throughout.  ('bf16x3' keeps the torch-op formulation: Attention._causal_hip_ok.)
+    meta['drop_p'] (attention dropout in training, Attention.dropout_on_kernels): the masked forms of the same kernels; the mask arrays ride behind
+    the saved tensors (so RngReplay's recomputed forward and the backward read the same ones)."""
     nparams = 6
 
     @staticmethod
@@ -531,18 +560,22 @@ class CInner:
             if f16:
                 q, kv = BF(q.hi, q.lo, K.hilo_to_f16(q)), BF(kv.hi, kv.lo, K.hilo_to_f16(kv))
         nk2, nv2, wth2 = CInner._small(p, g)
+        drop_p = float(meta.get('drop_p') or 0.0)
+        keep = _cattn_keep_mask(g.B, g.n, K.cattn_keys(g), g.heads, drop_p, h.hi.device) if drop_p else None
+        dkw = dict(keep=keep, drop_scale=1.0 / (1.0 - drop_p)) if drop_p else {}
         o16 = False
         if f16:             # fp16 core; the output as a bf16 copy + an fp16 copy (two-MFMA to_out) or a bf16 hi + lo pair (3-MFMA to_out)
             o16 = K.proj_f16x2('o') and 'out_16' in W and K.gemm_nt_f16x2_ok(R, p[5].shape[0], p[5].shape[1], out_bf16=False)
-            o, stats = K.cattn_fwd(g, q.f16, kv.f16[:, :inner], kv.f16[:, inner:], nk2, nv2, wth2, meta['mask_u8'], o_f16=o16)
+            o, stats = K.cattn_fwd(g, q.f16, kv.f16[:, :inner], kv.f16[:, inner:], nk2, nv2, wth2, meta['mask_u8'], o_f16=o16, **dkw)
         else:
-            o, stats = K.cattn_fwd(g, q.hi, kv.hi[:, :inner], kv.hi[:, inner:], nk2, nv2, wth2, meta['mask_u8'], lo=False)
+            o, stats = K.cattn_fwd(g, q.hi, kv.hi[:, :inner], kv.hi[:, inner:], nk2, nv2, wth2, meta['mask_u8'], lo=False, **dkw)
         y = K.gemm_nt_f16x2(o.f16, W['out_16']) if o16 else K.gemm_nt(o, W['out'], out_bf16=_fast())
-        return y, (K.hi_only(h), K.hi_only(ctx) if has_ctx else None, K.hi_only(q), K.hi_only(kv), stats, K.hi_only(o))
+        return y, (K.hi_only(h), K.hi_only(ctx) if has_ctx else None, K.hi_only(q), K.hi_only(kv), stats, K.hi_only(o)) + ((keep,) if drop_p else ())
 
     @staticmethod
     def bwd(saved, dy, p, meta, need_dbias=False, dy_f32=None):
-        h, ctx, q, kv, stats, o = saved
+        h, ctx, q, kv, stats, o = saved[:6]
+        keep = saved[6] if len(saved) > 6 else None          # attention dropout: the mask arrays of the forward
         W = XInner.weights(meta['cache'], p)
         nk, nv, wth, wq, wkv, wo = p
         g = meta['cgeom']
@@ -552,7 +585,8 @@ class CInner:
         d_o = K.gemm_nt(dy, W['outT'], out_bf16=True)
         dwo = torch.empty_like(wo)
         K.gemm_tn(dy, o, dwo)
-        dq, dkv, dwth, dnk, dnv = K.cattn_bwd(g, q.hi, kv.hi[:, :inner], kv.hi[:, inner:], d_o.hi, nk2, nv2, wth2, stats, meta['mask_u8'])
+        dq, dkv, dwth, dnk, dnv = K.cattn_bwd(g, q.hi, kv.hi[:, :inner], kv.hi[:, inner:], d_o.hi, nk2, nv2, wth2, stats, meta['mask_u8'], keep=keep,
+                                              drop_scale=1.0 / (1.0 - float(meta['drop_p'])) if keep is not None else 1.0)
         rot = meta.get('rotary')
         if rot is not None:
             dq = _rotary_bf(dq, rot, g.B, g.n, g.heads, inverse=True)
