@@ -43,7 +43,8 @@ int amdnuwa_abi_version(void);                 /* bumps when any signature or do
                                                 *     sampling tail of a generate() token, and amdnuwa_vq_nearest_l2 with its _workspace_bytes, the Euclidean
                                                 *     code lookup of the tokenizer, and amdnuwa_cross2dna_rows with its _workspace_bytes, the rows form of
                                                 *     amdnuwa_cross2dna_decode for the cache prefill of NUWASketch.generate, and amdnuwa_attn_rows with its _workspace_bytes,
-                                                *     the rows form of amdnuwa_attn_decode_rows for the cache prefill of a generate() over a long text context) */
+                                                *     the rows form of amdnuwa_attn_decode_rows for the cache prefill of a generate() over a long text context, and
+                                                *     amdnuwa_cross2dna_fwd_drop / _bwd_drop with amdnuwa_cross2dna_drop_supported, attention dropout inside SparseCross2DNA) */
 const char* amdnuwa_error_string(int code);
 /* runtime tuning knobs (A/B benchmarking only; 0 = the library's auto policy everywhere):
  *   key 0  NT GEMM variant: 2 direct-to-LDS BK 32 (128x128 tiles), 5 register-staged 128x128, 7 the 256x256 ring family for every size,
@@ -444,6 +445,32 @@ int amdnuwa_cross2dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uin
                           uint16_t* dq, uint16_t* dq_lo, int lddq, uint16_t* dk, uint16_t* dv, uint16_t* dk_lo, uint16_t* dv_lo,
                           int lddkv, float* d_null_k, float* d_null_v, float* dw_th, void* workspace, size_t workspace_bytes,
                           amdnuwa_stream stream);
+/* Attention dropout inside SparseCross2DNA (the `self.dropout(attn)` of reference nuwa_pytorch.py:888-892, behind the talking-heads mix of
+ * the windowed queries; additive at ABI 21).  With P = softmax over the J = kf*kh*kw + 1 slots and P' = W_th . P, the V product and dV take
+ * P'' = keep . P' . drop_scale and the backward takes dP' = keep . (dO . V^T) . drop_scale; everything below dP' -- dq, dk / dv over the
+ * context, d_null_k, d_null_v, dw_th -- is amdnuwa_cross2dna_bwd's.  keep: uint8 [B][ntok - 1][J][heads], the index order of the ds / P'
+ * workspace, nonzero = keep (the caller draws it; the same array goes to the forward and to the backward); drop_scale = 1 / (1 - p), finite
+ * and >= 1.  The arguments are those of amdnuwa_cross2dna_fwd / _bwd with keep and drop_scale in front of the stream, the checks and their
+ * order are theirs, and keep == NULL or a drop_scale that is not finite or < 1 is AMDNUWA_ERR_ARG (behind the geometry and UNSUPPORTED
+ * answers, in front of the workspace one, at B = 0 as well).  The mask has no alignment rule: the cross route runs the masked forms of the
+ * VALU window kernels (row and column-tiled, bf16 and hi + lo operands) and never a band kernel.  Slots hidden by key_mask or by the 'same'
+ * padding have P = 0 and ignore the mask; the <bos> query row (nuwa_pytorch.py:826-844: no dropout, no talking heads) stays the caller's and has no
+ * row in keep.  An all-ones mask with drop_scale = 1 gives the bits of amdnuwa_cross2dna_fwd / _bwd.  amdnuwa_cross2dna_drop_supported()
+ * answers as amdnuwa_s3_supported() (g->noncausal is ignored, as in the entries); the backward uses the workspace of
+ * amdnuwa_cross2dna_bwd_workspace_bytes(). */
+int amdnuwa_cross2dna_drop_supported(const amdnuwa_s3_geom* g, int lo_operands);
+int amdnuwa_cross2dna_fwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
+                               const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
+                               const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v, const uint16_t* null_v_lo,
+                               const uint8_t* key_mask, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, const uint8_t* keep,
+                               float drop_scale, amdnuwa_stream stream);
+int amdnuwa_cross2dna_bwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
+                               const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
+                               const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v, const uint16_t* null_v_lo,
+                               const uint8_t* key_mask, const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo,
+                               uint16_t* dq, uint16_t* dq_lo, int lddq, uint16_t* dk, uint16_t* dv, uint16_t* dk_lo, uint16_t* dv_lo,
+                               int lddkv, float* d_null_k, float* d_null_v, float* dw_th, void* workspace, size_t workspace_bytes,
+                               const uint8_t* keep, float drop_scale, amdnuwa_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Incremental decoding for NUWA.generate (np.py:1841-1915).  The reference recomputes the whole prefix for every sampled

@@ -120,6 +120,9 @@ SIGNATURES = {
     'amdnuwa_cross2dna_fwd': (I, [SG, P, P, I, I, P, P, P, P, I, P, P, P, P, P, P, P, P, I, P]),
     'amdnuwa_cross2dna_bwd_workspace_bytes': (SZ, [SG]),
     'amdnuwa_cross2dna_bwd': (I, [SG, P, P, I, I, P, P, P, P, I, P, P, P, P, P, P, P, P, I, P, P, I, P, P, P, P, I, P, P, P, P, SZ, P]),
+    'amdnuwa_cross2dna_drop_supported': (I, [SG, I]),
+    'amdnuwa_cross2dna_fwd_drop': (I, [SG, P, P, I, I, P, P, P, P, I, P, P, P, P, P, P, P, P, I, P, F, P]),
+    'amdnuwa_cross2dna_bwd_drop': (I, [SG, P, P, I, I, P, P, P, P, I, P, P, P, P, P, P, P, P, I, P, P, I, P, P, P, P, I, P, P, P, P, SZ, P, F, P]),
     'amdnuwa_decode_shift': (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     'amdnuwa_decode_ln': (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, P]),
     'amdnuwa_s3_decode': (I, [SG, P, P, P, P, I, P, P, P, P, P]),

@@ -3216,30 +3216,54 @@ int cross_setup(S3Args& a, S3Route& r, const amdnuwa_s3_geom* g, int ctx_rows, c
 }
 }  // namespace
 
-extern "C" int amdnuwa_cross2dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
-                                     const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
-                                     const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v,
-                                     const uint16_t* null_v_lo, const uint8_t* key_mask, const float* w_th, uint16_t* o,
-                                     uint16_t* o_lo, int ldo, hipStream_t stream) {
+// the masked (attention dropout) forms of the cross entries: the VALU window kernels (row and column-tiled, both operand forms) -- the cross
+// route takes no band kernel, so no alignment of the mask is asked for; g->noncausal is ignored as in the entries themselves
+extern "C" int amdnuwa_cross2dna_drop_supported(const amdnuwa_s3_geom* g, int lo_operands) { return amdnuwa_s3_supported(g, lo_operands); }
+
+// amdnuwa_cross2dna_fwd (m = {}) and amdnuwa_cross2dna_fwd_drop: the DROP form of the same VALU kernel
+static int cross_fwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
+                         const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
+                         const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v,
+                         const uint16_t* null_v_lo, const uint8_t* key_mask, const float* w_th, uint16_t* o,
+                         uint16_t* o_lo, int ldo, const S3Mask& m, hipStream_t stream) {
     S3Args a{};
     S3Route r{};
     int rc = cross_setup(a, r, g, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask);
     if (rc) return rc;
     if (!q || !w_th || !o || ldq % 8 || ldo % 8 || (k_lo != nullptr) != (q_lo != nullptr)) return AMDNUWA_ERR_ARG;
+    if (!mask_ok(m, false)) return AMDNUWA_ERR_ARG;
     if (g->B <= 0) return AMDNUWA_OK;
     a.q = q; a.ql = q_lo; a.ld = ldq; a.o = o; a.ol = o_lo; a.ldo = ldo; a.wth = w_th;
-    return s3_fwd_launch(a, g, r, k_lo != nullptr, nullptr, 1.f, stream);
+    return s3_fwd_launch(a, g, r, k_lo != nullptr, m.keep, m.s, stream);
+}
+extern "C" int amdnuwa_cross2dna_fwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
+                                     const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
+                                     const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v,
+                                     const uint16_t* null_v_lo, const uint8_t* key_mask, const float* w_th, uint16_t* o,
+                                     uint16_t* o_lo, int ldo, hipStream_t stream) {
+    return cross_fwd_run(g, q, q_lo, ldq, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask, w_th, o, o_lo, ldo,
+                         {}, stream);
+}
+extern "C" int amdnuwa_cross2dna_fwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
+                                          const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
+                                          const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v,
+                                          const uint16_t* null_v_lo, const uint8_t* key_mask, const float* w_th, uint16_t* o,
+                                          uint16_t* o_lo, int ldo, const uint8_t* keep, float drop_scale, hipStream_t stream) {
+    return cross_fwd_run(g, q, q_lo, ldq, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask, w_th, o, o_lo, ldo,
+                         {true, keep, drop_scale}, stream);
 }
 
 extern "C" size_t amdnuwa_cross2dna_bwd_workspace_bytes(const amdnuwa_s3_geom* g) { return amdnuwa_sparse3dna_bwd_workspace_bytes(g); }
 
-extern "C" int amdnuwa_cross2dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
-                                     const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
-                                     const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v,
-                                     const uint16_t* null_v_lo, const uint8_t* key_mask, const float* w_th, const uint16_t* dO,
-                                     const uint16_t* dO_lo, int lddo, uint16_t* dq, uint16_t* dq_lo, int lddq, uint16_t* dk,
-                                     uint16_t* dv, uint16_t* dk_lo, uint16_t* dv_lo, int lddkv, float* d_null_k, float* d_null_v,
-                                     float* dw_th, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// amdnuwa_cross2dna_bwd (m = {}) and amdnuwa_cross2dna_bwd_drop: the DROP form of the query side; the key side and the final sums read P''
+// where they read P' (d_null_v through the part_v0 partials, which the query side forms with the mask byte of slot 0)
+static int cross_bwd_run(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
+                         const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
+                         const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v,
+                         const uint16_t* null_v_lo, const uint8_t* key_mask, const float* w_th, const uint16_t* dO,
+                         const uint16_t* dO_lo, int lddo, uint16_t* dq, uint16_t* dq_lo, int lddq, uint16_t* dk,
+                         uint16_t* dv, uint16_t* dk_lo, uint16_t* dv_lo, int lddkv, float* d_null_k, float* d_null_v,
+                         float* dw_th, void* workspace, size_t workspace_bytes, const S3Mask& m, hipStream_t stream) {
     S3Args a{};
     S3Route r{};
     int rc = cross_setup(a, r, g, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask);
@@ -3248,6 +3272,7 @@ extern "C" int amdnuwa_cross2dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q
         return AMDNUWA_ERR_ARG;
     const bool lo = k_lo != nullptr;
     if (lo != (q_lo != nullptr) || lo != (dO_lo != nullptr)) return AMDNUWA_ERR_ARG;
+    if (!mask_ok(m, false)) return AMDNUWA_ERR_ARG;
     if (!workspace || workspace_bytes < s3_ws(g).bytes) return AMDNUWA_ERR_WORKSPACE;
     if (g->B <= 0) return AMDNUWA_OK;
     a.q = q; a.ql = q_lo; a.ld = ldq; a.wth = w_th;
@@ -3255,7 +3280,29 @@ extern "C" int amdnuwa_cross2dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q
     a.dq = dq; a.dql = dq_lo; a.ldd = lddq; a.dk = dk; a.dv = dv; a.dkl = dk_lo; a.dvl = dv_lo; a.lddk = lddkv;
     a.dwth = dw_th; a.accumulate = 0; a.dnull_k = d_null_k; a.dnull_v = d_null_v;
     bind_ws(a, g, workspace);
-    return s3_bwd_launch(a, g, r, lo, nullptr, 1.f, stream);
+    return s3_bwd_launch(a, g, r, lo, m.keep, m.s, stream);
+}
+extern "C" int amdnuwa_cross2dna_bwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
+                                     const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
+                                     const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v,
+                                     const uint16_t* null_v_lo, const uint8_t* key_mask, const float* w_th, const uint16_t* dO,
+                                     const uint16_t* dO_lo, int lddo, uint16_t* dq, uint16_t* dq_lo, int lddq, uint16_t* dk,
+                                     uint16_t* dv, uint16_t* dk_lo, uint16_t* dv_lo, int lddkv, float* d_null_k, float* d_null_v,
+                                     float* dw_th, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return cross_bwd_run(g, q, q_lo, ldq, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask, w_th, dO, dO_lo, lddo,
+                         dq, dq_lo, lddq, dk, dv, dk_lo, dv_lo, lddkv, d_null_k, d_null_v, dw_th, workspace, workspace_bytes, {}, stream);
+}
+extern "C" int amdnuwa_cross2dna_bwd_drop(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq, int ctx_rows,
+                                          const uint16_t* k, const uint16_t* v, const uint16_t* k_lo, const uint16_t* v_lo, int ldkv,
+                                          const uint16_t* null_k, const uint16_t* null_k_lo, const uint16_t* null_v,
+                                          const uint16_t* null_v_lo, const uint8_t* key_mask, const float* w_th, const uint16_t* dO,
+                                          const uint16_t* dO_lo, int lddo, uint16_t* dq, uint16_t* dq_lo, int lddq, uint16_t* dk,
+                                          uint16_t* dv, uint16_t* dk_lo, uint16_t* dv_lo, int lddkv, float* d_null_k, float* d_null_v,
+                                          float* dw_th, void* workspace, size_t workspace_bytes, const uint8_t* keep, float drop_scale,
+                                          hipStream_t stream) {
+    return cross_bwd_run(g, q, q_lo, ldq, ctx_rows, k, v, k_lo, v_lo, ldkv, null_k, null_k_lo, null_v, null_v_lo, key_mask, w_th, dO, dO_lo, lddo,
+                         dq, dq_lo, lddq, dk, dv, dk_lo, dv_lo, lddkv, d_null_k, d_null_v, dw_th, workspace, workspace_bytes,
+                         {true, keep, drop_scale}, stream);
 }
 
 AMDNUWA_SAT_ACCESSOR(sparse3dna)

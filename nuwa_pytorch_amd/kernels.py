@@ -1048,7 +1048,7 @@ def s3_drop_supported(g, lo=None):
 
 
 def _s3_keep(g, keep):
-    """the keep mask of sparse3dna_fwd / _bwd as the uint8 [B, ntok - 1, J, heads] array the kernels read"""
+    """the keep mask of sparse3dna_fwd / _bwd (and cross2dna_fwd / _bwd) as the uint8 [B, ntok - 1, J, heads] array the kernels read"""
     J = g.kf * g.kh * g.kw + 1
     if tuple(keep.shape) != (g.B, g.ntok - 1, J, g.heads) or keep.dtype not in (torch.bool, torch.uint8):
         raise ValueError(f'keep must be bool / uint8 [B, ntok - 1, J, heads] = {(g.B, g.ntok - 1, J, g.heads)}, got {keep.dtype} {tuple(keep.shape)}')
@@ -1142,24 +1142,34 @@ def sparse3dna_bwd(g, qkv, wth, dO, rel_bias=None, keep=None, drop_scale=1.0):
     return dqkv, dwth, drel
 
 
-def cross2dna_fwd(g, q, kv, null_k, null_v, mask_u8, wth, ctx_rows):
+def cross2dna_drop_supported(g, lo=None):
+    """do the masked (attention dropout) forms of the SparseCross2DNA kernels take this geometry in the current precision mode?"""
+    lo = (get_precision() != 'bf16') if lo is None else lo
+    return bool(_lib.lib().amdnuwa_cross2dna_drop_supported(C.byref(g), 1 if lo else 0))
+
+
+def cross2dna_fwd(g, q, kv, null_k, null_v, mask_u8, wth, ctx_rows, keep=None, drop_scale=1.0):
     """SparseCross2DNA core.  q BF [B*ntok, inner]; kv BF [B*ctx_rows, 2*inner] (k | v); null_k / null_v BF [inner]; mask_u8 [B, ctx_rows]
-    or None.  Returns o BF [B*ntok, inner] whose rows b*ntok (<bos>) are left for the caller."""
-    L = _lib.lib()
+    or None.  Returns o BF [B*ntok, inner] whose rows b*ntok (<bos>) are left for the caller.
+    keep (attention dropout, np.py:888-892): bool / uint8 [B, ntok - 1, J, heads], nonzero = keep, with drop_scale = 1 / (1 - p): the masked
+    form of the same kernel (amdnuwa_cross2dna_fwd_drop); the <bos> rows have no row in it"""
+    k8 = _s3_keep(g, keep) if keep is not None else None
     inner = g.heads * g.dim_head
     # deliberately not written and never read here: row b * ntok (<bos>) of every sample, which the module fills with its own glue
     # arithmetic (under the NaN-prefill guard of tests/guard_util.py those rows stay NaN: compare rows 1 .. ntok - 1)
     o = empty_bf((g.B * g.ntok, inner), q.hi.device, lo=q.lo is not None)
     k, v = (view(kv, cols=slice(i * inner, (i + 1) * inner)) for i in range(2))
-    check(L.amdnuwa_cross2dna_fwd(C.byref(g), _p(q.hi), _p(q.lo), q.hi.stride(0), ctx_rows, _p(k.hi), _p(v.hi), _p(k.lo), _p(v.lo),
-                                  kv.hi.stride(0), _p(null_k.hi), _p(null_k.lo), _p(null_v.hi), _p(null_v.lo), _p(mask_u8), _p(wth),
-                                  _p(o.hi), _p(o.lo), inner, _stream()), 'amdnuwa_cross2dna_fwd')
+    _s3_call('amdnuwa_cross2dna_fwd', [C.byref(g), _p(q.hi), _p(q.lo), q.hi.stride(0), ctx_rows, _p(k.hi), _p(v.hi), _p(k.lo), _p(v.lo),
+                                       kv.hi.stride(0), _p(null_k.hi), _p(null_k.lo), _p(null_v.hi), _p(null_v.lo), _p(mask_u8), _p(wth),
+                                       _p(o.hi), _p(o.lo), inner], k8, drop_scale)
     return o
 
 
-def cross2dna_bwd(g, q, kv, null_k, null_v, mask_u8, wth, dO, ctx_rows):
-    """returns dq BF [B*ntok, inner] (rows b*ntok untouched), dkv BF [B*ctx_rows, 2*inner], d_null_k, d_null_v fp32 [inner], dw_th [h, h]"""
+def cross2dna_bwd(g, q, kv, null_k, null_v, mask_u8, wth, dO, ctx_rows, keep=None, drop_scale=1.0):
+    """returns dq BF [B*ntok, inner] (rows b*ntok untouched), dkv BF [B*ctx_rows, 2*inner], d_null_k, d_null_v fp32 [inner], dw_th [h, h].
+    keep / drop_scale: the forward's (cross2dna_fwd)"""
     L = _lib.lib()
+    k8 = _s3_keep(g, keep) if keep is not None else None
     inner = g.heads * g.dim_head
     dev = q.hi.device
     lo = q.lo is not None
@@ -1172,11 +1182,10 @@ def cross2dna_bwd(g, q, kv, null_k, null_v, mask_u8, wth, dO, ctx_rows):
     dk, dv = (view(dkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(2))
     nb = L.amdnuwa_cross2dna_bwd_workspace_bytes(C.byref(g))
     ws = workspace(nb, dev)
-    check(L.amdnuwa_cross2dna_bwd(C.byref(g), _p(q.hi), _p(q.lo), q.hi.stride(0), ctx_rows, _p(k.hi), _p(v.hi), _p(k.lo), _p(v.lo),
-                                  kv.hi.stride(0), _p(null_k.hi), _p(null_k.lo), _p(null_v.hi), _p(null_v.lo), _p(mask_u8), _p(wth),
-                                  _p(dO.hi), _p(dO.lo), dO.hi.stride(0), _p(dq.hi), _p(dq.lo), dq.hi.stride(0), _p(dk.hi), _p(dv.hi),
-                                  _p(dk.lo), _p(dv.lo), dkv.hi.stride(0), _p(dnk), _p(dnv), _p(dwth), _p(ws), nb, _stream()),
-          'amdnuwa_cross2dna_bwd')
+    _s3_call('amdnuwa_cross2dna_bwd', [C.byref(g), _p(q.hi), _p(q.lo), q.hi.stride(0), ctx_rows, _p(k.hi), _p(v.hi), _p(k.lo), _p(v.lo),
+                                       kv.hi.stride(0), _p(null_k.hi), _p(null_k.lo), _p(null_v.hi), _p(null_v.lo), _p(mask_u8), _p(wth),
+                                       _p(dO.hi), _p(dO.lo), dO.hi.stride(0), _p(dq.hi), _p(dq.lo), dq.hi.stride(0), _p(dk.hi), _p(dv.hi),
+                                       _p(dk.lo), _p(dv.lo), dkv.hi.stride(0), _p(dnk), _p(dnv), _p(dwth), _p(ws), nb], k8, drop_scale)
     return dq, dkv, dnk, dnv, dwth
 
 

@@ -7,7 +7,8 @@ own forward() is never called on the decoder path.
 
 Scope: decoder stack, embeddings, logits/loss = HIP.  The text encoder (row f1,
 256 tokens once per step) runs its attention / FeedForward blocks through the same kernels.  NUWAVideoAudio (cfg 5) lives in
-video_audio.py; NUWASketch (row f4) shares the decoder kernels, with SparseCross2DNA and the sketch encoder on PyTorch-ROCm ops.
+video_audio.py; NUWASketch (row f4) shares the decoder kernels and runs SparseCross2DNA on the window kernels pointed at the sketch context
+(amdnuwa_cross2dna_*, with attention dropout in training on their masked forms); its sketch encoder runs the symmetric window kernels.
 """
 import contextlib
 import functools
@@ -618,7 +619,15 @@ class SparseCross2DNA(nn.Module):
     position in EVERY sketch frame (+ a learned null key); the <bos> query attends to all sketch tokens, without talking heads.
     On the MI355X the windowed queries run on the 3DNA kernels pointed at the sketch context (amdnuwa_cross2dna_*, row f4; the B
     <bos> rows are glue arithmetic between the kernels); `_forward_torch` keeps the gather formulation on PyTorch ops for shapes the
-    kernels do not take (other head sizes, attention dropout in training)."""
+    kernels do not take (other head sizes, windows whose slot tables outgrow the LDS).
+
+    Attention dropout in training (np.py:888-892) runs on the masked forms of the same kernels (amdnuwa_cross2dna_fwd_drop / _bwd_drop:
+    P'' = keep . P' / (1 - p) behind the talking-heads mix of the windowed queries; the <bos> query has no dropout in the reference either).
+    ops.XC2Inner draws the mask from torch's RNG stream and saves it for the backward, so a SandwichNorm fuses the block in plain and
+    reversible stacks as it does without dropout.  `dropout_on_kernels = False` (class or instance attribute) restores the PyTorch-op
+    route for live dropout: the A/B switch, and the way to keep that forward in fp32."""
+
+    dropout_on_kernels = True
 
     def __init__(self, *, dim, image_size, heads=8, dim_head=64, dropout=0., kernel_size=3, dilation=1):
         super().__init__()
@@ -642,10 +651,19 @@ class SparseCross2DNA(nn.Module):
     def _params(self):
         return (self.null_k, self.null_v, self.talking_heads.weight, self.to_q.weight, self.to_kv.weight, self.to_out.weight)
 
+    def _drop_live(self):
+        return self.training and self.dropout.p > 0
+
     def _hip_ok(self, ctx_len):
         tpf = self.image_size ** 2
-        if ctx_len <= 0 or ctx_len % tpf or (self.training and self.dropout.p > 0):
+        if ctx_len <= 0 or ctx_len % tpf:
             return False
+        if self._drop_live():
+            # live attention dropout: the masked forms of the kernels (dropout_on_kernels), else the PyTorch-op formulation below
+            if not self.dropout_on_kernels:
+                return False
+            return K.cross2dna_drop_supported(K.s3_geom(1, 2, (1, self.image_size, self.image_size), (ctx_len // tpf, self.kernel_size, self.kernel_size),
+                                                        (1, self.dilation, self.dilation), self.heads, self.dim_head, causal=False))
         # the window holds kernel^2 slots of EVERY sketch frame: with many frames / a large kernel its LDS tables outgrow the CU
         # (e.g. kernel 5 with 6 frames, kernel 3 with 16) and the PyTorch-op formulation below takes over
         return K.s3_supported((1, self.image_size, self.image_size), (ctx_len // tpf, self.kernel_size, self.kernel_size),
@@ -658,7 +676,10 @@ class SparseCross2DNA(nn.Module):
         g = K.s3_geom(B, n, (frames, self.image_size, self.image_size), (T // tpf, self.kernel_size, self.kernel_size),
                       (1, self.dilation, self.dilation), self.heads, self.dim_head, causal=False)
         mask_u8 = context_mask.to(torch.uint8).contiguous() if exists(context_mask) else None
-        return dict(kind='xc2', cache=self._cache, geom=g, ctx_T=T, mask_u8=mask_u8)
+        meta = dict(kind='xc2', cache=self._cache, geom=g, ctx_T=T, mask_u8=mask_u8)
+        if self._drop_live() and self.dropout_on_kernels:
+            meta['drop_p'] = float(self.dropout.p)           # ops.XC2Inner draws the keep mask and runs the masked kernels
+        return meta
 
     def forward(self, x, *, context, context_mask=None, **kwargs):
         if x.is_cuda and self._hip_ok(context.shape[1]):

@@ -782,7 +782,9 @@ class XC2Inner:
     params: null_k, null_v, talking_heads.w, to_q.w, to_kv.w, to_out.w  (the layout of XInner)
     The windowed queries run on the 3DNA kernels pointed at the context (amdnuwa_cross2dna_*); the single <bos> query of every
     sample -- full attention over all context tokens, no talking heads (np.py:813-830) -- is B rows of glue arithmetic on torch ops
-    between the kernels, forward and backward."""
+    between the kernels, forward and backward.  meta['drop_p'] (attention dropout in training, np.py:888-892): the masked forms of the same
+    kernels; the mask is drawn here, covers the windowed queries only (the <bos> glue knows no dropout) and rides behind the saved tensors,
+    so RngReplay's recomputed forward and the backward read the same one."""
     nparams = 6
 
     @staticmethod
@@ -810,7 +812,10 @@ class XC2Inner:
         q = K.gemm_nt(h, W['q'], out_bf16=True)
         kv = K.gemm_nt(meta['ctx_bf'], W['kv'], out_bf16=True)
         nk, nv = XC2Inner._null(p, q.lo is not None)
-        o = K.cross2dna_fwd(g, q, kv, nk, nv, meta['mask_u8'], wth2, T)
+        drop_p = float(meta.get('drop_p') or 0.0)
+        keep_a = _attn_keep_mask(g.B, g.ntok - 1, g.kf * g.kh * g.kw + 1, heads, drop_p, q.hi.device) if drop_p else None
+        dkw = dict(keep=keep_a, drop_scale=1.0 / (1.0 - drop_p)) if drop_p else {}
+        o = K.cross2dna_fwd(g, q, kv, nk, nv, meta['mask_u8'], wth2, T, **dkw)
         # <bos> query rows
         rows0 = torch.arange(g.B, device=q.hi.device) * g.ntok
         q0 = _bf_val(K.BF(q.hi[rows0], None if q.lo is None else q.lo[rows0])).reshape(g.B, heads, dh)
@@ -820,11 +825,12 @@ class XC2Inner:
         o0 = P0[..., :1] * _bf_val(nv).reshape(1, heads, dh) + torch.einsum('bht,bthd->bhd', P0[..., 1:], kvf[:, :, 1])
         _bf_put(o, rows0, o0.reshape(g.B, inner))
         y = K.gemm_nt(o, W['out'], out_bf16=_fast())
-        return y, _sv(h, q, kv, nk, nv, o, P0)
+        return y, tuple(_sv(h, q, kv, nk, nv, o, P0)) + ((keep_a,) if drop_p else ())
 
     @staticmethod
     def bwd(saved, dy, p, meta, need_dbias=False, dy_f32=None):
-        h, q, kv, nk, nv, o, P0 = saved
+        h, q, kv, nk, nv, o, P0 = saved[:7]
+        keep_a = saved[7] if len(saved) > 7 else None        # attention dropout: the keep mask of the forward
         W = XInner.weights(meta['cache'], p)
         nkp, nvp, wth, wq, wkv, wo = p
         g, T = meta['geom'], meta['ctx_T']
@@ -834,7 +840,8 @@ class XC2Inner:
         d_o = K.gemm_nt(dy, W['outT'], out_bf16=True)
         dwo = torch.empty_like(wo)
         K.gemm_tn(dy, o, dwo)
-        dq, dkv, dnk, dnv, dwth = K.cross2dna_bwd(g, q, kv, nk, nv, meta['mask_u8'], wth2, d_o, T)
+        dkw = dict(keep=keep_a, drop_scale=1.0 / (1.0 - float(meta['drop_p']))) if keep_a is not None else {}
+        dq, dkv, dnk, dnv, dwth = K.cross2dna_bwd(g, q, kv, nk, nv, meta['mask_u8'], wth2, d_o, T, **dkw)
         # <bos> query rows: softmax attention backward on B rows
         rows0 = torch.arange(g.B, device=q.hi.device) * g.ntok
         sub = lambda t: _bf_val(K.BF(t.hi[rows0], None if t.lo is None else t.lo[rows0])).reshape(g.B, heads, dh)
