@@ -285,6 +285,36 @@ int amdnuwa_geglu_dropout_fwd(const uint16_t* in, const uint16_t* in_lo, int ld_
 int amdnuwa_geglu_il_bwd_dropout(const uint16_t* u_hi, const uint16_t* u_lo, const uint16_t* d_hi, const uint16_t* d_lo,
                                  const uint8_t* keep, int ld_keep, float scale, uint16_t* du_hi, uint16_t* du_lo,
                                  long long R, int FP, amdnuwa_stream stream);
+/* Dropout keep masks from a counter-based generator, in a kernel of their own (csrc/keepmask.hip; added at ABI 21, purely additive).
+ * They serve every nn.Dropout the library runs on masked kernels -- reference nuwa_pytorch.py:276 (FeedForward), :554-564 and :746-752
+ * (Sparse3DNA, SparseCausal2DNA), :888-892 (SparseCross2DNA) and :370-374 (Attention) -- and write the layouts those kernels read today.
+ *
+ * THE DECISION FUNCTION.  Philox4x32-10 with the standard constants: multipliers 0xD2511F53 (on counter word 0) and 0xCD9E8D57 (on word 2),
+ * Weyl key increments 0x9E3779B9 and 0xBB67AE85, ten rounds, the key bumped between rounds; key = (seed word 0, seed word 1), the low 32
+ * bits of the two 64-bit words `seed` points to on the device.  For the logical element e (64-bit):
+ *     word = output word (e mod 4) of Philox(counter = (floor(e / 4) mod 2^32, floor(e / 4) >> 32, 0, 0), key);   keep  <=>  word >= thr
+ * with thr = min(2^32 - 1, round(p * 2^32)), computed by the caller in ONE place (kernels.keep_threshold); the kept values are scaled by
+ * drop_scale = 1 / (1 - p) as before.  Known answers (counter; key -> output words in order):
+ *     0 0 0 0; 0 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8        ffffffff x 4; ffffffff x 2 -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     243f6a88 85a308d3 13198a2e 03707344; a4093822 299f31d0 -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * Logical elements:
+ *     FeedForward mask [R, C]                       e = r * C + c
+ *     window / SparseCross2DNA mask [B, nq, J, heads]   e = ((b * nq + i) * J + j) * heads + g         (the storage index)
+ *     cattn                                         e = ((b * n + i) * (T + 1) + j) * 8 + g, j = 0 the null slot, always 8 head lanes
+ * The decision depends on (seed, e) alone: not on the launch, the output's alignment, or how a caller splits a batch (e0 / b_first).  A
+ * later in-kernel generator has to reproduce exactly this function.  The kernels READ the seed: the host never synchronises.
+ *
+ * amdnuwa_keep_mask_linear: keep[i] = 1 if element e0 + i is kept, else 0, for i < count; any count > 0, any alignment of keep (16-byte
+ * stores between a byte-wise head and tail).
+ * amdnuwa_keep_mask_cattn: the three arrays of amdnuwa_cattn_fwd_drop / _bwd_drop for samples b_first .. b_first + B - 1 (b above = b_first +
+ * the array's sample index): keep [B][n][KP], keep_t [B][T][NP] (the same bytes transposed), keep0 [B][n]; KP / NP = T / n rounded up to 32;
+ * bit g = head g kept; every padding byte and every bit at or above `heads` zero.  keep and keep_t are both written in 16-byte pieces of
+ * contiguous rows (one 64 x 64 tile transposed through LDS), keep / keep_t bases 4-byte aligned.
+ * NULL arrays or seed, heads outside 1 .. 8, non-positive sizes, a negative e0 / b_first, a misaligned keep / keep_t (cattn) or seed:
+ * AMDNUWA_ERR_ARG before anything is launched. */
+int amdnuwa_keep_mask_linear(uint8_t* keep, long long count, long long e0, uint32_t thr, const uint64_t* seed, amdnuwa_stream stream);
+int amdnuwa_keep_mask_cattn(uint8_t* keep, uint8_t* keep_t, uint8_t* keep0, int B, int n, int T, int heads, long long b_first,
+                            uint32_t thr, const uint64_t* seed, amdnuwa_stream stream);
 /* dst[r][c<C] = bf16(src[r][c]), zero for C <= c < Cp */
 int amdnuwa_cast_pad(const float* src, int ld_src, uint16_t* hi, uint16_t* lo, int ld_dst, long long R, int C, int Cp,
                      amdnuwa_stream stream);

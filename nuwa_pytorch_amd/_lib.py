@@ -94,6 +94,8 @@ SIGNATURES = {
     'amdnuwa_geglu_bwd': (I, [P, P, P, P, P, P, LL, I, P]),
     'amdnuwa_geglu_dropout_fwd': (I, [P, P, I, I, P, I, F, P, P, I, P, I, LL, I, P]),
     'amdnuwa_geglu_il_bwd_dropout': (I, [P, P, P, P, P, I, F, P, P, LL, I, P]),
+    'amdnuwa_keep_mask_linear': (I, [P, LL, LL, C.c_uint32, P, P]),
+    'amdnuwa_keep_mask_cattn': (I, [P, P, P, I, I, I, I, LL, C.c_uint32, P, P]),
     'amdnuwa_cast_pad': (I, [P, I, P, P, I, LL, I, I, P]),
     'amdnuwa_transpose_cast': (I, [P, I, P, P, I, I, I, P]),
     'amdnuwa_embed_fwd': (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, P]),

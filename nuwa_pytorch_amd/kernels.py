@@ -2,6 +2,7 @@
 Tensors only provide device memory (torch caching allocator) and the current HIP stream; all
 arithmetic happens inside libamdnuwa."""
 import ctypes as C
+import math
 import os
 import threading
 from collections import namedtuple
@@ -860,6 +861,49 @@ def _keep_u8(keep, R, Cc):
     assert keep.dtype in (torch.bool, torch.uint8) and tuple(keep.shape) == (R, Cc) and keep.stride(1) == 1, 'keep mask: bool [R, C], unit inner stride'
     _chk_dev(keep)
     return keep
+
+
+def keep_threshold(p):
+    """thr of the keep-mask generator (include/amdnuwa.h, the decision function): element kept <=> its Philox word >= thr.  THE one place that
+    turns a dropout probability into the uint32 the kernels compare with: min(2^32 - 1, round(p * 2^32)), halves rounded up"""
+    p = float(p)
+    assert 0.0 <= p < 1.0, p
+    return min(0xFFFFFFFF, int(math.floor(p * 4294967296.0 + 0.5)))
+
+
+def _chk_seed(seed):
+    assert seed.dtype == torch.int64 and seed.is_contiguous() and seed.numel() >= 2, 'seed: two int64 words on the device'
+    _chk_dev(seed)
+    return seed
+
+
+def keep_mask_linear(count, thr, seed, e0=0, out=None):
+    """count keep bytes (uint8, 0 / 1) of the logical elements e0 .. e0 + count - 1 from the Philox generator (amdnuwa_keep_mask_linear).  seed:
+    int64 device tensor of two words (low 32 bits used), read by the kernel -- no host synchronisation.  out: a contiguous uint8 tensor of
+    `count` elements at any alignment (default: a new one)"""
+    _chk_seed(seed)
+    if out is None:
+        out = torch.empty((count,), dtype=torch.uint8, device=seed.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == count and out.device == seed.device
+    _chk_dev(out)
+    check(_lib.lib().amdnuwa_keep_mask_linear(_p(out), int(count), int(e0), int(thr), _p(seed), _stream()), 'amdnuwa_keep_mask_linear')
+    return out
+
+
+def keep_mask_cattn(B, n, T, heads, thr, seed, b_first=0, out=None):
+    """(keep [B, n, KP], keep_t [B, T, NP], keep0 [B, n]) uint8 of the masked cattn kernels (what ops.cattn_pack_keep builds from a boolean mask)
+    for the logical samples b_first .. b_first + B - 1, from the Philox generator (amdnuwa_keep_mask_cattn).  seed as in keep_mask_linear;
+    out: the three arrays to write (default: new ones)"""
+    _chk_seed(seed)
+    shapes = ((B, n, -(-T // 32) * 32), (B, T, -(-n // 32) * 32), (B, n))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.uint8, device=seed.device) for s in shapes)
+    for t, s in zip(out, shapes):
+        assert t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == s and t.device == seed.device, (tuple(t.shape), s)
+    _chk_dev(*out)
+    check(_lib.lib().amdnuwa_keep_mask_cattn(_p(out[0]), _p(out[1]), _p(out[2]), B, n, T, heads, int(b_first), int(thr), _p(seed), _stream()),
+          'amdnuwa_keep_mask_cattn')
+    return tuple(out)
 
 
 def geglu_dropout_fwd_f16(g16, keep, scale, out16=None):

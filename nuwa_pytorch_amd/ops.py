@@ -202,9 +202,39 @@ def block_plan(kind, R, D, p, meta, has_resid=False, ln=True):
     return plan(R, D, p, meta, has_resid, ln) if plan is not None else Plan()
 
 
+# Where the dropout keep masks come from.  'torch' (default): torch.rand(...) >= p, the draw every release so far made.  'device': the Philox
+# generator kernels of csrc/keepmask.hip write the masks in the layouts the masked kernels read -- no fp32 uniforms, no pack passes, no
+# transposes; the keep decision is the function of (seed, logical element) stated in include/amdnuwa.h.  Another generator samples other masks
+# from a seed, so the route is opt-in (set_keep_mask_source / AMDNUWA_KEEP_MASK_SOURCE).
+KEEP_MASK_SOURCES = ('torch', 'device')
+_KEEP_MASK_SOURCE = os.environ.get('AMDNUWA_KEEP_MASK_SOURCE', 'torch')
+if _KEEP_MASK_SOURCE not in KEEP_MASK_SOURCES:
+    raise ValueError(f'AMDNUWA_KEEP_MASK_SOURCE={_KEEP_MASK_SOURCE!r}: expected one of {KEEP_MASK_SOURCES}')
+
+
+def set_keep_mask_source(name):
+    global _KEEP_MASK_SOURCE
+    if name not in KEEP_MASK_SOURCES:
+        raise ValueError(name)
+    _KEEP_MASK_SOURCE = name
+
+
+def get_keep_mask_source():
+    return _KEEP_MASK_SOURCE
+
+
+def _keep_seed(device):
+    """the two seed words of one generated mask: ONE tiny draw from torch's generator of that device, left on the device (the generator kernel
+    reads them; nothing synchronises).  torch.manual_seed, RngReplay's recorded states and a forked stream therefore govern the generated
+    masks exactly as they govern a torch.rand draw"""
+    return torch.randint(0, 1 << 32, (2,), dtype=torch.int64, device=device)
+
+
 def _attn_keep_mask(B, nq, J, heads, p, device):
     """keep mask of the nn.Dropout(p) on the window attention map (np.py:558, 748), in the kernels' [B, query, slot, head] order (torch's RNG
-    stream; tests replace this function by a fixed mask)"""
+    stream, or under set_keep_mask_source('device') the generator kernel seeded from it; tests replace this function by a fixed mask)"""
+    if _KEEP_MASK_SOURCE == 'device':
+        return K.keep_mask_linear(B * nq * J * heads, K.keep_threshold(p), _keep_seed(device)).view(torch.bool).view(B, nq, J, heads)
     return torch.rand((B, nq, J, heads), device=device) >= p
 
 
@@ -517,7 +547,10 @@ _CATTN_DRAW_MAX = 1 << 26          # most fp32 values of one transient draw of _
 def _cattn_keep_mask(B, n, T, heads, p, device):
     """keep mask of the nn.Dropout(p) on the mixed attention map [B, heads, n, T + 1] (np.py:370-374), as the mask arrays of the masked cattn
     kernels (cattn_pack_keep).  Drawn from torch's RNG stream a batch chunk at a time, so the transient fp32 draw stays bounded; tests replace
-    this function by a fixed mask"""
+    this function by a fixed mask.  Under set_keep_mask_source('device') the generator kernel writes the three arrays directly, seeded from
+    torch's RNG stream: no uniforms, no pack passes, no transposed copy"""
+    if _KEEP_MASK_SOURCE == 'device':
+        return K.keep_mask_cattn(B, n, T, heads, K.keep_threshold(p), _keep_seed(device))
     bc = max(1, min(B, _CATTN_DRAW_MAX // max(1, heads * n * (T + 1))))
     parts = [cattn_pack_keep(torch.rand((min(bc, B - b0), heads, n, T + 1), device=device) >= p) for b0 in range(0, B, bc)]
     return tuple(torch.cat(ts, 0) if len(ts) > 1 else ts[0] for ts in zip(*parts))
@@ -602,7 +635,10 @@ class CInner:
 
 
 def _ff_keep_mask(R, C, p, device):
-    """keep mask of nn.Dropout(p) over the GEGLU output [R, C] (torch's RNG stream; tests replace this function by a fixed mask)"""
+    """keep mask of nn.Dropout(p) over the GEGLU output [R, C] (torch's RNG stream, or under set_keep_mask_source('device') the generator
+    kernel seeded from it; tests replace this function by a fixed mask)"""
+    if _KEEP_MASK_SOURCE == 'device':
+        return K.keep_mask_linear(R * C, K.keep_threshold(p), _keep_seed(device)).view(torch.bool).view(R, C)
     return torch.rand((R, C), device=device) >= p
 
 
