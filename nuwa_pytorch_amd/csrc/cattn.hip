@@ -653,11 +653,6 @@ size_t lds_grad(const amdnuwa_cattn_geom* g, int mode) {
     const size_t inner = (size_t)g->heads * g->dim_head;
     return 2 * YT * (inner * 2 + 16) + (mode ? inner * TP : 256 * 65 * 4) + 3 * NHM * YT * 4 + 16 + 4 * 64 * 4;
 }
-template <typename Kern, typename KA>
-void launch(Kern kern, int grid, size_t lds, hipStream_t stream, const KA& a) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-}
 // workgroups of the query-stationary sweeps (the only ones that leave per-workgroup partials) and of the key-stationary sweeps
 long long wgs(const amdnuwa_cattn_geom* g) { return (long long)g->B * ((g->n + XW - 1) / XW); }
 long long wgs_k(const amdnuwa_cattn_geom* g) { return (long long)g->B * ((keys_of(g) + XW - 1) / XW); }
@@ -673,6 +668,17 @@ int check_mask(const CMask& mk, bool bwd) {
     return AMDNUWA_OK;
 }
 
+// The half of CArgs the forward and the backward run share: inputs, key mask, null key / value, W_th and the geometry.  Everything else
+// stays zero; a run adds its own operands.
+CArgs c_args(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, const uint16_t* k, const uint16_t* v, int ldkv, const uint8_t* key_mask,
+             const float* null_k, const float* null_v, const float* w_th, const float* stats) {
+    CArgs a{};
+    a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldkv = ldkv; a.mask = key_mask;
+    a.null_k = null_k; a.null_v = null_v; a.wth = w_th; a.stats = const_cast<float*>(stats);
+    a.B = g->B; a.n = g->n; a.nk = keys_of(g); a.heads = g->heads; a.causal = g->causal ? 1 : 0; a.scale = g->scale; a.c1 = g->scale * 1.4426950408889634f;
+    return a;
+}
+
 // one body of amdnuwa_cattn_fwd and amdnuwa_cattn_fwd_drop (mk == NULL: the unmasked kernels)
 int cattn_fwd_run(const amdnuwa_cattn_geom* g, const uint16_t* q16, int ldq, const uint16_t* k16, const uint16_t* v16, int ldkv, const uint8_t* key_mask,
                   const float* null_k, const float* null_v, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, float* stats, int f16,
@@ -683,27 +689,14 @@ int cattn_fwd_run(const amdnuwa_cattn_geom* g, const uint16_t* q16, int ldq, con
     if (ldq < g->heads * g->dim_head || ldkv < g->heads * g->dim_head || ldo < g->heads * g->dim_head) return AMDNUWA_ERR_ARG;
     if (!o && !(o_lo && o_lo_f16)) return AMDNUWA_ERR_ARG;
     if (mk && (rc = check_mask(*mk, false))) return rc;
-    CArgs a{};
-    a.q = q16; a.k = k16; a.v = v16; a.ldq = ldq; a.ldkv = ldkv; a.mask = key_mask;
-    a.null_k = null_k; a.null_v = null_v; a.wth = w_th; a.o = o; a.ol = o_lo; a.ldo = ldo; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0; a.stats = stats;
-    a.B = g->B; a.n = g->n; a.nk = keys_of(g); a.heads = g->heads; a.causal = g->causal ? 1 : 0; a.scale = g->scale; a.c1 = g->scale * 1.4426950408889634f;
-    const int grid = (int)wgs(g);
-    const size_t lds = lds_apply(g);
-    auto go = [&](auto drop) {
-        constexpr bool D = decltype(drop)::value;
-        const CKArgs<D> ka = c_kargs<D>(a, mk ? *mk : CMask{});
-        if (g->dim_head == 64) {
-            if (f16) launch(cattn_apply_kernel<64, true, false, D>, grid, lds, stream, ka);
-            else launch(cattn_apply_kernel<64, false, false, D>, grid, lds, stream, ka);
-        } else {
-            if (f16) launch(cattn_apply_kernel<32, true, false, D>, grid, lds, stream, ka);
-            else launch(cattn_apply_kernel<32, false, false, D>, grid, lds, stream, ka);
-        }
-    };
-    if (mk) go(std::true_type{});
-    else go(std::false_type{});
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    CArgs a = c_args(g, q16, ldq, k16, v16, ldkv, key_mask, null_k, null_v, w_th, stats);
+    a.o = o; a.ol = o_lo; a.ldo = ldo; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0;
+    const dim3 grid((unsigned)wgs(g));
+    return launch_if(mk != nullptr, [&](auto drop) {
+        const CKArgs<drop()> ka = c_kargs<drop()>(a, mk ? *mk : CMask{});
+        return launch_pick<64, 32>(g->dim_head, [&](auto dh) { return launch_if(f16 != 0, [&](auto h) {
+            return launch_kernel(cattn_apply_kernel<dh(), h(), false, drop()>, grid, dim3(256), lds_apply(g), true, stream, ka); }); });
+    });
 }
 
 // one body of amdnuwa_cattn_bwd and amdnuwa_cattn_bwd_drop (mk == NULL: the unmasked kernels); the workspace is the same
@@ -721,9 +714,8 @@ int cattn_bwd_run(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, const
     const size_t rows = (size_t)g->B * g->n;
     char* wp = (char*)workspace;
     auto take = [&](size_t bytes) { char* p = wp; wp += al(bytes); return p; };
-    CArgs a{};
-    a.q = q; a.k = k; a.v = v; a.dO = dO; a.ldq = ldq; a.ldkv = ldkv; a.lddo = lddo; a.mask = key_mask;
-    a.null_k = null_k; a.null_v = null_v; a.wth = w_th; a.stats = const_cast<float*>(stats);
+    CArgs a = c_args(g, q, ldq, k, v, ldkv, key_mask, null_k, null_v, w_th, stats);
+    a.dO = dO; a.lddo = lddo; a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddkv = lddkv;
     a.delta = (float*)take(rows * g->heads * 4);
     a.ds0 = (float*)take(rows * NHM * 4);
     a.a0 = (float*)take(rows * NHM * 4);
@@ -733,34 +725,23 @@ int cattn_bwd_run(const amdnuwa_cattn_geom* g, const uint16_t* q, int ldq, const
     const size_t cs1 = amdnuwa_colsum_workspace_bytes(wgs(g), 64), cs2 = amdnuwa_colsum_workspace_bytes(null_chunks(g), 2 * inner);
     void* cws1 = take(cs1);
     void* cws2 = take(cs2);
-    a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddkv = lddkv;
-    a.B = g->B; a.n = g->n; a.nk = keys_of(g); a.heads = g->heads; a.causal = g->causal ? 1 : 0; a.scale = g->scale; a.c1 = g->scale * 1.4426950408889634f;
-    const int grid = (int)wgs(g), grid_k = (int)wgs_k(g);
-    const bool d64 = g->dim_head == 64;
+    const dim3 grid((unsigned)wgs(g)), grid_k((unsigned)wgs_k(g)), block(256);
     // 1. delta, the talking-heads partials and the null key's dS / A per query;  2. dq (query-stationary), dk and dv (key-stationary)
-    auto go = [&](auto drop) -> int {
-        constexpr bool D = decltype(drop)::value;
-        const CKArgs<D> ka = c_kargs<D>(a, mk ? *mk : CMask{});
-        if (d64) launch(cattn_grad_kernel<64, false, 0, D>, grid, lds_grad(g, 0), stream, ka);
-        else launch(cattn_grad_kernel<32, false, 0, D>, grid, lds_grad(g, 0), stream, ka);
-        LAUNCH_CHECK();
-        if (d64) launch(cattn_grad_kernel<64, false, 1, D>, grid, lds_grad(g, 1), stream, ka);
-        else launch(cattn_grad_kernel<32, false, 1, D>, grid, lds_grad(g, 1), stream, ka);
-        LAUNCH_CHECK();
-        if (d64) launch(cattn_grad_kernel<64, true, 1, D>, grid_k, lds_grad(g, 1), stream, ka);
-        else launch(cattn_grad_kernel<32, true, 1, D>, grid_k, lds_grad(g, 1), stream, ka);
-        LAUNCH_CHECK();
-        if (d64) launch(cattn_apply_kernel<64, false, true, D>, grid_k, lds_apply(g), stream, ka);
-        else launch(cattn_apply_kernel<32, false, true, D>, grid_k, lds_apply(g), stream, ka);
-        LAUNCH_CHECK();
-        return AMDNUWA_OK;
-    };
-    rc = mk ? go(std::true_type{}) : go(std::false_type{});
+    rc = launch_if(mk != nullptr, [&](auto drop) {
+        const CKArgs<drop()> ka = c_kargs<drop()>(a, mk ? *mk : CMask{});
+        return launch_pick<64, 32>(g->dim_head, [&](auto dh) {
+            int r = launch_kernel(cattn_grad_kernel<dh(), false, 0, drop()>, grid, block, lds_grad(g, 0), true, stream, ka);
+            if (!r) r = launch_kernel(cattn_grad_kernel<dh(), false, 1, drop()>, grid, block, lds_grad(g, 1), true, stream, ka);
+            if (!r) r = launch_kernel(cattn_grad_kernel<dh(), true, 1, drop()>, grid_k, block, lds_grad(g, 1), true, stream, ka);
+            if (!r) r = launch_kernel(cattn_apply_kernel<dh(), false, true, drop()>, grid_k, block, lds_apply(g), true, stream, ka);
+            return r;
+        });
+    });
     if (rc) return rc;
     // 3. the small gradients: fixed-order reductions of the partials
-    hipLaunchKernelGGL(cattn_null_grads_kernel, dim3((unsigned)null_chunks(g)), dim3(256), 0, stream, q, ldq, dO, lddo, a.ds0, a.a0, part_null, (long)rows,
+    rc = launch_kernel(cattn_null_grads_kernel, dim3((unsigned)null_chunks(g)), block, 0, false, stream, q, ldq, dO, lddo, a.ds0, a.a0, part_null, (long)rows,
                        inner, g->dim_head);
-    LAUNCH_CHECK();
+    if (rc) return rc;
     rc = amdnuwa_colsum(a.part_th, dw_th, wgs(g), 64, 0, cws1, cs1, stream);
     if (rc) return rc;
     rc = amdnuwa_colsum(part_null, dnull, null_chunks(g), 2 * inner, 0, cws2, cs2, stream);

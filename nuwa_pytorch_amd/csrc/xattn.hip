@@ -677,14 +677,11 @@ static int xattn_pack_impl(const amdnuwa_xattn_geom* g, const uint16_t* kv, cons
     if (!kv_lo && (p->Kp_lo || p->Kt_lo || p->Vp_lo || p->Vt_lo)) return AMDNUWA_ERR_ARG;
     if (g->B <= 0) return AMDNUWA_OK;
     const dim3 grid(g->B * g->heads, (g->JP + 63) / 64);
-    if (kv_lo)
-        hipLaunchKernelGGL(xattn_pack_kernel<true>, grid, dim3(256), 0, stream, kv, kv_lo, ldkv, null_k, null_v, context_mask, p->Kp, p->Kp_lo, p->Kt,
-                           p->Kt_lo, p->Vp, p->Vp_lo, p->Vt, p->Vt_lo, p->valid, g->B, g->T, g->heads, g->dim_head, g->JP, lo_f16);
-    else
-        hipLaunchKernelGGL(xattn_pack_kernel<false>, grid, dim3(256), 0, stream, kv, kv_lo, ldkv, null_k, null_v, context_mask, p->Kp, (bf16_t*)nullptr, p->Kt,
-                           (bf16_t*)nullptr, p->Vp, (bf16_t*)nullptr, p->Vt, (bf16_t*)nullptr, p->valid, g->B, g->T, g->heads, g->dim_head, g->JP, lo_f16);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    // (without kv_lo the check above has left every lo image pointer NULL)
+    return launch_if(kv_lo != nullptr, [&](auto lo) {
+        return launch_kernel(xattn_pack_kernel<lo()>, grid, dim3(256), 0, false, stream, kv, kv_lo, ldkv, null_k, null_v, context_mask, p->Kp, p->Kp_lo, p->Kt,
+                             p->Kt_lo, p->Vp, p->Vp_lo, p->Vt, p->Vt_lo, p->valid, g->B, g->T, g->heads, g->dim_head, g->JP, lo_f16);
+    });
 }
 
 static XArgs make_args(const amdnuwa_xattn_geom* g, const amdnuwa_xattn_kv* p, const float* w_th) {
@@ -693,6 +690,18 @@ static XArgs make_args(const amdnuwa_xattn_geom* g, const amdnuwa_xattn_kv* p, c
     a.valid = p->valid; a.wth = w_th;
     a.B = g->B; a.n = g->n; a.NH = g->heads; a.JP = g->JP; a.nkb = g->JP / 16; a.scale = g->scale;
     return a;
+}
+
+// one workgroup per 32 query rows of a sample, one wave per head
+struct XLaunch { dim3 grid, block; size_t lds; };
+static XLaunch x_launch(const amdnuwa_xattn_geom* g) {
+    return {dim3(g->B * ((g->n + 31) / 32)), dim3(g->heads * 64), (size_t)2 * g->heads * 4 * 64 * 4 * sizeof(float)};
+}
+// The kernel of amdnuwa_xattn_fwd_stats (the only reader of tuning key 5): the production shape -- dim_head 64, 256 text tokens -> 18 key
+// blocks, bf16 -- takes the branch-free NKB = 18 instantiation unless key 5 is set; everything else the guarded form.
+enum XFwdRoute { XFWD_NKB18, XFWD_GUARDED };
+static XFwdRoute xattn_fwd_route(const amdnuwa_xattn_geom* g, bool x3) {
+    return (g->dim_head == 64 && !x3 && g->JP / 16 == 18 && g_amdnuwa_tuning[5] == 0) ? XFWD_NKB18 : XFWD_GUARDED;
 }
 
 extern "C" int amdnuwa_xattn_fwd(const amdnuwa_xattn_geom* g, const uint16_t* q, const uint16_t* q_lo, int ldq,
@@ -713,21 +722,11 @@ extern "C" int amdnuwa_xattn_fwd_stats(const amdnuwa_xattn_geom* g, const uint16
     XArgs a = make_args(g, p, w_th);
     a.q = q; a.ql = q_lo; a.ldq = ldq; a.o = o; a.ol = o_lo; a.ldo = ldo;
     a.P = P; a.Pl = P_lo; a.Pm = Pm; a.Pml = Pm_lo; a.stats = stats;
-    const int tiles = (g->n + 31) / 32;
-    dim3 grid(g->B * tiles), block(g->heads * 64);
-    const size_t lds = (size_t)2 * g->heads * 4 * 64 * 4 * sizeof(float);
-#define XF(DH_, X3_, NKB_)                                                                                        \
-    do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)xattn_fwd_kernel<DH_, X3_, NKB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((xattn_fwd_kernel<DH_, X3_, NKB_>), grid, block, lds, stream, a);                      \
-    } while (0)
-    // production shape (dim_head 64, 256 text tokens -> 18 key blocks, bf16): branch-free instantiation
-    if (g->dim_head == 64 && !x3 && a.nkb == 18 && g_amdnuwa_tuning[5] == 0) XF(64, false, 18);
-    else if (g->dim_head == 64) { if (x3) XF(64, true, 0); else XF(64, false, 0); }
-    else { if (x3) XF(32, true, 0); else XF(32, false, 0); }
-#undef XF
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    const XLaunch l = x_launch(g);
+    if (xattn_fwd_route(g, x3) == XFWD_NKB18) return launch_kernel(xattn_fwd_kernel<64, false, 18>, l.grid, l.block, l.lds, true, stream, a);
+    return launch_pick<64, 32>(g->dim_head, [&](auto dh) {
+        return launch_if(x3, [&](auto lo) { return launch_kernel(xattn_fwd_kernel<dh(), lo(), 0>, l.grid, l.block, l.lds, true, stream, a); });
+    });
 }
 
 extern "C" size_t amdnuwa_xattn_bwd_workspace_bytes(const amdnuwa_xattn_geom* g) {
@@ -751,23 +750,14 @@ extern "C" int amdnuwa_xattn_bwd(const amdnuwa_xattn_geom* g, const uint16_t* dO
     a.dO = dO; a.dOl = dO_lo; a.lddo = lddo;
     a.P = (bf16_t*)P; a.Pl = (bf16_t*)P_lo; a.dS = dS; a.dSl = dS_lo; a.dq = dq; a.dql = dq_lo; a.lddq = lddq;
     a.part_th = (float*)workspace;
-    const int tiles = (g->n + 31) / 32;
-    dim3 grid(g->B * tiles), block(g->heads * 64);
-    const size_t lds = (size_t)2 * g->heads * 4 * 64 * 4 * sizeof(float);
-#define XB(DH_, X3_, NKB_)                                                                                        \
-    do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)xattn_bwd_kernel<DH_, X3_, NKB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((xattn_bwd_kernel<DH_, X3_, NKB_>), grid, block, lds, stream, a);                      \
-    } while (0)
+    const XLaunch l = x_launch(g);
     // (a branch-free NKB = 18 instantiation of the backward spills registers -- dP is live throughout -- so the
     //  backward always uses the guarded form with explicit prefetch)
-    if (g->dim_head == 64) { if (x3) XB(64, true, 0); else XB(64, false, 0); }
-    else { if (x3) XB(32, true, 0); else XB(32, false, 0); }
-#undef XB
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(xattn_wth_reduce_kernel, dim3(1), dim3(1024), 0, stream, a.part_th, g->B * tiles, g->heads * g->heads, dw_th, accumulate);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    rc = launch_pick<64, 32>(g->dim_head, [&](auto dh) {
+        return launch_if(x3, [&](auto lo) { return launch_kernel(xattn_bwd_kernel<dh(), lo(), 0>, l.grid, l.block, l.lds, true, stream, a); });
+    });
+    if (rc) return rc;
+    return launch_kernel(xattn_wth_reduce_kernel, dim3(1), dim3(1024), 0, false, stream, a.part_th, (int)l.grid.x, g->heads * g->heads, dw_th, accumulate);
 }
 
 extern "C" int amdnuwa_xattn_unpack(const amdnuwa_xattn_geom* g, const float* dKp, const float* dVp, uint16_t* dkv,
@@ -777,10 +767,8 @@ extern "C" int amdnuwa_xattn_unpack(const amdnuwa_xattn_geom* g, const float* dK
     if (rc) return rc;
     if (!dKp || !dVp || !dkv || !dnull_k || !dnull_v || ldkv % 8) return AMDNUWA_ERR_ARG;
     if (g->B <= 0) return AMDNUWA_OK;
-    hipLaunchKernelGGL(xattn_unpack_kernel, dim3(g->B * g->heads + 1), dim3(256), 0, stream, dKp, dVp, dkv, dkv_lo, ldkv, dnull_k, dnull_v,
-                       g->B, g->T, g->heads, g->dim_head, g->JP, accumulate & 1, (accumulate >> 1) & 1, (accumulate >> 2) & 1);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return launch_kernel(xattn_unpack_kernel, dim3(g->B * g->heads + 1), dim3(256), 0, false, stream, dKp, dVp, dkv, dkv_lo, ldkv, dnull_k, dnull_v,
+                         g->B, g->T, g->heads, g->dim_head, g->JP, accumulate & 1, (accumulate >> 1) & 1, (accumulate >> 2) & 1);
 }
 
 AMDNUWA_SAT_ACCESSOR(xattn)

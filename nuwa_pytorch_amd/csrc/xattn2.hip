@@ -842,40 +842,48 @@ int check2(const amdnuwa_xattn_geom* g) {
 
 extern "C" int amdnuwa_xattn2_supported(const amdnuwa_xattn_geom* g) { return check2(g) == AMDNUWA_OK; }
 
-extern "C" int amdnuwa_xattn2_fwd(const amdnuwa_xattn_geom* g, const uint16_t* q, int ldq, const amdnuwa_xattn_kv* p, const float* w_th,
-                                  uint16_t* o, int ldo, float* stats, hipStream_t stream) {
+namespace {
+// What every kernel of this file reads: the geometry, the key / value images (f16: the fp16 images, which travel in the lo slots of the
+// image set) and W_th.  Everything else stays zero; an entry point adds its own operands.
+X2Args x2_args(const amdnuwa_xattn_geom* g, const amdnuwa_xattn_kv* p, bool f16, const float* w_th) {
+    X2Args a{};
+    a.Kp = f16 ? p->Kp_lo : p->Kp; a.Vp = f16 ? p->Vp_lo : p->Vp; a.Vt = f16 ? p->Vt_lo : p->Vt; a.valid = p->valid; a.wth = w_th;
+    a.B = g->B; a.n = g->n; a.JP = g->JP; a.nch = g->JP / 32; a.T = g->T; a.scale = g->scale;
+    return a;
+}
+// ... and the operands of the backward's query side (xattn3_bwd_kernel), one workgroup per 64 query rows
+X2Args x2_bwd_args(const amdnuwa_xattn_geom* g, const uint16_t* q, int ldq, const uint16_t* dO, int lddo, const amdnuwa_xattn_kv* p, const float* w_th,
+                   const float* stats, uint16_t* dq, int lddq, float* part_th) {
+    X2Args a = x2_args(g, p, false, w_th);
+    a.q = q; a.ldq = ldq; a.dO = dO; a.lddo = lddo; a.stats = const_cast<float*>(stats); a.dq = dq; a.lddq = lddq; a.part_th = part_th;
+    return a;
+}
+int x2_bwd_query_side(const amdnuwa_xattn_geom* g, const X2Args& a, hipStream_t stream) {
+    return launch_kernel(xattn3_bwd_kernel, dim3(g->B * ((g->n + 63) / 64)), dim3(256), 2 * STAGE, true, stream, a);
+}
+// one body of amdnuwa_xattn2_fwd (bf16 images, no second output) and amdnuwa_xattn2_fwd_f16
+int x2_fwd_run(const amdnuwa_xattn_geom* g, const uint16_t* q, int ldq, const amdnuwa_xattn_kv* p, const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo,
+               int o_lo_f16, float* stats, bool f16, hipStream_t stream) {
     int rc = check2(g);
     if (rc) return rc;
-    if (!q || !p || !p->Kp || !p->Vt || !p->valid || !w_th || !o || ldq % 8 || ldo % 4) return AMDNUWA_ERR_ARG;
+    if (!q || !p || !(f16 ? p->Kp_lo : p->Kp) || !(f16 ? p->Vt_lo : p->Vt) || !p->valid || !w_th || !o || ldq % 8 || ldo % 4) return AMDNUWA_ERR_ARG;
     if (g->B <= 0 || g->n <= 0) return AMDNUWA_OK;
-    X2Args a{};
-    a.q = q; a.ldq = ldq; a.Kp = p->Kp; a.Vp = p->Vp; a.Vt = p->Vt; a.valid = p->valid; a.wth = w_th;
-    a.o = o; a.ldo = ldo; a.stats = stats;
-    a.B = g->B; a.n = g->n; a.JP = g->JP; a.nch = g->JP / 32; a.T = g->T; a.scale = g->scale;
-    const int tiles = (g->n + 63) / 64;
-    const int lds4 = 2 * STAGE + 8 * XCH;
-    (void)hipFuncSetAttribute((const void*)xattn4_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
-    hipLaunchKernelGGL(xattn4_fwd_kernel<false>, dim3(g->B * tiles), dim3(512), lds4, stream, a);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    X2Args a = x2_args(g, p, f16, w_th);
+    a.q = q; a.ldq = ldq; a.o = o; a.ol = o_lo; a.ldo = ldo; a.stats = stats; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0;
+    return launch_if(f16, [&](auto h) {
+        return launch_kernel(xattn4_fwd_kernel<h()>, dim3(g->B * ((g->n + 63) / 64)), dim3(512), 2 * STAGE + 8 * XCH, true, stream, a);
+    });
+}
+}  // namespace
+
+extern "C" int amdnuwa_xattn2_fwd(const amdnuwa_xattn_geom* g, const uint16_t* q, int ldq, const amdnuwa_xattn_kv* p, const float* w_th,
+                                  uint16_t* o, int ldo, float* stats, hipStream_t stream) {
+    return x2_fwd_run(g, q, ldq, p, w_th, o, nullptr, ldo, 0, stats, false, stream);
 }
 
 extern "C" int amdnuwa_xattn2_fwd_f16(const amdnuwa_xattn_geom* g, const uint16_t* q_f16, int ldq, const amdnuwa_xattn_kv* p,
                                       const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, int o_lo_f16, float* stats, hipStream_t stream) {
-    int rc = check2(g);
-    if (rc) return rc;
-    if (!q_f16 || !p || !p->Kp_lo || !p->Vt_lo || !p->valid || !w_th || !o || ldq % 8 || ldo % 4) return AMDNUWA_ERR_ARG;
-    if (g->B <= 0 || g->n <= 0) return AMDNUWA_OK;
-    X2Args a{};
-    a.q = q_f16; a.ldq = ldq; a.Kp = p->Kp_lo; a.Vp = p->Vp_lo; a.Vt = p->Vt_lo; a.valid = p->valid; a.wth = w_th;    // the fp16 images
-    a.o = o; a.ol = o_lo; a.ldo = ldo; a.stats = stats; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0;
-    a.B = g->B; a.n = g->n; a.JP = g->JP; a.nch = g->JP / 32; a.T = g->T; a.scale = g->scale;
-    const int tiles = (g->n + 63) / 64;
-    const int lds4 = 2 * STAGE + 8 * XCH;
-    (void)hipFuncSetAttribute((const void*)xattn4_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
-    hipLaunchKernelGGL(xattn4_fwd_kernel<true>, dim3(g->B * tiles), dim3(512), lds4, stream, a);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return x2_fwd_run(g, q_f16, ldq, p, w_th, o, o_lo, ldo, o_lo_f16, stats, true, stream);
 }
 
 extern "C" size_t amdnuwa_xattn2_bwd_workspace_bytes(const amdnuwa_xattn_geom* g) {
@@ -901,16 +909,9 @@ extern "C" int amdnuwa_xattn2_bwd_ex(const amdnuwa_xattn_geom* g, const uint16_t
         return AMDNUWA_ERR_ARG;
     if (!part_th || part_bytes < amdnuwa_xattn2_bwd_workspace_bytes(g)) return AMDNUWA_ERR_WORKSPACE;
     if (g->B <= 0 || g->n <= 0) return AMDNUWA_OK;
-    X2Args a{};
-    a.q = q; a.ldq = ldq; a.dO = dO; a.lddo = lddo; a.Kp = p->Kp; a.Vp = p->Vp; a.Vt = p->Vt; a.valid = p->valid; a.wth = w_th;
-    a.stats = const_cast<float*>(stats); a.dS = dS; a.Pm = Pm; a.dq = dq; a.lddq = lddq; a.part_th = part_th;
-    a.B = g->B; a.n = g->n; a.JP = g->JP; a.nch = g->JP / 32; a.T = g->T; a.scale = g->scale;
-    const int tiles = (g->n + 63) / 64;
-    a.cm = flags & 1;
-    (void)hipFuncSetAttribute((const void*)xattn3_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
-    hipLaunchKernelGGL(xattn3_bwd_kernel, dim3(g->B * tiles), dim3(256), 2 * STAGE, stream, a);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    X2Args a = x2_bwd_args(g, q, ldq, dO, lddo, p, w_th, stats, dq, lddq, part_th);
+    a.dS = dS; a.Pm = Pm; a.cm = flags & 1;
+    return x2_bwd_query_side(g, a, stream);
 }
 
 // The recomputing backward: query side (dq, dW_th partials, nb / delta) + key side (dKp / dVp), no dS / P' arrays.
@@ -928,18 +929,11 @@ extern "C" int amdnuwa_xattn2_bwd_rc(const amdnuwa_xattn_geom* g, const uint16_t
     if (!part_th || part_bytes < amdnuwa_xattn2_bwd_workspace_bytes(g) || !nbd || nbd_bytes < amdnuwa_xattn2_bwd_rc_stats_bytes(g))
         return AMDNUWA_ERR_WORKSPACE;
     if (g->B <= 0 || g->n <= 0) return AMDNUWA_OK;
-    X2Args a{};
-    a.q = q; a.ldq = ldq; a.dO = dO; a.lddo = lddo; a.Kp = p->Kp; a.Vp = p->Vp; a.Vt = p->Vt; a.valid = p->valid; a.wth = w_th;
-    a.stats = const_cast<float*>(stats); a.dq = dq; a.lddq = lddq; a.part_th = part_th;
-    a.B = g->B; a.n = g->n; a.JP = g->JP; a.nch = g->JP / 32; a.T = g->T; a.scale = g->scale;
+    X2Args a = x2_bwd_args(g, q, ldq, dO, lddo, p, w_th, stats, dq, lddq, part_th);
     a.nostore = 1; a.nbd = nbd; a.dKp = dKp; a.dVp = dVp; a.flags = 0;
-    (void)hipFuncSetAttribute((const void*)xattn3_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
-    hipLaunchKernelGGL(xattn3_bwd_kernel, dim3(g->B * ((g->n + 63) / 64)), dim3(256), 2 * STAGE, stream, a);
-    LAUNCH_CHECK();
-    (void)hipFuncSetAttribute((const void*)xattn5_bwd_kv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ST5);
-    hipLaunchKernelGGL(xattn5_bwd_kv_kernel, dim3(g->B * (g->JP / 32)), dim3(256), 2 * ST5, stream, a);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    int rc = x2_bwd_query_side(g, a, stream);
+    if (rc) return rc;
+    return launch_kernel(xattn5_bwd_kv_kernel, dim3(g->B * (g->JP / 32)), dim3(256), 2 * ST5, true, stream, a);
 }
 
 AMDNUWA_SAT_ACCESSOR(xattn2)

@@ -1005,6 +1005,27 @@ int check6(const amdnuwa_xattn_geom* g) {
     return AMDNUWA_OK;
 }
 
+bool x6_images_ok(const amdnuwa_xattn6_kv* kv) { return kv && kv->K6 && kv->V6 && kv->vbits; }
+
+// What both args structs share: the images, the null key / value, W_th and the batch; x6_args / x6b_args add the forward's and the
+// backward's geometry words.  Everything else stays zero; an entry point adds its own operands.
+template <class Args>
+Args x6_common(const amdnuwa_xattn_geom* g, const amdnuwa_xattn6_kv* kv, const float* null_k, const float* null_v, const float* w_th) {
+    Args a{};
+    a.K6 = (const char*)kv->K6; a.V6 = (const char*)kv->V6; a.vbits = kv->vbits; a.null_k = null_k; a.null_v = null_v; a.wth = w_th;
+    a.B = g->B; a.n = g->n;
+    return a;
+}
+X6Args x6_args(const amdnuwa_xattn_geom* g, const amdnuwa_xattn6_kv* kv, const float* null_k, const float* null_v, const float* w_th) {
+    X6Args a = x6_common<X6Args>(g, kv, null_k, null_v, w_th);
+    a.nch = amdnuwa_xattn6_nch(g->T); a.c1 = g->scale * 1.4426950408889634f;
+    return a;
+}
+X6BArgs x6b_args(const amdnuwa_xattn_geom* g, const amdnuwa_xattn6_kv* kv, const float* null_k, const float* null_v, const float* w_th) {
+    X6BArgs a = x6_common<X6BArgs>(g, kv, null_k, null_v, w_th);
+    a.nch = g->JP / 32; a.T = g->T; a.scale = g->scale;
+    return a;
+}
 }  // namespace
 
 extern "C" int amdnuwa_xattn6_supported(const amdnuwa_xattn_geom* g) { return check6(g) == AMDNUWA_OK; }
@@ -1017,17 +1038,13 @@ extern "C" int amdnuwa_xattn6_pack(const amdnuwa_xattn_geom* g, const uint16_t* 
                                    const amdnuwa_xattn6_kv* out, hipStream_t stream) {
     int rc = check6(g);
     if (rc) return rc;
-    if (!kv16 || !out || !out->K6 || !out->V6 || !out->vbits || ldkv % 8 || ldkv < 2 * NH * DH) return AMDNUWA_ERR_ARG;
+    if (!kv16 || !x6_images_ok(out) || ldkv % 8 || ldkv < 2 * NH * DH) return AMDNUWA_ERR_ARG;
     if (g->B <= 0) return AMDNUWA_OK;
     const int nch = amdnuwa_xattn6_nch(g->T);
-    if (f16)
-        hipLaunchKernelGGL(xattn6_pack_kernel<true>, dim3(g->B * nch), dim3(256), 0, stream, kv16, ldkv, context_mask, (char*)out->K6, (char*)out->V6,
-                           out->vbits, g->T, nch);
-    else
-        hipLaunchKernelGGL(xattn6_pack_kernel<false>, dim3(g->B * nch), dim3(256), 0, stream, kv16, ldkv, context_mask, (char*)out->K6, (char*)out->V6,
-                           out->vbits, g->T, nch);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return launch_if(f16 != 0, [&](auto h) {
+        return launch_kernel(xattn6_pack_kernel<h()>, dim3(g->B * nch), dim3(256), 0, false, stream, kv16, ldkv, context_mask, (char*)out->K6, (char*)out->V6,
+                             out->vbits, g->T, nch);
+    });
 }
 
 extern "C" int amdnuwa_xattn6_fwd(const amdnuwa_xattn_geom* g, const uint16_t* q16, int ldq, const amdnuwa_xattn6_kv* kv, const float* null_k,
@@ -1035,26 +1052,15 @@ extern "C" int amdnuwa_xattn6_fwd(const amdnuwa_xattn_geom* g, const uint16_t* q
                                   int f16, hipStream_t stream) {
     int rc = check6(g);
     if (rc) return rc;
-    if (!q16 || !kv || !kv->K6 || !kv->V6 || !kv->vbits || !null_k || !null_v || !w_th || ldq % 8 || ldo % 4) return AMDNUWA_ERR_ARG;
+    if (!q16 || !x6_images_ok(kv) || !null_k || !null_v || !w_th || ldq % 8 || ldo % 4) return AMDNUWA_ERR_ARG;
     if (!o && !(o_lo && o_lo_f16)) return AMDNUWA_ERR_ARG;        // o == NULL: the fp16 copy is the only output
     if (g->B <= 0 || g->n <= 0) return AMDNUWA_OK;
-    X6Args a{};
-    a.q = q16; a.ldq = ldq; a.K6 = (const char*)kv->K6; a.V6 = (const char*)kv->V6; a.vbits = kv->vbits;
-    a.null_k = null_k; a.null_v = null_v; a.wth = w_th;
-    a.o = o; a.ol = o_lo; a.ldo = ldo; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0; a.stats = stats;
-    a.B = g->B; a.n = g->n; a.nch = amdnuwa_xattn6_nch(g->T); a.c1 = g->scale * 1.4426950408889634f;
+    X6Args a = x6_args(g, kv, null_k, null_v, w_th);
+    a.q = q16; a.ldq = ldq; a.o = o; a.ol = o_lo; a.ldo = ldo; a.ol_f16 = (o_lo && o_lo_f16) ? 1 : 0; a.stats = stats;
     const int tiles = (g->n + 63) / 64, NT = g->B * tiles;
     // one workgroup per CU (160 KiB of LDS each); the grid stays a multiple of 8 so that a workgroup's items all lie in one XCD's slab
     const int grid = NT < cu_count() ? NT : cu_count() / 8 * 8;
-    if (f16) {
-        (void)hipFuncSetAttribute((const void*)xattn6_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        hipLaunchKernelGGL(xattn6_fwd_kernel<true>, dim3(grid), dim3(512), LDS_BYTES, stream, a);
-    } else {
-        (void)hipFuncSetAttribute((const void*)xattn6_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        hipLaunchKernelGGL(xattn6_fwd_kernel<false>, dim3(grid), dim3(512), LDS_BYTES, stream, a);
-    }
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return launch_if(f16 != 0, [&](auto h) { return launch_kernel(xattn6_fwd_kernel<h()>, dim3(grid), dim3(512), LDS_BYTES, true, stream, a); });
 }
 
 extern "C" size_t amdnuwa_xattn6_bwd_image_bytes(const amdnuwa_xattn_geom* g) {
@@ -1064,42 +1070,27 @@ namespace {
 int x6_pack_bwd(const amdnuwa_xattn_geom* g, const uint16_t* kv, int ldkv, const float* null_k, const float* null_v, const uint8_t* context_mask,
                 const amdnuwa_xattn6_kv* out, bool f16, hipStream_t stream) {
     if (!amdnuwa_xattn6_bwd_image_bytes(g)) return g ? AMDNUWA_ERR_UNSUPPORTED : AMDNUWA_ERR_ARG;
-    if (!kv || !null_k || !null_v || !out || !out->K6 || !out->V6 || !out->vbits || ldkv % 8 || ldkv < 2 * NH * DH) return AMDNUWA_ERR_ARG;
+    if (!kv || !null_k || !null_v || !x6_images_ok(out) || ldkv % 8 || ldkv < 2 * NH * DH) return AMDNUWA_ERR_ARG;
     if (g->B <= 0) return AMDNUWA_OK;
     const int nch = g->JP / 32;
-    if (f16)
-        hipLaunchKernelGGL(xattn6_pack_bwd_kernel<true>, dim3(g->B * nch), dim3(256), 0, stream, kv, ldkv, null_k, null_v, context_mask, (char*)out->K6,
-                           (char*)out->V6, out->vbits, g->T, nch);
-    else
-        hipLaunchKernelGGL(xattn6_pack_bwd_kernel<false>, dim3(g->B * nch), dim3(256), 0, stream, kv, ldkv, null_k, null_v, context_mask, (char*)out->K6,
-                           (char*)out->V6, out->vbits, g->T, nch);
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return launch_if(f16, [&](auto h) {
+        return launch_kernel(xattn6_pack_bwd_kernel<h()>, dim3(g->B * nch), dim3(256), 0, false, stream, kv, ldkv, null_k, null_v, context_mask, (char*)out->K6,
+                             (char*)out->V6, out->vbits, g->T, nch);
+    });
 }
 int x6_bwd(const amdnuwa_xattn_geom* g, const uint16_t* q, int ldq, const uint16_t* dO, int lddo, const amdnuwa_xattn6_kv* kv, const float* null_k,
            const float* null_v, const float* w_th, const float* stats, uint16_t* dS, uint16_t* Pm, uint16_t* dq, int lddq, float* part_th,
            size_t part_bytes, bool g16, hipStream_t stream) {
     if (!amdnuwa_xattn6_bwd_image_bytes(g)) return g ? AMDNUWA_ERR_UNSUPPORTED : AMDNUWA_ERR_ARG;
-    if (!q || !dO || !kv || !kv->K6 || !kv->V6 || !kv->vbits || !null_k || !null_v || !w_th || !stats || !dS || !Pm || !dq || ldq % 8 || lddo % 8 || lddq % 4)
-        return AMDNUWA_ERR_ARG;
+    if (!q || !dO || !x6_images_ok(kv) || !null_k || !null_v || !w_th || !stats || !dS || !Pm || !dq || ldq % 8 || lddo % 8 || lddq % 4) return AMDNUWA_ERR_ARG;
     if (!part_th || part_bytes < amdnuwa_xattn6_bwd_workspace_bytes(g)) return AMDNUWA_ERR_WORKSPACE;
     if (g->B <= 0 || g->n <= 0) return AMDNUWA_OK;
-    X6BArgs a{};
-    a.q = q; a.ldq = ldq; a.dO = dO; a.lddo = lddo; a.K6 = (const char*)kv->K6; a.V6 = (const char*)kv->V6; a.vbits = kv->vbits;
-    a.null_k = null_k; a.null_v = null_v; a.wth = w_th; a.stats = stats; a.dS = dS; a.Pm = Pm; a.dq = dq; a.lddq = lddq; a.part_th = part_th;
-    a.B = g->B; a.n = g->n; a.nch = g->JP / 32; a.T = g->T; a.scale = g->scale;
+    X6BArgs a = x6b_args(g, kv, null_k, null_v, w_th);
+    a.q = q; a.ldq = ldq; a.dO = dO; a.lddo = lddo; a.stats = stats; a.dS = dS; a.Pm = Pm; a.dq = dq; a.lddq = lddq; a.part_th = part_th;
     // LDS: the two-stage K + V ring, the null key / value rows, one 4-KiB turning tile per wave (the dW_th products)
     constexpr int LB = 2 * STAGE + 4096 + 4 * 4096;
     const dim3 grid(g->B * ((g->n + 63) / 64));
-    if (g16) {
-        (void)hipFuncSetAttribute((const void*)xattn6_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LB);
-        hipLaunchKernelGGL(xattn6_bwd_kernel<true>, grid, dim3(256), LB, stream, a);
-    } else {
-        (void)hipFuncSetAttribute((const void*)xattn6_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LB);
-        hipLaunchKernelGGL(xattn6_bwd_kernel<false>, grid, dim3(256), LB, stream, a);
-    }
-    LAUNCH_CHECK();
-    return AMDNUWA_OK;
+    return launch_if(g16, [&](auto h) { return launch_kernel(xattn6_bwd_kernel<h()>, grid, dim3(256), LB, true, stream, a); });
 }
 }  // namespace
 

@@ -689,6 +689,16 @@ def empty_bf_f16(shape, device):
     return BF(torch.empty(shape, dtype=torch.bfloat16, device=device), None, torch.empty(shape, dtype=torch.float16, device=device))
 
 
+def core_out(shape, device, o_f16, lo=True):
+    """the output of an attention core, and the (o_lo pointer, o_lo_f16 flag) of its call.  o_f16 False: a hi + lo pair (lo=False: the bf16 copy
+    alone); True: a bf16 copy + an fp16 copy; 'only': the fp16 copy alone (the block's backward runs on fp16 gradients)"""
+    if o_f16 == 'only':
+        o = BF(None, None, torch.empty(shape, dtype=torch.float16, device=device))
+    else:
+        o = empty_bf_f16(shape, device) if o_f16 else empty_bf(shape, device, lo=lo)
+    return o, _p(o.f16 if o_f16 else o.lo), 1 if o_f16 else 0
+
+
 @_family('ln')
 def ln_fwd(x, w, b, *, resid=None, stable=False, eps=1e-5, shift=None, f16=False, minus=False):
     """x fp32 [R, D] contiguous (or a hi-only BF pair).  resid None -> (BF out, mean, rstd, inv_amax);
@@ -1120,15 +1130,9 @@ def sparse3dna_fwd(g, qkv, wth, rel_bias=None, o_f16=False, keep=None, drop_scal
     if qkv.f16 is not None:            # fp16 operand form: single fp16 MFMAs; output hi + lo, or (o_f16) a bf16 copy + an fp16 copy
         q16, k16, v16 = (qkv.f16[:, i * inner:(i + 1) * inner] for i in range(3))
         dev = qkv.f16.device
-        if o_f16 == 'only':            # ... or the fp16 copy alone (the block's backward runs on fp16 gradients: sparse3dna_bwd16)
-            o = BF(None, None, torch.empty((R, inner), dtype=torch.float16, device=dev))
-        elif o_f16:
-            o = BF(torch.empty((R, inner), dtype=torch.bfloat16, device=dev), None,
-                   torch.empty((R, inner), dtype=torch.float16, device=dev))
-        else:
-            o = empty_bf((R, inner), dev, lo=True)
-        _s3_call('amdnuwa_sparse3dna_fwd_f16', [C.byref(g), _p(q16), _p(k16), _p(v16), qkv.f16.stride(0), _p(wth), _p(o.hi),
-                                                _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0], k8, drop_scale)
+        o, o_lo, o_lo_f16 = core_out((R, inner), dev, o_f16)   # ('only': the fp16 copy alone, for sparse3dna_bwd16)
+        _s3_call('amdnuwa_sparse3dna_fwd_f16', [C.byref(g), _p(q16), _p(k16), _p(v16), qkv.f16.stride(0), _p(wth), _p(o.hi), o_lo, inner, o_lo_f16],
+                 k8, drop_scale)
         return o
     o = empty_bf((R, inner), qkv.hi.device, lo=qkv.lo is not None)
     q, k, v = (view(qkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
@@ -1447,26 +1451,18 @@ class PackedKV:
 def xattn_pack(g, kv, null_k, null_v, mask_u8, out=None, lean=False):
     """kv with an f16 copy: the lo images of the result are FP16 images (for xattn2_fwd_f16), not bf16 residuals.
     out: a PackedKV of the same geometry / operand form to pack INTO (a captured HIP graph keeps reading the same buffers)"""
-    L = _lib.lib()
+    entry, lo = 'amdnuwa_xattn_pack', kv.lo
     if out is not None:
         assert kv.f16 is None and (out.Kp.lo is not None) == (kv.lo is not None)
-        check(L.amdnuwa_xattn_pack(C.byref(g), _p(kv.hi), _p(kv.lo), kv.hi.stride(0), _p(null_k), _p(null_v), _p(mask_u8),
-                                   C.byref(out.struct), _stream()), 'amdnuwa_xattn_pack')
-        return out
-    if lean == 'bwd':
-        pk = PackedKV(g, kv.hi.device, False, lean='bwd')
-        check(L.amdnuwa_xattn_pack(C.byref(g), _p(kv.hi), None, kv.hi.stride(0), _p(null_k), _p(null_v), _p(mask_u8),
-                                   C.byref(pk.struct), _stream()), 'amdnuwa_xattn_pack')
-        return pk
-    if kv.f16 is not None:
-        pk = PackedKV(g, kv.hi.device, True, lean=lean)
-        check(L.amdnuwa_xattn_pack_f16(C.byref(g), _p(kv.hi), _p(kv.f16), kv.hi.stride(0), _p(null_k), _p(null_v), _p(mask_u8),
-                                       C.byref(pk.struct), _stream()), 'amdnuwa_xattn_pack_f16')
+        pk = out
+    elif lean == 'bwd':
+        pk, lo = PackedKV(g, kv.hi.device, False, lean='bwd'), None
+    elif kv.f16 is not None:
+        pk, lo, entry = PackedKV(g, kv.hi.device, True, lean=lean), kv.f16, 'amdnuwa_xattn_pack_f16'
         pk.f16 = True
-        return pk
-    pk = PackedKV(g, kv.hi.device, kv.lo is not None)
-    check(L.amdnuwa_xattn_pack(C.byref(g), _p(kv.hi), _p(kv.lo), kv.hi.stride(0), _p(null_k), _p(null_v), _p(mask_u8),
-                               C.byref(pk.struct), _stream()), 'amdnuwa_xattn_pack')
+    else:
+        pk = PackedKV(g, kv.hi.device, kv.lo is not None)
+    check(getattr(_lib.lib(), entry)(C.byref(g), _p(kv.hi), _p(lo), kv.hi.stride(0), _p(null_k), _p(null_v), _p(mask_u8), C.byref(pk.struct), _stream()), entry)
     return pk
 
 
@@ -1478,24 +1474,19 @@ def xattn2_fwd_f16(g, q, pk, wth, o_f16=False):
     assert q.f16 is not None and getattr(pk, 'f16', False)
     inner = g.heads * g.dim_head
     dev = q.hi.device
-    if o_f16:
-        o = BF(torch.empty((g.B * g.n, inner), dtype=torch.bfloat16, device=dev), None,
-               torch.empty((g.B * g.n, inner), dtype=torch.float16, device=dev))
-    else:
-        o = empty_bf((g.B * g.n, inner), dev, lo=True)
+    o, o_lo, o_lo_f16 = core_out((g.B * g.n, inner), dev, bool(o_f16))     # (this core always writes the bf16 copy)
     stats = torch.empty((g.B, g.heads, g.n, 2), dtype=torch.float32, device=dev)
-    check(L.amdnuwa_xattn2_fwd_f16(C.byref(g), _p(q.f16), q.f16.stride(0), C.byref(pk.struct), _p(wth), _p(o.hi),
-                                   _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _p(stats), _stream()), 'amdnuwa_xattn2_fwd_f16')
+    check(L.amdnuwa_xattn2_fwd_f16(C.byref(g), _p(q.f16), q.f16.stride(0), C.byref(pk.struct), _p(wth), _p(o.hi), o_lo, inner, o_lo_f16, _p(stats), _stream()),
+          'amdnuwa_xattn2_fwd_f16')
     return o, stats
 
 
 class PackedKV6:
     """key / value images of the xattn6 cross-attention kernels (amdnuwa_xattn6_pack): K6 / V6 [B, nch, heads, 32, 64] 16-bit in the
-    kernels' LDS order, vbits [B, nch] (bit j of word c: context key 32 c + j takes part)"""
+    kernels' LDS order, vbits [B, nch] (bit j of word c: context key 32 c + j takes part); nch: the chunk count, amdnuwa_xattn6_nch(T) unless given"""
 
-    def __init__(self, g, device, f16):
-        L = _lib.lib()
-        self.nch = L.amdnuwa_xattn6_nch(g.T)
+    def __init__(self, g, device, f16, nch=None):
+        self.nch = _lib.lib().amdnuwa_xattn6_nch(g.T) if nch is None else nch
         dt = torch.float16 if f16 else torch.bfloat16
         sh = (g.B, self.nch, g.heads, 32, g.dim_head)
         self.K6, self.V6 = torch.empty(sh, dtype=dt, device=device), torch.empty(sh, dtype=dt, device=device)
@@ -1543,33 +1534,18 @@ def xattn6_fwd(g, q16, pk, null_k, null_v, wth, o_f16=False, lo=True):
     assert pk.f16 == f16 and q16.stride(1) == 1
     inner = g.heads * g.dim_head
     dev = q16.device
-    if o_f16 == 'only':                # the fp16 copy alone (the block's backward runs on fp16 gradients: xattn6_bwd16)
-        o = BF(None, None, torch.empty((g.B * g.n, inner), dtype=torch.float16, device=dev))
-    elif o_f16:
-        o = BF(torch.empty((g.B * g.n, inner), dtype=torch.bfloat16, device=dev), None,
-               torch.empty((g.B * g.n, inner), dtype=torch.float16, device=dev))
-    else:
-        o = empty_bf((g.B * g.n, inner), dev, lo=lo)
+    o, o_lo, o_lo_f16 = core_out((g.B * g.n, inner), dev, o_f16, lo)       # ('only': the fp16 copy alone, for xattn6_bwd16)
     stats = torch.empty((g.B, g.heads, g.n, 2), dtype=torch.float32, device=dev)
-    check(L.amdnuwa_xattn6_fwd(C.byref(g), _p(q16), q16.stride(0), C.byref(pk.struct), _p(null_k), _p(null_v), _p(wth), _p(o.hi),
-                               _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _p(stats), 1 if f16 else 0, _stream()),
-          'amdnuwa_xattn6_fwd')
+    check(L.amdnuwa_xattn6_fwd(C.byref(g), _p(q16), q16.stride(0), C.byref(pk.struct), _p(null_k), _p(null_v), _p(wth), _p(o.hi), o_lo, inner, o_lo_f16,
+                               _p(stats), 1 if f16 else 0, _stream()), 'amdnuwa_xattn6_fwd')
     return o, stats
 
 
-class PackedKV6B:
+class PackedKV6B(PackedKV6):
     """bf16 [key][d] images of the xattn6 backward (amdnuwa_xattn6_pack_bwd): key 0 = the null key, keys 1..T the context, JP / 32 chunks"""
 
     def __init__(self, g, device, f16=False):
-        self.nch = g.JP // 32
-        self.f16 = f16
-        sh = (g.B, self.nch, g.heads, 32, g.dim_head)
-        dt = torch.float16 if f16 else torch.bfloat16
-        self.K6, self.V6 = torch.empty(sh, dtype=dt, device=device), torch.empty(sh, dtype=dt, device=device)
-        self.vbits = torch.empty((g.B, self.nch), dtype=torch.int32, device=device)
-        s = _lib.X6KV()
-        s.K6, s.V6, s.vbits = _p(self.K6), _p(self.V6), _p(self.vbits)
-        self.struct = s
+        super().__init__(g, device, f16, nch=g.JP // 32)
 
 
 def xattn6_bwd_ok(g):
@@ -1588,6 +1564,14 @@ def xattn6_pack_bwd(g, kv16, null_k, null_v, mask_u8):
     return pk
 
 
+def _wth_partials(g, nbytes, dev):
+    """the talking-heads partials of a backward core: (part fp32 [workgroups, h * h] for the core to fill, its size in bytes as the query
+    nbytes gives it, total) with total() = the fixed-order sum over the workgroups as [h, h]"""
+    nb = nbytes(C.byref(g))
+    part = torch.empty((nb // (4 * g.heads * g.heads), g.heads * g.heads), dtype=torch.float32, device=dev)
+    return part, nb, lambda: colsum(part).reshape(g.heads, g.heads)
+
+
 @_family('xattn', _x_work('bwd'))
 def xattn6_bwd16(g, q16, dO16, pk, wth, stats, s2):
     """fp16-gradient form of xattn6_bwd: q16 fp16 [B*n, inner] (the forward's operand), dO16 = fp16(S dO), pk = fp16 images, s2 = device {S, 1 / S}.
@@ -1599,12 +1583,10 @@ def xattn6_bwd16(g, q16, dO16, pk, wth, stats, s2):
     dq = torch.empty((g.B * g.n, inner), dtype=torch.float16, device=dev)
     shape = (g.B, g.heads, g.JP // 32, g.n, 32)
     dS, Pm = torch.empty(shape, dtype=torch.float16, device=dev), torch.empty(shape, dtype=torch.float16, device=dev)
-    nb = L.amdnuwa_xattn6_bwd_workspace_bytes(C.byref(g))
-    part = torch.empty((nb // (4 * g.heads * g.heads), g.heads * g.heads), dtype=torch.float32, device=dev)
+    part, nb, total = _wth_partials(g, L.amdnuwa_xattn6_bwd_workspace_bytes, dev)
     check(L.amdnuwa_xattn6_bwd_f16(C.byref(g), _p(q16), q16.stride(0), _p(dO16), dO16.stride(0), C.byref(pk.struct), _p(pk.null_k), _p(pk.null_v), _p(wth),
                                    _p(stats), _p(dS), _p(Pm), _p(dq), inner, _p(part), nb, _stream()), 'amdnuwa_xattn6_bwd_f16')
-    dwth = (colsum(part) * (s2[1] * 64.0)).reshape(g.heads, g.heads)  # fixed-order reduction over the workgroups; the partials carry S / 64 (the V image's 2^-6)
-    return dq, dS, Pm, dwth
+    return dq, dS, Pm, total() * (s2[1] * 64.0)          # the partials carry S / 64 (the V image's 2^-6)
 
 
 @_family('xattn', _x_work('bwd'))
@@ -1617,12 +1599,10 @@ def xattn6_bwd(g, q, dO, pk, wth, stats):
     dq = empty_bf((g.B * g.n, inner), dev, lo=False)
     shape = (g.B, g.heads, g.JP // 32, g.n, 32)
     dS, Pm = empty_bf(shape, dev, lo=False), empty_bf(shape, dev, lo=False)
-    nb = L.amdnuwa_xattn6_bwd_workspace_bytes(C.byref(g))
-    part = torch.empty((nb // (4 * g.heads * g.heads), g.heads * g.heads), dtype=torch.float32, device=dev)
+    part, nb, total = _wth_partials(g, L.amdnuwa_xattn6_bwd_workspace_bytes, dev)
     check(L.amdnuwa_xattn6_bwd(C.byref(g), _p(q.hi), q.hi.stride(0), _p(dO.hi), dO.hi.stride(0), C.byref(pk.struct), _p(pk.null_k), _p(pk.null_v), _p(wth), _p(stats),
                                _p(dS.hi), _p(Pm.hi), _p(dq.hi), inner, _p(part), nb, _stream()), 'amdnuwa_xattn6_bwd')
-    dwth = colsum(part).reshape(g.heads, g.heads)          # fixed-order reduction over the workgroups
-    return dq, BF(dS.hi, None), BF(Pm.hi, None), dwth
+    return dq, BF(dS.hi, None), BF(Pm.hi, None), total()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1699,14 +1679,10 @@ def cattn_fwd(g, q16, k16, v16, null_k, null_v, wth, mask_u8=None, o_f16=False, 
     assert k16.shape[0] == v16.shape[0] == g.B * cattn_keys(g) and (mask_u8 is None or mask_u8.numel() == k16.shape[0])
     _chk_dev(q16, k16, v16, null_k, null_v, wth, mask_u8)
     dev = q16.device
-    if o_f16:
-        o = BF(torch.empty((g.B * g.n, inner), dtype=torch.bfloat16, device=dev), None,
-               torch.empty((g.B * g.n, inner), dtype=torch.float16, device=dev))
-    else:
-        o = empty_bf((g.B * g.n, inner), dev, lo=lo)
+    o, o_lo, o_lo_f16 = core_out((g.B * g.n, inner), dev, bool(o_f16), lo)    # (the wrapper always asks for the bf16 copy)
     stats = torch.empty((g.B, g.heads, g.n, 2), dtype=torch.float32, device=dev)
     args = (C.byref(g), _p(q16), q16.stride(0), _p(k16), _p(v16), k16.stride(0), _p(mask_u8), _p(null_k), _p(null_v), _p(wth),
-            _p(o.hi), _p(o.f16 if o_f16 else o.lo), inner, 1 if o_f16 else 0, _p(stats), 1 if f16 else 0)
+            _p(o.hi), o_lo, inner, o_lo_f16, _p(stats), 1 if f16 else 0)
     if keep is not None:
         kp, _, k0 = _chk_keep(g, keep, False)
         _chk_dev(q16, kp, k0)
@@ -1847,12 +1823,11 @@ def xattn2_bwd(g, q, dO, pk, wth, stats, chunk_major=None):
     shape = (g.B, g.heads, g.JP // 32, g.n, 32) if cm else (g.B, g.heads, g.n, g.JP)
     dS = empty_bf(shape, dev, lo=False)
     Pm = empty_bf(shape, dev, lo=False)
-    nb = L.amdnuwa_xattn2_bwd_workspace_bytes(C.byref(g))
-    part = torch.empty((nb // (4 * g.heads * g.heads), g.heads * g.heads), dtype=torch.float32, device=dev)
+    part, nb, total = _wth_partials(g, L.amdnuwa_xattn2_bwd_workspace_bytes, dev)
     check(L.amdnuwa_xattn2_bwd_ex(C.byref(g), _p(q.hi), q.hi.stride(0), _p(dO.hi), dO.hi.stride(0), C.byref(pk.struct), _p(wth),
                                   _p(stats), _p(dS.hi), _p(Pm.hi), _p(dq.hi), inner, _p(part), nb, 1 if cm else 0, _stream()),
           'amdnuwa_xattn2_bwd_ex')
-    dwth = colsum(part).reshape(g.heads, g.heads)          # fixed-order reduction over the workgroups
+    dwth = total()
     if cm:
         return dq, BF(dS.hi, None), BF(Pm.hi, None), dwth
     # lane groups of the last chunk whose 8 keys are all padding write nothing: hand out the columns that exist (views: the row pitch stays JP)
@@ -1888,8 +1863,7 @@ def xattn2_bwd_rc(g, q, dO, pk, wth, stats):
     inner = g.heads * g.dim_head
     dev = q.hi.device
     dq = empty_bf((g.B * g.n, inner), dev, lo=False)
-    nb = L.amdnuwa_xattn2_bwd_workspace_bytes(C.byref(g))
-    part = torch.empty((nb // (4 * g.heads * g.heads), g.heads * g.heads), dtype=torch.float32, device=dev)
+    part, nb, total = _wth_partials(g, L.amdnuwa_xattn2_bwd_workspace_bytes, dev)
     sb = L.amdnuwa_xattn2_bwd_rc_stats_bytes(C.byref(g))
     nbd = torch.empty(sb // 4, dtype=torch.float32, device=dev)
     dKp = torch.empty((g.B, g.heads, g.JP, g.dim_head), dtype=torch.float32, device=dev)
@@ -1897,23 +1871,31 @@ def xattn2_bwd_rc(g, q, dO, pk, wth, stats):
     check(L.amdnuwa_xattn2_bwd_rc(C.byref(g), _p(q.hi), q.hi.stride(0), _p(dO.hi), dO.hi.stride(0), C.byref(pk.struct), _p(wth),
                                   _p(stats), _p(dq.hi), inner, _p(part), nb, _p(nbd), sb, _p(dKp), _p(dVp), _stream()),
           'amdnuwa_xattn2_bwd_rc')
-    return dq, dKp, dVp, colsum(part).reshape(g.heads, g.heads)
+    return dq, dKp, dVp, total()
+
+
+def _xattn_kv_products(g, Mx, cm, dev, products, **fields):
+    """dKp, dVp fp32 [B, h, JP, dh] = alpha A^T B per (sample, head) for the two products (A, A lo, B [B*n, ld], B lo, alpha): batched TN GEMMs
+    (reduction over queries) on Mx key rows; fields: further descriptor words.  Rows Mx .. JP - 1 of both results -- padding keys -- are
+    deliberately unwritten and never read (xattn_unpack takes the key rows only)"""
+    dKp = torch.empty((g.B, g.heads, g.JP, g.dim_head), dtype=torch.float32, device=dev)
+    dVp = torch.empty_like(dKp)
+    for out, (A, Alo, Bm, Blo, alpha) in zip((dKp, dVp), products):
+        d = _xattn_tn_desc(g, Mx, cm)
+        d.A, d.Alo, d.B, d.Blo, d.ldb = _p(A), _p(Alo), _p(Bm), _p(Blo), Bm.stride(0)
+        d.strideB, d.strideB_inner = g.n * Bm.stride(0), g.dim_head
+        d.C, d.alpha = _p(out), float(alpha)
+        for name, value in fields.items():
+            setattr(d, name, value)
+        gemm_tn_batched(d, dev)
+    return dKp, dVp
 
 
 @_family('xattn', _x_work('kv'))
 def xattn_kv_grads16(g, dS16, Pm16, q16, dO16, s2):
     """fp16-gradient form of xattn_kv_grads on the chunk-major fp16 arrays of xattn6_bwd16: dKp = scale / S * (S dS)^T q, dVp = 1 / S * Pm^T (S dO)"""
-    dev = q16.device
-    Mx = xattn_permuted_extent(g)
-    dKp = torch.empty((g.B, g.heads, g.JP, g.dim_head), dtype=torch.float32, device=dev)
-    dVp = torch.empty_like(dKp)
-    for (A, Bm, out, alpha) in ((dS16, q16, dKp, g.scale), (Pm16, dO16, dVp, 1.0)):
-        d = _xattn_tn_desc(g, Mx, True)
-        d.A, d.B, d.ldb, d.ab_f16 = _p(A), _p(Bm), Bm.stride(0), 1
-        d.strideB, d.strideB_inner = g.n * Bm.stride(0), g.dim_head
-        d.C, d.alpha, d.alpha_dev = _p(out), float(alpha), s2.data_ptr() + 4
-        gemm_tn_batched(d, dev)
-    return dKp, dVp
+    return _xattn_kv_products(g, xattn_permuted_extent(g), True, q16.device, ((dS16, None, q16, None, g.scale), (Pm16, None, dO16, None, 1.0)),
+                              ab_f16=1, alpha_dev=s2.data_ptr() + 4)
 
 
 def xattn_bwd16_ok(g):
@@ -1931,21 +1913,13 @@ def xattn_bwd16_ok(g):
 def xattn_kv_grads(g, dS, Pm, q, dO):
     """dKp = scale * dS^T q, dVp = Pm^T dO per (sample, head): two batched TN GEMMs (reduction over queries).
     returns fp32 [B, h, JP, dh] x 2 (rows past the last column of dS / Pm -- padding keys -- are not written)"""
-    dev = q.hi.device
     cm = dS.hi.dim() == 5                      # chunk-major dS / Pm (xattn2_bwd)
     Mx = xattn_permuted_extent(g) if cm else dS.hi.shape[-1]      # (xattn2_bwd hands out only the columns that hold a key)
-    # deliberately unwritten and never read (xattn_unpack takes the key rows only): rows Mx .. JP - 1 of both results
-    dKp = torch.empty((g.B, g.heads, g.JP, g.dim_head), dtype=torch.float32, device=dev)
-    dVp = torch.empty_like(dKp)
-    for (A, Bm, out, alpha) in ((dS, q, dKp, g.scale), (Pm, dO, dVp, 1.0)):
+
+    def product(A, Bm, alpha):                 # (the lo parts count only where both operands carry one)
         x3 = A.lo is not None and Bm.lo is not None
-        d = _xattn_tn_desc(g, Mx, cm)
-        d.A, d.Alo = _p(A.hi), _p(A.lo) if x3 else None
-        d.B, d.Blo, d.ldb = _p(Bm.hi), _p(Bm.lo) if x3 else None, Bm.hi.stride(0)
-        d.strideB, d.strideB_inner = g.n * Bm.hi.stride(0), g.dim_head
-        d.C, d.alpha = _p(out), float(alpha)
-        gemm_tn_batched(d, dev)
-    return dKp, dVp
+        return A.hi, A.lo if x3 else None, Bm.hi, Bm.lo if x3 else None, alpha
+    return _xattn_kv_products(g, Mx, cm, q.hi.device, (product(dS, q, g.scale), product(Pm, dO, 1.0)))
 
 
 def xattn_key_positions(JP, device):

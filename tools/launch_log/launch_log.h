@@ -2,12 +2,13 @@
 //
 //     hipcc ... -include tools/launch_log/launch_log.h FILE.hip        (tools/launch_log/run.py does this)
 //
-// turns hipFuncSetAttribute, hipLaunchKernelGGL, hipGetLastError and hipMemsetAsync of that file into a logger: nothing reaches a device, so
+// turns hipFuncSetAttribute, hipLaunchKernelGGL, hipGetLastError, hipMemsetAsync and hipMemcpyAsync of that file into a logger: nothing reaches a device, so
 // the entry points can be walked with fake operand pointers on a machine without a GPU.  One line per call:
 //
 //     attr   <kernel> <attribute> <value>
 //     launch <kernel> grid x y z block x y z lds <bytes> args <64-bit FNV-1a of the argument bytes>
 //     memset <value> <bytes>
+//     memcpy <bytes> <kind>
 //
 // <kernel> is the offset of the host-side kernel handle inside the scratch library ("+0x..."); run.py turns it into the symbol through the
 // library's symbol table.  Every argument is converted to the kernel's own parameter type before it is hashed, so the hash does not depend
@@ -65,6 +66,12 @@ inline hipError_t memset_async(void*, int value, size_t bytes, hipStream_t) {
     lines() += buf;
     return hipSuccess;
 }
+inline hipError_t memcpy_async(void*, const void*, size_t bytes, hipMemcpyKind kind, hipStream_t) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "memcpy %zu %d\n", bytes, (int)kind);
+    lines() += buf;
+    return hipSuccess;
+}
 
 }  // namespace launch_log
 
@@ -82,3 +89,4 @@ extern "C" __attribute__((visibility("default"), weak)) size_t launch_log_take(c
 #define hipFuncSetAttribute(...) ::launch_log::attr(__VA_ARGS__)
 #define hipGetLastError() hipSuccess
 #define hipMemsetAsync(...) ::launch_log::memset_async(__VA_ARGS__)
+#define hipMemcpyAsync(...) ::launch_log::memcpy_async(__VA_ARGS__)
