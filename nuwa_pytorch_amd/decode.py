@@ -186,6 +186,10 @@ class IncrementalDecoder:
                     raise NotImplementedError('IncrementalDecoder needs causal Sparse3DNA')
                 else:
                     grid = (inner.video_shape, inner.kernel_size, inner.dilation)
+                if inner.heads > 8:
+                    # the single-row kernels (csrc/decode.hip) stop at 8 heads: declined here, at construction -- whatever the other blocks
+                    # of the stack are -- and not by a launch in mid-sampling
+                    raise NotImplementedError(f'IncrementalDecoder: no single-row path for {type(inner).__name__} with {inner.heads} heads (up to 8)')
                 blk.kind = 's3'
                 blk.geom = K.s3_geom(batch, max_rows, *grid, inner.heads, inner.dim_head)
                 blk.kvcache = K.zeros_bf((batch, max_rows, 2 * inner.heads * inner.dim_head), dev, lo=lo)

@@ -504,6 +504,9 @@ class Attention(nn.Module):
         return self.to_out(out)
 
 
+S3_MAX_HEADS = 8          # every Sparse3DNA kernel of the library (window, band, single-row decode) stops here
+
+
 class Sparse3DNA(nn.Module):
     """np.py:381-613.  forward = qkv GEMM -> fused gfx950 3DNA kernel (no unfold materialisation) -> to_out GEMM, for the causal
     window of the video decoder AND the symmetric window of NUWASketch's sketch encoder (causal=False, np.py:429: the same kernels
@@ -558,6 +561,11 @@ class Sparse3DNA(nn.Module):
 
     def _meta(self, B, n, device, **_):
         assert n - 1 <= self.max_num_tokens, 'sequence longer than the video shape allows'
+        if self.heads > S3_MAX_HEADS:
+            # the causal window has no PyTorch-op formulation to fall back to: say so here, by name, instead of letting the library's
+            # AMDNUWA_ERR_UNSUPPORTED surface from the first launch (the symmetric window never gets here: _hip_ok keeps it on torch ops)
+            raise NotImplementedError(f'causal Sparse3DNA with {self.heads} heads: the window kernels take up to {S3_MAX_HEADS} heads '
+                                      f'(dim_head 32 / 64)')
         g = K.s3_geom(B, n, self.video_shape, self.kernel_size, self.dilation, self.heads, self.dim_head, causal=self.causal)
         meta = dict(kind='s3', cache=self._cache, geom=g)
         if self.training and self.dropout.p > 0:
@@ -569,8 +577,9 @@ class Sparse3DNA(nn.Module):
 
     def _hip_ok(self):
         """geometry the 3DNA kernels take: head size 32 / 64, up to 8 heads, feature maps up to 64 wide (rows of more than 128 / heads
-        columns run in column tiles).  The causal decoder path never falls back (an unsupported shape raises from the library); the
-        symmetric variant keeps its PyTorch-op formulation for head sizes / widths / windows outside the kernels"""
+        columns run in column tiles).  The causal decoder path never falls back (more than 8 heads is a NotImplementedError from _meta
+        that names the limit; any other unsupported shape raises from the library); the symmetric variant keeps its PyTorch-op
+        formulation for head counts / head sizes / widths / windows outside the kernels"""
         if self.causal:
             return True
         if self.training and self.dropout.p > 0:
