@@ -364,7 +364,7 @@ typedef struct {
     int F, H, W;            /* token grid (max_frames, fmap, fmap) */
     int kf, kh, kw;         /* kernel size */
     int df, dh, dw;         /* dilation */
-    int heads, dim_head;    /* heads 1..8; dim_head in {32, 64}; W*heads*4 <= 512 (one workgroup per grid row) or W <= 64 (column tiles) */
+    int heads, dim_head;    /* heads 1..8 (9..16: the amdnuwa_sparse3dna_mh_* entries); dim_head in {32, 64}; W*heads*4 <= 512 (one workgroup per grid row) or W <= 64 (column tiles) */
     float scale;            /* dim_head ** -0.5 */
     /* relative-position bias (Sparse3DNA(rel_pos_bias=True), np.py:512-516, 542): rel_bias[j][head] is added to the score of
      * key slot j (j = 0 is <bos>: pass 0 there), fp32 [kf*kh*kw + 1][heads] or NULL.  The backward writes its gradient
@@ -416,6 +416,24 @@ int amdnuwa_sparse3dna_bwd_f16(const amdnuwa_s3_geom* g, const uint16_t* q_f16, 
                                const float* w_th, const uint16_t* dO_f16, int lddo, uint16_t* dq_f16, uint16_t* dk_f16, uint16_t* dv_f16,
                                int ldd, float* dw_th, int accumulate, const float* scale2, void* workspace, size_t workspace_bytes,
                                amdnuwa_stream stream);
+/* Many-head form of the causal window (additive, ABI unchanged): 9 .. 16 heads on VALU kernels of their own (csrc/sparse3dna_mh.hip),
+ * every geometry in column tiles of at most floor(128 / heads) columns.  Argument lists, operand forms (bf16, or hi + lo pairs when the
+ * lo pointers are given), workspace layout, return codes and their order are those of amdnuwa_sparse3dna_fwd / _bwd, rel_bias /
+ * d_rel_bias of the geometry included.  Envelope: heads 9 .. 16, dim_head 32 / 64, causal only (g->noncausal == 0), W <= 64, and the
+ * tile's LDS tables within the CU's 160 KiB: amdnuwa_s3mh_supported() says whether it applies, the entries answer
+ * AMDNUWA_ERR_UNSUPPORTED outside it -- for heads <= 8 too, which amdnuwa_sparse3dna_fwd / _bwd serve.  No fp16 operand form, no
+ * fp16-gradient form, no masked (attention dropout) form, no SparseCross2DNA form, no cached decoding. */
+int amdnuwa_s3mh_supported(const amdnuwa_s3_geom* g, int lo_operands);
+size_t amdnuwa_sparse3dna_mh_bwd_workspace_bytes(const amdnuwa_s3_geom* g);
+int amdnuwa_sparse3dna_mh_fwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                              const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                              const float* w_th, uint16_t* o, uint16_t* o_lo, int ldo, amdnuwa_stream stream);
+int amdnuwa_sparse3dna_mh_bwd(const amdnuwa_s3_geom* g, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                              const uint16_t* q_lo, const uint16_t* k_lo, const uint16_t* v_lo, int ld,
+                              const float* w_th, const uint16_t* dO, const uint16_t* dO_lo, int lddo, uint16_t* dq,
+                              uint16_t* dk, uint16_t* dv, uint16_t* dq_lo, uint16_t* dk_lo, uint16_t* dv_lo, int ldd,
+                              float* dw_th, int accumulate, void* workspace, size_t workspace_bytes,
+                              amdnuwa_stream stream);
 /* Attention dropout inside the causal window (the `self.dropout(attn)` of reference nuwa_pytorch.py:554-564, Sparse3DNA, and 746-752,
  * SparseCausal2DNA as a (time, 1, 1) grid; additive at ABI 21).  With P = softmax over the J slots and P' = W_th . P, the V product and dV take
  * P'' = keep . P' . drop_scale, and the backward takes dP' = keep . (dO . V^T) . drop_scale; everything below dP' is amdnuwa_sparse3dna_bwd's.

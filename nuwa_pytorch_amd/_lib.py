@@ -114,6 +114,10 @@ SIGNATURES = {
     'amdnuwa_sparse3dna_bwd': (I, [SG, P, P, P, P, P, P, I, P, P, P, I, P, P, P, P, P, P, I, P, I, P, SZ, P]),
     'amdnuwa_sparse3dna_bwd_f16_supported': (I, [SG]),
     'amdnuwa_sparse3dna_bwd_f16': (I, [SG, P, P, P, I, P, P, I, P, P, P, I, P, I, P, P, SZ, P]),
+    'amdnuwa_s3mh_supported': (I, [SG, I]),
+    'amdnuwa_sparse3dna_mh_bwd_workspace_bytes': (SZ, [SG]),
+    'amdnuwa_sparse3dna_mh_fwd': (I, [SG, P, P, P, P, P, P, I, P, P, P, I, P]),
+    'amdnuwa_sparse3dna_mh_bwd': (I, [SG, P, P, P, P, P, P, I, P, P, P, I, P, P, P, P, P, P, I, P, I, P, SZ, P]),
     'amdnuwa_s3_drop_supported': (I, [SG, I]),
     'amdnuwa_sparse3dna_fwd_drop': (I, [SG, P, P, P, P, P, P, I, P, P, P, I, P, F, P]),
     'amdnuwa_sparse3dna_bwd_drop': (I, [SG, P, P, P, P, P, P, I, P, P, P, I, P, P, P, P, P, P, I, P, I, P, SZ, P, F, P]),

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libamdnuwa.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'amdnuwa.h')
-SOURCES = ['api.hip', 'gemm.hip', 'elementwise.hip', 'dropout.hip', 'keepmask.hip', 'sparse3dna.hip', 'sparse3dna_wide.hip', 'xattn.hip', 'xattn2.hip', 'xattn6.hip', 'cattn.hip', 'vae.hip', 'optim.hip', 'decode.hip', 'sample.hip', 'comm.hip']
+SOURCES = ['api.hip', 'gemm.hip', 'elementwise.hip', 'dropout.hip', 'keepmask.hip', 'sparse3dna.hip', 'sparse3dna_wide.hip', 'sparse3dna_mh.hip', 'xattn.hip', 'xattn2.hip', 'xattn6.hip', 'cattn.hip', 'vae.hip', 'optim.hip', 'decode.hip', 'sample.hip', 'comm.hip']
 # One generic `gfx950` code object (loads whatever the device's XNACK mode).  Measured at the end of round 6 (profiles/r06zn_xnack_ab.txt): a code object built for
 # XNACK-off devices only (AMDNUWA_BUILD_ARCH=gfx950:xnack-) runs the step 0.5 % faster in an A/B/A/B of one call (457.0 -> 454.4 ms: the generic object must stay
 # safe under XNACK replay, e.g. a load's destination may not overlap its address registers) -- an opt-in for deployments that never enable demand paging; it
@@ -76,7 +76,7 @@ def build(force=False, verbose=True, variant=''):
     vflags = VARIANTS[variant] if variant in VARIANTS else variant.split()
     os.makedirs(LIBDIR, exist_ok=True)
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
-    common = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 's3_args.h'), HEADER]
+    common = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 's3_args.h'), os.path.join(CSRC, 's3mh_index.h'), HEADER]
     objs, jobs = [], []
     for s in srcs:
         src = os.path.join(CSRC, s)

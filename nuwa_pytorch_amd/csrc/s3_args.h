@@ -90,6 +90,13 @@ template <class F> int s3_dispatch(int dim_head, bool lo, bool drop, F&& f) {
 // keep != NULL launches the masked (DROP) forms of the forward and of the query-side backward
 int s3w_fwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds, const uint8_t* keep, float drop_s, hipStream_t stream);
 int s3w_bwd_launch(const S3Args& a, int dim_head, bool lo, size_t lds_q, size_t lds_kv, const uint8_t* keep, float drop_s, hipStream_t stream);
+// host-side pieces of sparse3dna.hip that the many-head entry points (sparse3dna_mh.hip, 9 .. 16 heads, causal) reuse, generic in the head count:
+// bytes of the backward workspace (the s3_ws() map); geometry fields of `a` for the causal self-attention window (tile fields from s3_tile());
+// slot-0 key / value = the <bos> row, and (workspace != NULL) the workspace pointers; final sums of the backward + the d(rel_bias) column sums
+size_t s3_ws_bytes(const amdnuwa_s3_geom* g);
+void s3_fill_causal(S3Args& a, const amdnuwa_s3_geom* g);
+void s3_bind_self(S3Args& a, const amdnuwa_s3_geom* g, void* workspace);
+int s3_bwd_tail(const S3Args& a, const amdnuwa_s3_geom* g, void* workspace, hipStream_t stream);
 
 namespace {
 

@@ -3144,6 +3144,25 @@ extern "C" int amdnuwa_sparse3dna_bwd_drop(const amdnuwa_s3_geom* g, const uint1
                       workspace, workspace_bytes, {true, keep, drop_scale}, stream);
 }
 
+// What the many-head entry points (sparse3dna_mh.hip, 9 .. 16 heads) share with the ones above, all of it generic in the head count: the
+// geometry fill, the workspace map, and the tail of the backward (final sums + the column sums of d(rel_bias)).  Host code only.
+size_t s3_ws_bytes(const amdnuwa_s3_geom* g) { return s3_ws(g).bytes; }
+void s3_fill_causal(S3Args& a, const amdnuwa_s3_geom* g) { fill_geom(a, g, S3Route{}); }
+void s3_bind_self(S3Args& a, const amdnuwa_s3_geom* g, void* workspace) {
+    self_kv(a);
+    if (workspace) bind_ws(a, g, workspace);
+}
+int s3_bwd_tail(const S3Args& a, const amdnuwa_s3_geom* g, void* workspace, hipStream_t stream) {
+    hipLaunchKernelGGL(s3_bwd_fin_kernel, dim3(g->B * ((g->heads * g->dim_head + 63) / 64) + (g->heads * g->heads + 15) / 16), dim3(1024), 0, stream, a, g->dim_head);
+    LAUNCH_CHECK();
+    if (g->d_rel_bias) {         // as in s3_bwd_run
+        const long long rows = (long long)g->B * (g->ntok - 1);
+        const int cols = (int)(s3_slots(g) * g->heads);
+        return amdnuwa_colsum(a.ds, g->d_rel_bias, rows, cols, 0, (float*)workspace + s3_ws(g).colsum, amdnuwa_colsum_workspace_bytes(rows, cols), stream);
+    }
+    return AMDNUWA_OK;
+}
+
 // fp16-gradient form of the backward ('bf16x3-fwd' with block class 's' of AMDNUWA_BWD_F16): q / k / v are the fp16 copies the forward core
 // read (the ONLY 16-bit copies the block keeps), dO = fp16(S dO), dq / dk / dv leave as fp16(S gradient), dW_th as fp32 without the factor.
 // scale2 = device {S, 1 / S}.  AMDNUWA_ERR_UNSUPPORTED outside amdnuwa_sparse3dna_bwd_f16_supported().

@@ -1190,6 +1190,52 @@ def sparse3dna_bwd(g, qkv, wth, dO, rel_bias=None, keep=None, drop_scale=1.0):
     return dqkv, dwth, drel
 
 
+S3_MAX_HEADS = 8            # the window, band and single-row decode kernels of sparse3dna.hip / sparse3dna_wide.hip / decode.hip stop here
+S3MH_MAX_HEADS = 16         # the many-head window kernels of sparse3dna_mh.hip: S3_MAX_HEADS + 1 .. 16 heads, causal, full sequences only
+
+
+def s3mh_supported(g, lo=None):
+    """do the many-head window kernels (9 .. 16 heads, causal, dim_head 32 / 64, W <= 64, LDS tables within the CU) take this geometry?"""
+    lo = (get_precision() != 'bf16') if lo is None else lo
+    return bool(_lib.lib().amdnuwa_s3mh_supported(C.byref(g), 1 if lo else 0))
+
+
+@_family('s3', _s3_work('fwd'))
+def sparse3dna_mh_fwd(g, qkv, wth, rel_bias=None):
+    """sparse3dna_fwd for 9 .. 16 heads: qkv BF [B*ntok, 3*inner] (bf16, or hi + lo pairs) -> o BF [B*ntok, inner].  No fp16 operand form,
+    no keep mask"""
+    g.rel_bias, g.d_rel_bias = _p(rel_bias), None
+    inner = g.heads * g.dim_head
+    R = g.B * g.ntok
+    o = empty_bf((R, inner), qkv.hi.device, lo=qkv.lo is not None)
+    q, k, v = (view(qkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
+    _s3_call('amdnuwa_sparse3dna_mh_fwd', [C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
+                                           _p(wth), _p(o.hi), _p(o.lo), inner], None, 1.0)
+    return o
+
+
+@_family('s3', _s3_work('bwd'))
+def sparse3dna_mh_bwd(g, qkv, wth, dO, rel_bias=None):
+    """sparse3dna_bwd for 9 .. 16 heads: returns (dqkv BF [R, 3*inner], dw_th fp32 [h, h], d(rel_bias) fp32 [J, heads] or None)"""
+    L = _lib.lib()
+    drel = torch.empty_like(rel_bias) if rel_bias is not None else None
+    g.rel_bias, g.d_rel_bias = _p(rel_bias), _p(drel)
+    inner = g.heads * g.dim_head
+    R = g.B * g.ntok
+    dev = qkv.hi.device
+    dqkv = empty_bf((R, 3 * inner), dev, lo=qkv.lo is not None)
+    dwth = torch.empty((g.heads, g.heads), dtype=torch.float32, device=dev)
+    q, k, v = (view(qkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
+    dq, dk, dv = (view(dqkv, cols=slice(i * inner, (i + 1) * inner)) for i in range(3))
+    nb = L.amdnuwa_sparse3dna_mh_bwd_workspace_bytes(C.byref(g))
+    ws = workspace(nb, dev)
+    _s3_call('amdnuwa_sparse3dna_mh_bwd', [C.byref(g), _p(q.hi), _p(k.hi), _p(v.hi), _p(q.lo), _p(k.lo), _p(v.lo), qkv.hi.stride(0),
+                                           _p(wth), _p(dO.hi), _p(dO.lo), dO.hi.stride(0), _p(dq.hi), _p(dk.hi), _p(dv.hi),
+                                           _p(dq.lo), _p(dk.lo), _p(dv.lo), dqkv.hi.stride(0), _p(dwth), 0, _p(ws), nb], None, 1.0)
+    g.d_rel_bias = None
+    return dqkv, dwth, drel
+
+
 def cross2dna_drop_supported(g, lo=None):
     """do the masked (attention dropout) forms of the SparseCross2DNA kernels take this geometry in the current precision mode?"""
     lo = (get_precision() != 'bf16') if lo is None else lo

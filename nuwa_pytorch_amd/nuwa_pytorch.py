@@ -504,14 +504,21 @@ class Attention(nn.Module):
         return self.to_out(out)
 
 
-S3_MAX_HEADS = 8          # every Sparse3DNA kernel of the library (window, band, single-row decode) stops here
+S3_MAX_HEADS = K.S3_MAX_HEADS     # the window, band and single-row decode kernels stop here; Sparse3DNA.many_heads goes on to K.S3MH_MAX_HEADS
 
 
 class Sparse3DNA(nn.Module):
     """np.py:381-613.  forward = qkv GEMM -> fused gfx950 3DNA kernel (no unfold materialisation) -> to_out GEMM, for the causal
     window of the video decoder AND the symmetric window of NUWASketch's sketch encoder (causal=False, np.py:429: the same kernels
     with the tap origin in the middle of the window).  `query_num_frames_chunk` only bounds the reference's unfolded tensors; it is
-    accepted and ignored (chunked == unchunked bit for bit in the reference)."""
+    accepted and ignored (chunked == unchunked bit for bit in the reference).
+
+    `many_heads = True` (class or instance attribute, off by default) lets the causal window run with 9 .. 16 heads on the many-head VALU
+    kernels (csrc/sparse3dna_mh.hip): bf16 hi[/lo] operands, no fp16 core, no attention dropout, full sequences only -- training, and
+    generate() on the recompute loop; the cached decoder keeps declining such a block.  With it off, more than 8 heads is the
+    NotImplementedError of `_meta`."""
+
+    many_heads = False
 
     def __init__(self, dim, video_shape, kernel_size=3, dilation=1, heads=8, dim_head=64, dropout=0., causal=False,
                  query_num_frames_chunk=None, rel_pos_bias=False):
@@ -561,12 +568,25 @@ class Sparse3DNA(nn.Module):
 
     def _meta(self, B, n, device, **_):
         assert n - 1 <= self.max_num_tokens, 'sequence longer than the video shape allows'
-        if self.heads > S3_MAX_HEADS:
+        if self.heads > S3_MAX_HEADS and not (self.many_heads and self.causal):
             # the causal window has no PyTorch-op formulation to fall back to: say so here, by name, instead of letting the library's
             # AMDNUWA_ERR_UNSUPPORTED surface from the first launch (the symmetric window never gets here: _hip_ok keeps it on torch ops)
             raise NotImplementedError(f'causal Sparse3DNA with {self.heads} heads: the window kernels take up to {S3_MAX_HEADS} heads '
-                                      f'(dim_head 32 / 64)')
+                                      f'(dim_head 32 / 64); Sparse3DNA.many_heads = True opts into the many-head VALU kernels '
+                                      f'({S3_MAX_HEADS + 1} .. {K.S3MH_MAX_HEADS} heads, training and recompute-loop generation)')
         g = K.s3_geom(B, n, self.video_shape, self.kernel_size, self.dilation, self.heads, self.dim_head, causal=self.causal)
+        if self.heads > S3_MAX_HEADS:
+            # many_heads: the kernels of csrc/sparse3dna_mh.hip.  What they do not take is refused here, by name, before anything is launched
+            if self.heads > K.S3MH_MAX_HEADS:
+                raise NotImplementedError(f'causal Sparse3DNA with {self.heads} heads: the many-head window kernels take up to '
+                                          f'{K.S3MH_MAX_HEADS} heads')
+            if self.training and self.dropout.p > 0:
+                raise NotImplementedError(f'causal Sparse3DNA with {self.heads} heads and attention dropout: the many-head window kernels '
+                                          f'have no masked form (attn_dropout = 0, or up to {S3_MAX_HEADS} heads)')
+            if not K.s3mh_supported(g):
+                raise NotImplementedError(f'causal Sparse3DNA with {self.heads} heads: the many-head window kernels do not take this geometry '
+                                          f'(dim_head {self.dim_head}: 32 / 64; width {self.video_shape[2]}: up to 64; window {tuple(self.kernel_size)} '
+                                          f'x dilation {tuple(self.dilation)}: its key-slot tables must fit the LDS)')
         meta = dict(kind='s3', cache=self._cache, geom=g)
         if self.training and self.dropout.p > 0:
             # attention dropout in training (np.py:558): the masked window kernels (ops.S3Inner draws the mask from torch's RNG stream).  Causal

@@ -277,6 +277,9 @@ class S3Inner:
         's'): that, the two-MFMA to_out, no relative-position bias, and the band kernels and the five backward products take the shapes"""
         wq, wkv, wo = S3Inner.guarded(p)
         g, inner = meta['geom'], wq.shape[0]
+        if g.heads > K.S3_MAX_HEADS:
+            # many heads (Sparse3DNA.many_heads): the VALU kernels of sparse3dna_mh.hip on bf16 hi[/lo] operands, nothing else
+            return Plan(guarded=(wq, wkv, wo))
         if meta.get('drop_p') and not K.s3_f16_supported(g):
             # live attention dropout off the band geometry: the masked core is the VALU window kernels on bf16 hi[/lo] operands -- no fp16
             # core (and so no fp16 projections around it), no fp16-gradient backward.  At band geometry the band kernels have masked forms in
@@ -320,7 +323,10 @@ class S3Inner:
             h = _f16_to_pair(h)
             qkv = K.gemm_nt(h, W['qkv'], out_bf16=True, shift=meta.get('shift'), out_f16=pl.core16)
         # two-MFMA to_out (o16): the fp16 core hands its output over as a bf16 copy (backward) + an fp16 copy (this product's A operand)
-        o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel, o_f16=pl.o16, **dkw)
+        if g.heads > K.S3_MAX_HEADS:
+            o = K.sparse3dna_mh_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel)
+        else:
+            o = K.sparse3dna_fwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), rel_bias=rel, o_f16=pl.o16, **dkw)
         y = K.gemm_nt_f16x2(o.f16, W['out_16'], bias=bo.detach()) if pl.o16 else K.gemm_nt(o, W['out'], bias=bo.detach(), out_bf16=_fast())
         return y, tuple(_sv(h, qkv, o)) + tail
 
@@ -348,8 +354,11 @@ class S3Inner:
         d_o = K.gemm_nt(dy, W['outT'], out_bf16=True)
         dwo = torch.empty_like(wo)
         K.gemm_tn(dy, o, dwo)
-        dqkv, dwth, drel = K.sparse3dna_bwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), d_o, rel_bias=rel, keep=keep,
-                                            drop_scale=1.0 / (1.0 - float(meta['drop_p'])) if keep is not None else 1.0)
+        if g.heads > K.S3_MAX_HEADS:
+            dqkv, dwth, drel = K.sparse3dna_mh_bwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), d_o, rel_bias=rel)
+        else:
+            dqkv, dwth, drel = K.sparse3dna_bwd(g, qkv, wth.detach().reshape(g.heads, g.heads).contiguous(), d_o, rel_bias=rel, keep=keep,
+                                                drop_scale=1.0 / (1.0 - float(meta['drop_p'])) if keep is not None else 1.0)
         dh = K.gemm_nt(dqkv, W['qkvT'], out_bf16=_fast_bwd())
         sh = meta.get('shift')
         dwqkv = torch.empty((3 * inner, wq.shape[1]), dtype=torch.float32, device=wq.device)   # one wgrad GEMM for [to_q; to_kv]
