@@ -929,7 +929,11 @@ typedef struct {
     float bias_correction1, bias_correction2;   /* 1 - beta^t with t = number of updates THIS parameter has received (torch keeps
                                                     the step count per parameter: one skipped for lack of a gradient lags behind) */
 } amdnuwa_adamw_chunk;
-/* out2[0] = global L2 norm of all gradients, out2[1] = min(1, max_norm / (norm + 1e-6)) (1 if max_norm <= 0); fixed-order
+/* Alignment: p, g, m and v need the 4-byte alignment of a float and nothing more.  A chunk whose pointers all lie on 16-byte borders
+ * (g alone for amdnuwa_grad_norm) runs the float4 loops; any other chunk -- a gradient that is a view at an odd element offset of a
+ * flat bucket, say -- runs the same arithmetic on float accesses, the same elements in the same order, with bit-identical results.  The test
+ * is per chunk, so keep tensors of more than 65536 elements on 16-byte borders as a whole (chunk k starts 262144 k bytes in). */
+/* out2[0] = global L2 norm of all gradients, out2[1] = min(1, max_norm / (norm + 1e-6)) (1 if max_norm <= 0; NaN if the norm is); fixed-order
  * reduction; partials: nchunks floats of scratch.  Everything stays on the device. */
 int amdnuwa_grad_norm(const amdnuwa_adamw_chunk* chunks, int nchunks, float max_norm, float* partials, float* out2,
                       amdnuwa_stream stream);

@@ -15,15 +15,27 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// chunk-uniform: every pointer given is on a 16-byte border (the float4 loops below need that; amdnuwa.h states the contract)
+__device__ __forceinline__ bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+    return (((unsigned long long)a | (unsigned long long)b | (unsigned long long)c | (unsigned long long)d) & 15ULL) == 0;
+}
+
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const amdnuwa_adamw_chunk* __restrict__ ch, float* __restrict__ partials) {
     __shared__ float red[4];
     const amdnuwa_adamw_chunk c = ch[blockIdx.x];
     float s = 0.f;
     if (c.g) {
         const long long n4 = c.n & ~3LL;
-        for (long long i = (long long)threadIdx.x * 4; i < n4; i += 1024) {
-            const float4 g = *reinterpret_cast<const float4*>(c.g + i);
-            s += (g.x * g.x + g.y * g.y) + (g.z * g.z + g.w * g.w);
+        auto add4 = [&](float x, float y, float z, float w) { s += (x * x + y * y) + (z * z + w * w); };
+        if (aligned16(c.g)) {
+            for (long long i = (long long)threadIdx.x * 4; i < n4; i += 1024) {
+                const float4 g = *reinterpret_cast<const float4*>(c.g + i);
+                add4(g.x, g.y, g.z, g.w);
+            }
+        } else {
+            // a gradient that is a view at an odd element offset of a flat bucket: four scalar loads per step, the SAME elements per
+            // thread in the SAME order, so the norm does not depend on where the gradient lies
+            for (long long i = (long long)threadIdx.x * 4; i < n4; i += 1024) add4(c.g[i], c.g[i + 1], c.g[i + 2], c.g[i + 3]);
         }
         for (long long i = n4 + threadIdx.x; i < c.n; i += 256) s += c.g[i] * c.g[i];
     }
@@ -45,7 +57,9 @@ __global__ __launch_bounds__(1024) void grad_norm_finalize_kernel(const float* _
     if (threadIdx.x == 0) {
         const float norm = sqrtf(red[0]);
         out[0] = norm;
-        out[1] = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;
+        // (a NaN norm gives a NaN coefficient, as torch's clamp does: fminf would hide it behind 1 and let every finite gradient through)
+        const float q = max_norm / (norm + 1e-6f);
+        out[1] = max_norm > 0.f ? (q >= 1.f ? 1.f : q) : 1.f;
     }
 }
 
@@ -72,12 +86,28 @@ __global__ __launch_bounds__(256) void adamw_kernel(const amdnuwa_adamw_chunk* _
         v = b2 * v + (1.f - b2) * g * g;
         p -= step * (m / (sqrtf(v) / sqrt_bias_c2 + eps));     // addcdiv_(exp_avg, sqrt(v) / sqrt(bc2) + eps, value = -lr / bc1)
     };
-    const long long n4 = c.n & ~3LL;
-    for (long long i = (long long)threadIdx.x * 4; i < n4; i += 1024) {
-        float4 p = *reinterpret_cast<float4*>(c.p + i), m = *reinterpret_cast<float4*>(c.m + i), v = *reinterpret_cast<float4*>(c.v + i);
-        const float4 g = *reinterpret_cast<const float4*>(c.g + i);
+    auto upd4 = [&](float4& p, const float4& g, float4& m, float4& v) {
         upd(p.x, g.x, m.x, v.x); upd(p.y, g.y, m.y, v.y); upd(p.z, g.z, m.z, v.z); upd(p.w, g.w, m.w, v.w);
-        *reinterpret_cast<float4*>(c.p + i) = p; *reinterpret_cast<float4*>(c.m + i) = m; *reinterpret_cast<float4*>(c.v + i) = v;
+    };
+    const long long n4 = c.n & ~3LL;
+    // float4 accesses only when p, g, m and v of the chunk are all on 16-byte borders; otherwise scalar loads and stores around the SAME
+    // four-element body, so the result does not depend on where the tensors lie
+    if (aligned16(c.p, c.g, c.m, c.v)) {
+        for (long long i = (long long)threadIdx.x * 4; i < n4; i += 1024) {
+            float4 p = *reinterpret_cast<float4*>(c.p + i), m = *reinterpret_cast<float4*>(c.m + i), v = *reinterpret_cast<float4*>(c.v + i);
+            const float4 g = *reinterpret_cast<const float4*>(c.g + i);
+            upd4(p, g, m, v);
+            *reinterpret_cast<float4*>(c.p + i) = p; *reinterpret_cast<float4*>(c.m + i) = m; *reinterpret_cast<float4*>(c.v + i) = v;
+        }
+    } else {
+        auto ld = [](const float* a) { return make_float4(a[0], a[1], a[2], a[3]); };
+        auto st = [](float* a, const float4& x) { a[0] = x.x; a[1] = x.y; a[2] = x.z; a[3] = x.w; };
+        for (long long i = (long long)threadIdx.x * 4; i < n4; i += 1024) {
+            float4 p = ld(c.p + i), m = ld(c.m + i), v = ld(c.v + i);
+            const float4 g = ld(c.g + i);
+            upd4(p, g, m, v);
+            st(c.p + i, p); st(c.m + i, m); st(c.v + i, v);
+        }
     }
     for (long long i = n4 + threadIdx.x; i < c.n; i += 256) upd(c.p[i], c.g[i], c.m[i], c.v[i]);
 }

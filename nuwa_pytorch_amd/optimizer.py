@@ -26,6 +26,19 @@ class _Chunk(C.Structure):                       # == amdnuwa_adamw_chunk
                 ('weight_decay', C.c_float), ('bias_correction1', C.c_float), ('bias_correction2', C.c_float)]
 
 
+def chunk_layout(numels):
+    """the chunk table's geometry as a function of the tensors' element counts alone -> (owner, byte offset inside the tensor, n), one entry
+    per chunk: tensor i gives ceil(numel_i / CHUNK) consecutive chunks of CHUNK elements, the last one ragged"""
+    numel = np.asarray(list(numels), dtype=np.int64)
+    counts = -(-numel // CHUNK)
+    nchunks = int(counts.sum())
+    owner = np.repeat(np.arange(len(numel)), counts)                              # chunk -> parameter index
+    first = np.concatenate(([0], np.cumsum(counts)[:-1])).astype(np.int64)
+    off = (np.arange(nchunks) - np.repeat(first, counts)).astype(np.uint64) * np.uint64(4 * CHUNK)
+    n = np.minimum(CHUNK, numel[owner] - (off // np.uint64(4)).astype(np.int64))
+    return owner, off, n
+
+
 def separate_weight_decayable_params(params):
     """optimizer.py:6-9"""
     no_wd = [p for p in params if p.ndim < 2]
@@ -64,17 +77,13 @@ class FusedAdamW(torch.optim.Optimizer):
         self._dtype = np.dtype([('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('n', '<i8'), ('weight_decay', '<f4'),
                                 ('bias_correction1', '<f4'), ('bias_correction2', '<f4')], align=True)
         assert self._dtype.itemsize == C.sizeof(_Chunk)
-        counts = np.array([-(-p.numel() // CHUNK) for p in self.params])
-        self.nchunks = int(counts.sum())
-        self._owner = np.repeat(np.arange(len(self.params)), counts)                 # chunk -> parameter index
-        first = np.concatenate(([0], np.cumsum(counts)[:-1]))
-        self._off = (np.arange(self.nchunks) - np.repeat(first, counts)).astype(np.uint64) * np.uint64(4 * CHUNK)   # byte offset inside the tensor
-        numel = np.array([p.numel() for p in self.params], dtype=np.int64)
+        self._owner, self._off, n = chunk_layout(p.numel() for p in self.params)
+        self.nchunks = len(self._owner)
         H = np.zeros(self.nchunks, dtype=self._dtype)
         H['p'] = np.array([p.data_ptr() for p in self.params], dtype=np.uint64)[self._owner] + self._off
         H['m'] = np.array([t.data_ptr() for t in self.state_m], dtype=np.uint64)[self._owner] + self._off
         H['v'] = np.array([t.data_ptr() for t in self.state_v], dtype=np.uint64)[self._owner] + self._off
-        H['n'] = np.minimum(CHUNK, numel[self._owner] - (self._off // np.uint64(4)).astype(np.int64))
+        H['n'] = n
         self._host = H
         self._pptr = [p.data_ptr() for p in self.params]
         self._table = torch.empty(self.nchunks * self._dtype.itemsize, dtype=torch.uint8, device=self.device)
@@ -125,7 +134,9 @@ class FusedAdamW(torch.optim.Optimizer):
         self._bind_state()
 
     def _upload(self, advance=False):
-        b1, b2 = self.betas
+        # the entry point takes the betas as floats and forms 1 - beta itself: the bias corrections come from those SAME fp32-rounded
+        # betas (held as doubles for the power), so the step is an exact AdamW for (float(b1), float(b2)) and not a mix of two pairs
+        b1, b2 = (float(np.float32(b)) for b in self.betas)
         gp = np.zeros(len(self.params), dtype=np.uint64)
         for i, p in enumerate(self.params):
             g = p.grad
@@ -169,6 +180,9 @@ class FusedAdamW(torch.optim.Optimizer):
                                            self._norm.data_ptr(), st), 'amdnuwa_grad_norm')
             clip = self._norm.data_ptr() + 4
         _lib.check(L.amdnuwa_adamw_step(self._table.data_ptr(), self.nchunks, lr, b1, b2, eps, clip, st), 'amdnuwa_adamw_step')
+        for i, p in enumerate(self.params):
+            if p.grad is not None:
+                self.state[p]['step'] = torch.tensor(float(self.param_steps[i]))
         torch.autograd.graph.increment_version([p for p in self.params if p.grad is not None])   # written behind autograd's back
         ops.weights_changed()                    # the operand copies of the weights and their fp16 range verdicts are stale now
         return loss
